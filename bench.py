@@ -6,7 +6,17 @@ the parity chunks plus SHA-256 of all d+p chunks (FilePart::write_with_encoder's
 reference src/file/file_part.rs:150-185), over BASELINE.json configs[1]'s shape: 4096 parts x
 10 data chunks x 1 MiB on each GPU, inputs already resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4] [--full]
+                  [--dump-outputs DIR]
+
+A plain run does only what its headline needs: it fills the buffers, runs W warmup and K timed
+steps, and prints the line (`value`, `ms_per_step`, and the `roofline` / `kernels` figures taken
+from the timed steps' own events).  `--full` adds everything else described below: c2's
+`north_star`, `baseline_configs` and `end_to_end` blocks, `check_vs_oracle`, `cpu_baseline`, and
+c3e2's `also_reconstruct`.  `--dump-outputs DIR` writes what the last timed step left for its
+caller (the parity chunks and digests of c2; the rebuilt chunks of the reconstruct configs) as
+float32 DIR/<name>.npy, a fixed seeded sample where an array is large; the inputs are the same
+from run to run, so two builds can be compared output for output.
 
 For N > 1 one rank runs per GPU under torch.distributed.run: the driver's launcher, or, when
 `--gpus N` is given with no WORLD_SIZE in the environment, this script starts it itself as a child
@@ -16,15 +26,15 @@ process group carries only the barrier, the max-over-ranks step time and the per
 `check_vs_oracle` (each rank's own sampled parts vs the oracle) is ANDed into the line's.
 
 Rank 0 prints ONE JSON line.  `roofline` describes the dominant kernel, timed with HIP events
-on the stream its launches go to; `cpu_baseline` times the CPU restatement of the reference
-crates (oracle/, the same scalar galois_8 table path + SHA-256 with SHA-NI like sha2 0.9.9's
-cpufeatures dispatch) on this host's cores over a bounded sample of the same workload.
+on the stream its launches go to; `cpu_baseline` (`--full`) times the CPU restatement of the
+reference crates (oracle/, the same scalar galois_8 table path + SHA-256 with SHA-NI like sha2
+0.9.9's cpufeatures dispatch) on this host's cores over a bounded sample of the same workload.
 
-The default (c2) line also carries: `north_star` (RS(10,4) encode and 2-erasure reconstruct_data
-on the headline's buffer, fractions of 8 TB/s), `baseline_configs` (BASELINE configs[2] C3 and
-configs[3] C4 per GPU), `end_to_end` (host-produced write stream, read + repair stream with
-damaged fetches retried, the PCIe link alone, the one-process scheduler path), and at N = 1
-`check_vs_oracle` (every part of the C2 and C4 buffers and of the end-to-end write stream
+With `--full` the default (c2) line also carries: `north_star` (RS(10,4) encode and 2-erasure
+reconstruct_data on the headline's buffer, fractions of 8 TB/s), `baseline_configs` (BASELINE
+configs[2] C3 and configs[3] C4 per GPU), `end_to_end` (host-produced write stream, read + repair
+stream with damaged fetches retried, the PCIe link alone, the one-process scheduler path), and
+at N = 1 `check_vs_oracle` (every part of the C2 and C4 buffers and of the end-to-end write stream
 against the oracle, plus whole sampled parts of each block).  At N > 1: `ranks` (each rank's own
 figures) and `node` (configs[3] and C3 at node level).  `--config c5` / `c5r` run BASELINE
 configs[4]: a `--stream-gib` (1 TiB) stream fed per batch from pageable rings, written, or read
@@ -447,8 +457,45 @@ def read_repair_flags():
     return ce.ReadPipeline.REBUILT_ONLY | (ce.ReadPipeline.CARRY if bench_carry() else 0)
 
 
+DUMP_LIMIT = 4 << 20  # elements per dumped array (float32: 16 MiB; a run dumps at most three)
+DUMP_WINDOW = 64      # a read-repair stream's dump: this many bytes at the head of every chunk
+
+
+def dump_array(out_dir, name, arr, rank=0, seed=0xD0D0):
+    """--dump-outputs: `arr` (a contiguous torch tensor or numpy array of bytes / flags) as float32
+    in out_dir/<name>.npy (rank r > 0: <name>_rank<r>.npy).  An array of more than DUMP_LIMIT
+    elements is reduced to a fixed sample: DUMP_LIMIT flat positions drawn from `seed`, the same
+    from run to run, in ascending order."""
+    import numpy as np
+    if isinstance(arr, np.ndarray):
+        arr = torch.from_numpy(np.array(arr))  # (a copy: contiguous, writable, ours)
+    assert arr.is_contiguous()
+    if arr.numel() > DUMP_LIMIT:
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randint(arr.numel(), (DUMP_LIMIT,), generator=g).sort().values
+        arr = arr.reshape(-1)[idx.to(arr.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + (f"_rank{rank}" if rank else "") + ".npy"),
+            arr.to(torch.float32).cpu().numpy())
+
+
+def dump_chunks(out_dir, name, buf, first, count, rank=0, seed=0xD1D1):
+    """--dump-outputs: chunks [first, first + count) of every part of `buf` ([n][t][L], the
+    chunks a step wrote) as float32 in out_dir/<name>.npy: whole ([n][count][L]) up to DUMP_LIMIT
+    bytes, else DUMP_LIMIT seeded (part, chunk, offset) positions of them, in drawing order."""
+    n, t, L = buf.shape
+    if n * count * L <= DUMP_LIMIT:
+        return dump_array(out_dir, name, buf[:, first:first + count].contiguous(), rank)
+    g = torch.Generator().manual_seed(seed)
+    part = torch.randint(n, (DUMP_LIMIT,), generator=g)
+    chunk = torch.randint(count, (DUMP_LIMIT,), generator=g) + first
+    off = torch.randint(L, (DUMP_LIMIT,), generator=g)
+    flat = (part * t + chunk) * L + off
+    dump_array(out_dir, name, buf.reshape(-1)[flat.to(buf.device)], rank)
+
+
 def timed_read_repair(codec, ring, ring_dig, L, P, depth, first, n_parts, world, corrupt,
-                      copier, seed, n_samples=3, rp=None):
+                      copier, seed, n_samples=3, rp=None, dump=None):
     """FileReadBuilder over parts [first, first + n_parts) with read_with_context's retries
     (chunky_ec.readstream over cec_read_pipeline, REBUILT_ONLY): each part loads d random
     chunks of its d+p, copied by `copier`'s threads from the pageable ring of stored chunks
@@ -459,6 +506,8 @@ def timed_read_repair(codec, ring, ring_dig, L, P, depth, first, n_parts, world,
     (file_part.rs:92-107), its verified chunks kept on the device (CEC_READ_CARRY: only the new
     chunk is fetched and uploaded; CEC_BENCH_CARRY=0 sends them again flagged
     CEC_PRESENT_VERIFIED).  One untimed warmup pass of `depth` batches, then the timed stream.
+    `dump` ([m][d][DUMP_WINDOW] bytes, --dump-outputs) receives the head of every data chunk of
+    the stream's last m parts as they were delivered.
     Returns (local seconds, stats dict, sampled output checks)."""
     import numpy as np
     d = codec.data_shard_count()
@@ -494,6 +543,12 @@ def timed_read_repair(codec, ring, ring_dig, L, P, depth, first, n_parts, world,
             retried_checked[0] += attempts > 1
             checks.append({"part": int(part), "attempts": int(attempts),
                            "ok": rp.part_bytes(slot, nb, k) == ring[part % R, :d].tobytes()})
+        # --dump-outputs: the head of every data chunk of the stream's last len(dump) parts
+        if dump is not None and part >= first + n_parts - len(dump):
+            import ctypes
+            for j, a in enumerate(rp.data_chunks(slot, nb)[k]):
+                dump[part - (first + n_parts - len(dump)), j] = np.frombuffer(
+                    ctypes.string_at(int(a), DUMP_WINDOW), np.uint8)
 
     warm = ReadRepairStream(rp, fetch, lambda ids: ring_dig[ids % R], seed=seed + 1)
     warm.run(first, min(n_parts, depth * P))
@@ -558,6 +613,10 @@ def run_stream(args, cfg, codec, world, rank, device, reduce_dev):
     collect = np.empty((hi - lo, d + p, 32), np.uint8) if args.check and world == 1 else None
     loc, slot, n = timed_write(pl, ring_reader(ring, copier), lo, hi - lo, world, collect)
     ok = write_check(pl, ring, slot, n, hi - 1) if hi > lo else True
+    if args.dump_outputs and hi > lo:  # the last batch's results, as a caller takes them
+        parity, dg = pl.wait(slot)
+        dump_array(args.dump_outputs, "parity", parity, rank)
+        dump_array(args.dump_outputs, "digests", dg, rank)
     ok = all_ranks_ok(ok, world, reduce_dev)
     el = max_over_ranks(loc, world, reduce_dev)
     del pl
@@ -600,8 +659,14 @@ def run_read_stream(args, cfg, codec, world, rank, device, reduce_dev):
     threads = rank_threads(world)
     copier = HostCopier(threads)
     ring, ring_dig = encoded_ring(codec, d, p, L, 2 * P, rank_seed(0xC5C5, rank), device, P)
+    dump = None
+    if args.dump_outputs:
+        import numpy as np
+        dump = np.zeros((min(P, hi - lo), d, DUMP_WINDOW), np.uint8)
     loc, stats, checks = timed_read_repair(codec, ring, ring_dig, L, P, depth, lo, hi - lo,
-                                           world, args.corrupt, copier, 0x5EED + rank)
+                                           world, args.corrupt, copier, 0x5EED + rank, dump=dump)
+    if dump is not None:
+        dump_array(args.dump_outputs, "data_heads", dump, rank)
     ok = all(c["ok"] for c in checks) and stats["undecodable_parts"] == 0
     ok = all_ranks_ok(ok, world, reduce_dev)
     el = max_over_ranks(loc, world, reduce_dev)
@@ -1137,6 +1202,10 @@ def run_stream_multi(args, cfg, codec, total_parts):
     for job in jobs:
         m.wait(job)
     el = time.perf_counter() - t0
+    if args.dump_outputs and n_jobs:  # the last job's results in its page-locked outputs
+        par, dig = outs[(n_jobs - 1) % J]
+        dump_array(args.dump_outputs, "parity", par.view(S, p, L)[:n])
+        dump_array(args.dump_outputs, "digests", dig.view(S, t, 32)[:n])
     total = total_parts * d * L
     per_shard = [m.shard_info(g) for g in range(len(devices))]
     print(json.dumps(_stream_line(
@@ -1261,6 +1330,14 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: c2's north_star, "
+                         "baseline_configs and end_to_end blocks, its check against the oracle and "
+                         "the CPU baseline; c3e2's reconstruct beside reconstruct_data")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (the chunks "
+                         "and digests it wrote; a fixed seeded sample of a large array) as float32 "
+                         "DIR/<name>.npy")
     ap.add_argument("--parts", type=int, default=None, help="override parts per GPU")
     ap.add_argument("--shape", default=None, help="d,p override for the encode-only configs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -1289,6 +1366,8 @@ def main():
     args.devices = [int(x) for x in args.devices.split(",")] if args.devices else None
     if args.devices and args.config != "c5":
         ap.error("--devices applies to c5 (the scheduler's write stream)")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     cfg = dict(CONFIGS[args.config])
     if args.parts:
@@ -1394,7 +1473,7 @@ def main():
     # One step = the hot path over the batch.  Each library call is one kernel launch on
     # `stream`; events bracket each launch so per-kernel averages come from the timed steps.
     fused = cfg["op"] == "encode_hash" and not args.separate
-    read_status = []
+    read_status, read_last = [], []
 
     def step(evs=None):
         if cfg["op"] == "encode_hash" and fused:
@@ -1427,10 +1506,11 @@ def main():
         elif cfg["op"] == "read":
             if evs is not None:
                 evs[0].record(stream)
-            _, st = ce.read_batch(codec, batch, present, digests.data_ptr(), stream)
+            ver, st = ce.read_batch(codec, batch, present, digests.data_ptr(), stream)
             if evs is not None:
                 evs[1].record(stream)
             read_status.append(sum(1 for x in st if x != ce.OK))
+            read_last[:] = [ver, st]
         else:
             if evs is not None:
                 evs[0].record(stream)
@@ -1456,6 +1536,22 @@ def main():
     t1 = time.perf_counter()
     local_s = (t1 - t0) / args.steps
     step_s = max_over_ranks(local_s, world, reduce_dev)
+
+    # --dump-outputs: what the last timed step left for its caller, before anything below
+    # touches the buffer again
+    if args.dump_outputs:
+        import numpy as np
+        out_dir = args.dump_outputs
+        if cfg["op"] in ("encode_hash", "encode"):
+            dump_chunks(out_dir, "parity", buf, d, p, rank)
+        elif cfg["op"] == "read":  # the data chunks, loaded or rebuilt, and the call's results
+            dump_chunks(out_dir, "data", buf, 0, d, rank)
+            dump_array(out_dir, "verified", np.frombuffer(read_last[0], np.uint8), rank)
+            dump_array(out_dir, "status", np.array(read_last[1], np.int32), rank)
+        else:  # reconstruct / reconstruct_data: rebuilt in place among the present chunks
+            dump_chunks(out_dir, "chunks", buf, 0, t, rank)
+        if cfg["op"] == "encode_hash":
+            dump_array(out_dir, "digests", digests, rank)
 
     # per-kernel averages over the timed steps
     def avg_ms(i, j):
@@ -1486,23 +1582,25 @@ def main():
         kernels["rs_apply_kernel(reconstruct_data)"] = {
             "ms": round(ms, 4), "algorithmic_bytes": algo_data,
             "GBs": round(algo_data / ms / 1e6, 1)}
-        # reconstruct (data + parity) of the same erasure sets, timed the same way
-        evf = [[torch.cuda.Event(enable_timing=True) for _ in range(2)] for _ in range(args.steps)]
-        ce.reconstruct_batch(codec, batch, present, False, stream)
-        for k in range(args.steps):
-            evf[k][0].record(stream)
+        if args.full:
+            # reconstruct (data + parity) of the same erasure sets, timed the same way
+            evf = [[torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                   for _ in range(args.steps)]
             ce.reconstruct_batch(codec, batch, present, False, stream)
-            evf[k][1].record(stream)
-        torch.cuda.synchronize(device)
-        ms_f = sum(e[0].elapsed_time(e[1]) for e in evf) / args.steps
-        full_gbs = algo_full / (ms_f / 1e3) / 1e9
-        kernels["also_reconstruct"] = {
-            "call": "reconstruct (data + parity, file_part.rs:304), same parts and erasures",
-            "ms": round(ms_f, 4), "algorithmic_bytes": algo_full,
-            "GBs": round(full_gbs, 1),
-            "roofline": {"bound": "hbm", "kernel": "rs_apply_var_kernel",
-                         "achieved": round(full_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(full_gbs / HBM_PEAK_GBS, 4)}}
+            for k in range(args.steps):
+                evf[k][0].record(stream)
+                ce.reconstruct_batch(codec, batch, present, False, stream)
+                evf[k][1].record(stream)
+            torch.cuda.synchronize(device)
+            ms_f = sum(e[0].elapsed_time(e[1]) for e in evf) / args.steps
+            full_gbs = algo_full / (ms_f / 1e3) / 1e9
+            kernels["also_reconstruct"] = {
+                "call": "reconstruct (data + parity, file_part.rs:304), same parts and erasures",
+                "ms": round(ms_f, 4), "algorithmic_bytes": algo_full,
+                "GBs": round(full_gbs, 1),
+                "roofline": {"bound": "hbm", "kernel": "rs_apply_var_kernel",
+                             "achieved": round(full_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(full_gbs / HBM_PEAK_GBS, 4)}}
     elif cfg["op"] == "read":
         # one read_batch call: verify (sha256_lane_kernel, d chunks per part) on the caller's
         # stream, the speculative decode (rs_apply_var_kernel) beside it on a side stream
@@ -1589,7 +1687,7 @@ def main():
     # against the oracle after every timed region: at N = 1 in the cpu_baseline leg (with every
     # part of the C2 / C4 buffers), at N > 1 on every rank, its own buffers, ANDed over the ranks
     snap = None
-    if args.config == "c2" and fused and (world > 1 or not args.no_cpu_baseline):
+    if args.full and args.config == "c2" and fused and (world > 1 or not args.no_cpu_baseline):
         snap = {"parts": (0, n_parts // 2, n_parts - 1)}
         snap["headline"] = snapshot_parts(buf, digests, snap["parts"])
         if world == 1 and not args.no_full_check:
@@ -1597,11 +1695,11 @@ def main():
             snap["c2_dev"] = buf  # checked whole in the cpu_baseline leg (batch_vs_oracle)
     # north_star's two >= 60 % targets on the same buffer (C2 only)
     nstar = None
-    if args.config == "c2" and not args.separate and not args.no_north_star:
+    if args.full and args.config == "c2" and not args.separate and not args.no_north_star:
         nstar = north_star_block(codec, batch, buf, digests, stream, device, rank, d, p, L,
                                  args.steps, snap)
     others = None
-    if args.config == "c2" and not args.separate and not args.no_north_star:
+    if args.full and args.config == "c2" and not args.separate and not args.no_north_star:
         others = baseline_configs_block(codec, batch, buf, digests, stream, device, rank, d, p,
                                         L, args.steps, snap)
     # the end-to-end forms below use their own buffers (with the whole-batch check on, `snap`
@@ -1611,7 +1709,7 @@ def main():
 
     # every rank streams its own share (barriers inside): the PCIe-inclusive figure
     e2e = stream = None
-    if args.config == "c2" and args.e2e_gib > 0 and not args.separate:
+    if args.full and args.config == "c2" and args.e2e_gib > 0 and not args.separate:
         e2e = end_to_end(codec, d, p, L, args.e2e_gib, world, rank, reduce_dev, e2e_threads,
                          ordinal, device, args.corrupt,
                          full_check=snap is not None and "c2_dev" in snap)
@@ -1716,7 +1814,8 @@ def main():
                          "part) vs oracle.encode_sep and hashlib SHA-256, after every timed region; "
                          "ANDed over the ranks (every part of the buffers: N = 1 only)"}
         line["host"] = host_report
-        if world == 1 and not args.no_cpu_baseline and cfg["op"] in ("encode_hash", "encode"):
+        if (args.full and world == 1 and not args.no_cpu_baseline
+                and cfg["op"] in ("encode_hash", "encode")):
             # the cpu_baseline leg (after every timed region), the one place the bench runs the
             # oracle: first this run's own buffers against it, then the timed CPU baseline; both
             # on the process's full CPU set (the main thread was bound to GPU0's NUMA node above)

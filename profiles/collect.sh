@@ -6,7 +6,7 @@
 # of other domains).  Each run is time-limited; the chain stops at the first failure.
 set -euo pipefail
 TAG=${1:-r1}; shift || true
-ARGS=${@:-"--steps 3 --warmup 1 --no-cpu-baseline"}
+ARGS=${@:-"--full --steps 3 --warmup 1 --no-cpu-baseline"}
 OUT=gpurun_out/prof_${TAG}
 mkdir -p "$OUT"
 echo "python3 bench.py $ARGS" > "$OUT/command.txt"

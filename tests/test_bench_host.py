@@ -356,3 +356,28 @@ def test_rccl_ranks_never_share_a_gpu():
     assert bench.rccl_overcommit(1, "nccl", 0) is None
     assert "2 RCCL ranks but 1 visible GPU" in bench.rccl_overcommit(2, "nccl", 1)
     assert bench.rccl_overcommit(4, "gloo", 1) is None
+
+
+def test_dump_outputs_whole_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs' writers: a small array is written whole as float32 (rank r > 0 under its
+    own name), a large one as a sample of DUMP_LIMIT positions that is the same on every call and
+    holds the array's own values at those positions; dump_chunks takes only the chunks asked for."""
+    import torch
+    n, t, L, d = 5, 7, 64, 4
+    buf = torch.from_numpy(np.random.default_rng(2).integers(0, 256, (n, t, L), dtype=np.uint8))
+    bench.dump_chunks(str(tmp_path), "parity", buf, d, t - d)
+    got = np.load(tmp_path / "parity.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, buf[:, d:].numpy())
+    bench.dump_array(str(tmp_path), "digests", buf.numpy(), rank=3)
+    assert np.array_equal(np.load(tmp_path / "digests_rank3.npy"), buf.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 100)
+    bench.dump_chunks(str(tmp_path / "a"), "parity", buf, d, t - d)
+    bench.dump_chunks(str(tmp_path / "b"), "parity", buf, d, t - d)
+    a, b = np.load(tmp_path / "a" / "parity.npy"), np.load(tmp_path / "b" / "parity.npy")
+    assert a.shape == (100,) and np.array_equal(a, b)
+    g = torch.Generator().manual_seed(0xD1D1)
+    part, chunk, off = (torch.randint(k, (100,), generator=g) for k in (n, t - d, L))
+    assert np.array_equal(a, buf.numpy()[part.numpy(), chunk.numpy() + d, off.numpy()])
+    bench.dump_array(str(tmp_path / "a"), "flat", buf)
+    flat = np.load(tmp_path / "a" / "flat.npy")
+    assert flat.shape == (100,) and set(flat.tolist()) <= set(buf.numpy().ravel().tolist())

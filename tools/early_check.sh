@@ -7,5 +7,5 @@ timeout -k 10 400 python -u -m pytest tests -m gpu -x -q --timeout 150 --timeout
 tail -1 $T/pytest_gpu.log
 timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $T/smoke.log 2>&1 || { cat $T/smoke.log; exit 1; }
 grep -v amdgpu.ids $T/smoke.log
-timeout -k 10 300 python -u bench.py > $T/bench.log 2>&1 || { tail -30 $T/bench.log; exit 1; }
+timeout -k 10 300 python -u bench.py --full > $T/bench.log 2>&1 || { tail -30 $T/bench.log; exit 1; }
 tail -c 1500 $T/bench.log

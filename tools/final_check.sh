@@ -9,5 +9,5 @@ tail -2 "$OUT/pytest_gpu.log"
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 \
     || { echo "smoke failed"; tail -20 "$OUT/smoke.log"; exit 1; }
 tail -1 "$OUT/smoke.log"
-timeout -k 10 300 python -u bench.py > "$OUT/bench_c2.log" 2>&1 || { echo "bench failed"; exit 1; }
+timeout -k 10 300 python -u bench.py --full > "$OUT/bench_c2.log" 2>&1 || { echo "bench failed"; exit 1; }
 echo "bench ok"

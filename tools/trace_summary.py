@@ -29,8 +29,8 @@ def main(trace_dir, bench_log, stats=None):
              bc["c4_encode_hash"]["ms"]),
             ("C3 1-4 erasures", "rs_apply_var_kernel<true, 4, 2, true, 4, 10, 5>", bc["c3_reconstruct"]["ms"])]
     print("# Round 6: kernel trace of the default command on the final tree\n")
-    print("`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 10 "
-          "--warmup 3 --no-cpu-baseline` (`tools/r6_check.sh`; raw stats: "
+    print("`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full "
+          "--steps 10 --warmup 3 --no-cpu-baseline` (`tools/r6_check.sh`; raw stats: "
           f"`{stats}`; this file: `tools/trace_summary.py`).  Trace only: "
           "no hot-path kernel changed in rounds 5-6, so the PMC passes (HBM traffic, SQ counters) "
           "of `profiles/r4e_c2_summary.md` still describe them; this run checks that the round-6 "
