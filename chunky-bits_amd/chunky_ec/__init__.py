@@ -36,9 +36,8 @@ except Exception:  # pragma: no cover - torch is optional for the host-buffer AP
     torch = None
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# CEC_LIBRARY points the A/B timing tools (tools/*_ab.py) at the attribution build
-# (tools/ab/libchunky_ec.so, `make -C chunky-bits_amd/csrc ab`); everything else loads the product
-# library next to this file.
+# CEC_LIBRARY loads another build of the library (the host-sanitizer build, `make -C
+# chunky-bits_amd/csrc asan`); everything else loads the library next to this file.
 LIB_PATH = os.environ.get("CEC_LIBRARY") or os.path.join(_HERE, "libchunky_ec.so")
 
 if not os.path.exists(LIB_PATH):

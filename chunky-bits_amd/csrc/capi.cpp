@@ -622,23 +622,11 @@ struct PinnedBuf {
 struct Arena {
     StageCtx dev;  // stream + device staging
     PinnedBuf in, out;
-    // CEC_COALESCE_EARLY_D2H: the parity comes back on a side stream as soon as the encode is
-    // done, beside the SHA-256 chains (made on first use; arenas live as long as the process)
+    // the parity comes back on a side stream as soon as the encode is done, beside the SHA-256
+    // chains (profiles/r2_early_d2h/; made on first use; arenas live as long as the process)
     hipStream_t side = nullptr;
     hipEvent_t encoded = nullptr;
 };
-
-// How the early parity download waits for the encode: on the host (the leader blocks on the
-// event, then queues the copy: the default, round 2's form, adopted after a 256-caller hang on
-// an earlier device-side form) or on the device (the side stream waits on the encode's event:
-// CEC_COALESCE_D2H_WAIT=device, kept for the A/B).  Both are deadlock-free (see the wait
-// itself), and DESIGN.md §4.7's A/B put them within run-to-run spread, so the default is the
-// form with the longer record.
-bool coalesce_d2h_host_wait() { return knobs().coalesce_d2h_host_wait; }
-
-bool coalesce_early_d2h() {  // default on (profiles/r2_early_d2h/); =0 for A/B
-    return knobs().coalesce_early_d2h;
-}
 
 struct CoalesceKey {
     const void* codec;
@@ -681,9 +669,6 @@ struct Batch {
 // each pay it (round 1, unconditional: 100 threads 7.1-8.2 GB/s with 1 vs 3.6-3.8 with 4,
 // profiles/r1y_percall_ab.log).  Overflowing callers (256 pageable parts vs a 1 GiB cap) then
 // copy in while the first batch runs: 13.9 -> ~26 GB/s (profiles/r2_percall/).
-// CEC_COALESCE_ADAPT=0 (A/B knob): fixed CEC_COALESCE_US window, no early exit.
-bool coalesce_adaptive() { return knobs().coalesce_adaptive; }
-
 uint32_t coalesce_inflight() { return knobs().coalesce_inflight; }
 
 template <typename Req, typename Impl>
@@ -760,13 +745,11 @@ class Coalescer {
             // results out and come back a few ms later; a short window splits the callers into
             // two alternating groups, each paying a full launch (10 threads: 5 parts per launch).
             // It ends early once as many callers are queued as were ever inside at once lately.
-            uint64_t window = coalesce_window_us();
-            if (coalesce_adaptive()) window = std::max<uint64_t>(window, last_run_us_ / 8);
+            const uint64_t window = std::max<uint64_t>(coalesce_window_us(), last_run_us_ / 8);
             const auto until =
                 std::chrono::steady_clock::now() + std::chrono::microseconds(window);
             gather_cv_.wait_until(lk, until, [&] {
-                return matching_bytes() >= coalesce_max_bytes() ||
-                       (coalesce_adaptive() && matching_count() >= peak_);
+                return matching_bytes() >= coalesce_max_bytes() || matching_count() >= peak_;
             });
         }
         Batch batch_state;
@@ -973,16 +956,10 @@ struct PartReq : ReqBase {
     // Page-locked caller buffers (cec_host_alloc): DMA'd directly, no copy-in / copy-out.
     bool in_pinned = false, out_pinned = false;
     size_t out_off = 0;                 // parity offset in the pinned output staging
-    // Early upload (CEC_COALESCE_EARLY_H2D): the caller queues its own part's H2D right after its
-    // copy-in, so the uploads overlap the other callers' copies instead of following them all.
-    bool early = false;
     uint8_t* dev_dst = nullptr;         // this part's place in the device batch
     hipStream_t stream = nullptr;       // the batch's stream
-    hipError_t early_err = hipSuccess;
     CoalesceKey key() const { return {codec, L, device}; }
 };
-
-bool coalesce_early_h2d() { return knobs().coalesce_early_h2d; }
 
 // Pinned layout: input [part][d][cs] (staged parts only, at in_off), output [part][p][cs]
 // (staged parts only, at out_off) then digests [part][d+p][32]; device batch [part][d+p][cs]
@@ -1028,13 +1005,10 @@ struct PartImpl {
         CEC_TRY(a.out.reserve(out_bytes + B * t * 32,
                               coalesce_max_bytes() / d * p + coalesce_max_bytes() / cs * t * 32));
         CEC_TRY(ctx_reserve(a.dev, round_up(B * t * 32, kChunkAlign) + B * t * cs));
-        const bool early = coalesce_early_h2d();
         uint8_t* dbase = a.dev.dbuf + round_up(B * t * 32, kChunkAlign);
         for (PartReq* r : batch) {
-            r->early = early;
             r->dev_dst = dbase + r->slot * t * cs;
             r->stream = a.dev.stream;
-            r->early_err = hipSuccess;
         }
         return CEC_OK;
     }
@@ -1056,10 +1030,6 @@ struct PartImpl {
             uint8_t* dst = r.arena->in.ptr + r.in_off;
             for (size_t j = 0; j < d; ++j) std::memcpy(dst + j * cs, r.data_buf + j * r.L, r.L);
         }
-        if (r.early) {
-            r.early_err = upload(r);
-            if (r.early_err != hipSuccess) (void)hipGetLastError();
-        }
     }
     static int run(std::vector<PartReq*>& batch, Arena& a) {
         cec_codec* c = batch[0]->codec;
@@ -1071,9 +1041,7 @@ struct PartImpl {
         uint8_t* ddig = a.dev.dbuf;
         uint8_t* dbase = a.dev.dbuf + round_up(B * t * 32, kChunkAlign);
         hipStream_t s = a.dev.stream;
-        if (batch[0]->early) {  // every caller queued its own upload after its copy-in
-            for (const PartReq* r : batch) HIP_TRY(r->early_err);
-        } else if (!per_part) {
+        if (!per_part) {
             HIP_TRY(hipMemcpy2DAsync(dbase, t * cs, a.in.ptr, d * cs, d * cs, B,
                                      hipMemcpyHostToDevice, s));
         } else {
@@ -1132,12 +1100,9 @@ struct PartImpl {
             ap.n_rows = uint32_t(p);
             ap.std_encode = c->bs ? 1u : 0u;
             HIP_TRY(launch_rs_encode(ap, true, s));
-            const bool early = coalesce_early_d2h();
-            if (early) {
-                if (!a.side) HIP_TRY(hipStreamCreateWithFlags(&a.side, hipStreamNonBlocking));
-                if (!a.encoded) HIP_TRY(hipEventCreateWithFlags(&a.encoded, hipEventDisableTiming));
-                HIP_TRY(hipEventRecord(a.encoded, s));
-            }
+            if (!a.side) HIP_TRY(hipStreamCreateWithFlags(&a.side, hipStreamNonBlocking));
+            if (!a.encoded) HIP_TRY(hipEventCreateWithFlags(&a.encoded, hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(a.encoded, s));
             ShaParams h{};
             h.base = dbase;
             h.part_stride = t * cs;
@@ -1148,23 +1113,15 @@ struct PartImpl {
             h.n_chunks = uint32_t(t);
             h.digests = ddig;
             HIP_TRY(launch_sha256(h, true, s));
-            if (early) {
-                // Parity down beside the SHA-256 chains (both only read the batch): the side
-                // stream waits on the device for the encode's event.  A wait on an event that
-                // was recorded before the wait is queued cannot deadlock, even when two streams
-                // share one in-order hardware queue (more streams than GPU_MAX_HW_QUEUES): the
-                // event's marker precedes the waiting packet in any queue order.  (Round 2 had
-                // the host block on the event here, blaming a 256-caller hang on such waits;
-                // that hang was the stranded-caller race fixed below, and the host hand-over
-                // build hung the same way before that fix.)
-                if (coalesce_d2h_host_wait())
-                    HIP_TRY(hipEventSynchronize(a.encoded));
-                else
-                    HIP_TRY(hipStreamWaitEvent(a.side, a.encoded, 0));
-                side_wait.q = a.side;
-                CEC_TRY(parity_down(a.side));
-                parity_sent = true;
-            }
+            // Parity down beside the SHA-256 chains (both only read the batch).  The leader
+            // blocks on the encode's event, then queues the copy on the side stream.  A
+            // device-side wait (the side stream waiting on the event) is deadlock-free too, since
+            // the event is recorded before the wait is queued, and DESIGN.md §4.7's A/B put the
+            // two within run-to-run spread; the host wait is the form with the longer record.
+            HIP_TRY(hipEventSynchronize(a.encoded));
+            side_wait.q = a.side;
+            CEC_TRY(parity_down(a.side));
+            parity_sent = true;
         }
         const size_t dig0 = batch[0]->item0;
         if (!parity_sent) CEC_TRY(parity_down(s));
@@ -1230,12 +1187,7 @@ extern "C" {
 int cec_abi_version(void) { return CEC_ABI_VERSION; }
 
 const char* cec_build_info(void) {
-#ifdef CEC_AB_TOOLS
-    return "chunky_ec gfx950 ab_tools=1 (A/B attribution build: CEC_FUSED_MODE 1/2 and "
-           "CEC_SHA_VARIANT 7/8 produce wrong outputs by design; not for production)";
-#else
     return "chunky_ec gfx950 ab_tools=0";
-#endif
 }
 
 const char* cec_status_name(int s) {
@@ -1685,16 +1637,13 @@ class SideLease {
     std::unique_ptr<SideCtx> c_;
 };
 
-// LDS each speculative-decode block reserves (A/B knob CEC_SPEC_LDS_KIB).  100 KiB keeps decode
-// blocks off the CUs holding SHA workgroups (>= 64 KiB each) and runs one per free CU: a
-// low-intensity decode spread under the SHA chains.  Measured on the c3r read (4 096 parts,
-// RS(10,4), d loaded, tools/c3r_ab.sh): 43.2 ms vs 45.3 (65 KiB: two per free CU) vs 46.5 (none:
-// decode everywhere, done in 17 ms, but the SHA chains slow from 42.6 to 46.4 ms beside it) vs
-// 53.0 ms without speculation.
-uint32_t decode_lds() { return knobs().spec_lds; }
-
-// CEC_READ_SPECULATE=0 (A/B knob): verify, wait, then decode from the verified chunks only.
-bool read_speculate() { return knobs().read_speculate; }
+// LDS each speculative-decode block reserves.  100 KiB keeps decode blocks off the CUs holding
+// SHA workgroups (>= 64 KiB each) and runs one per free CU: a low-intensity decode spread under
+// the SHA chains.  Measured on the c3r read (4 096 parts, RS(10,4), d loaded,
+// profiles/r1y_c3r_summary.md): 43.2 ms vs 45.3 (65 KiB: two per free CU) vs 46.5 (none: decode
+// everywhere, done in 17 ms, but the SHA chains slow from 42.6 to 46.4 ms beside it) vs 53.0 ms
+// without speculation.
+constexpr uint32_t kDecodeLds = 100u * 1024u;
 
 // A loaded chunk is hashed unless the caller marked it CEC_PRESENT_VERIFIED (a read retry's
 // chunks that an earlier pass already verified).
@@ -1708,18 +1657,6 @@ inline bool needs_hash(uint8_t f) { return f != 0 && f != CEC_PRESENT_VERIFIED; 
 int verify_loaded(const cec_part_batch* b, size_t t, const uint8_t* present_host,
                   const uint8_t* expected, uint8_t* ok, hipStream_t s) {
     const size_t n = b->n_parts * t;
-    if (!knobs().verify_compact) {  // A/B: strided launch with the skipped lanes
-        std::vector<uint32_t> mask(n);  // chunks to hash: loaded, not already verified
-        for (size_t i = 0; i < n; ++i) mask[i] = needs_hash(present_host[i]) ? 1u : 0u;
-        std::vector<uint8_t> bytes(n);
-        for (size_t i = 0; i < n; ++i) bytes[i] = uint8_t(mask[i]);
-        Scratch sc;
-        CEC_TRY(sc.acquire(n, s));
-        std::memcpy(sc.host(), bytes.data(), n);
-        HIP_TRY(hipMemcpyAsync(sc.dev(), sc.host(), n, hipMemcpyHostToDevice, s));
-        CEC_TRY(cec_verify_batch(b, 0, t, sc.dev(), expected, ok, s));
-        return CEC_OK;
-    }
     std::vector<uint32_t> items;
     items.reserve(n);
     for (size_t i = 0; i < n; ++i)
@@ -1766,7 +1703,6 @@ int verify_then_reconstruct(const cec_codec* c, const cec_part_batch* b,
     if (b->chunk_len == 0) return CEC_EMPTY_SHARD;
     const size_t d = c->d, t = c->d + c->p, n = b->n_parts * t;
     if (n > 0xFFFFFFFFull) return CEC_ERR_INVALID_ARGUMENT;
-    const bool speculate = read_speculate();
     Scratch ok_buf;  // device verification flags, released on s behind the readback
     CEC_TRY(ok_buf.acquire(n, s));
     uint8_t* ok = ok_buf.dev();
@@ -1776,16 +1712,13 @@ int verify_then_reconstruct(const cec_codec* c, const cec_part_batch* b,
     // queued: safe in shared in-order hardware queues (the rule of the coalescer's early parity
     // download above).
     SideLease lease;
-    SideCtx* side = nullptr;
-    if (speculate) {
-        CEC_TRY(lease.acquire());
-        side = lease.get();
-        HIP_TRY(hipEventRecord(side->fork, s));
-    }
+    CEC_TRY(lease.acquire());
+    SideCtx* side = lease.get();
+    HIP_TRY(hipEventRecord(side->fork, s));
     // Verification goes first so its long-lived workgroups claim their CUs (one or two per CU)
     // before the decode's blocks take the CUs left free.
     int st = verify_loaded(b, t, present_host, expected, ok, s);
-    if (st == CEC_OK && speculate) {
+    if (st == CEC_OK) {
         // Parts with fewer than d loaded chunks cannot be decoded: left out (mask all ones).
         std::vector<uint8_t> spec(present_host, present_host + n);
         for (size_t k = 0; k < b->n_parts; ++k) {
@@ -1798,7 +1731,7 @@ int verify_then_reconstruct(const cec_codec* c, const cec_part_batch* b,
         if (e != hipSuccess) st = hip_fail(e, "speculative decode fork");
         if (st == CEC_OK)
             st = reconstruct_batch(c, b, spec.data(), data_only ? 1 : 0, side->stream,
-                                   decode_lds());
+                                   kDecodeLds);
         if (st == CEC_OK) {
             e = hipEventRecord(side->join, side->stream);
             if (e == hipSuccess) e = hipStreamWaitEvent(s, side->join, 0);
@@ -1817,8 +1750,8 @@ int verify_then_reconstruct(const cec_codec* c, const cec_part_batch* b,
     for (size_t i = 0; i < n; ++i)  // verified by an earlier pass: trusted, not hashed again
         if (present_host[i] == CEC_PRESENT_VERIFIED) verified_host[i] = 1;
     // Parts with fewer than d verified chunks cannot be decoded (the reference's read returns
-    // the part short / resilver reports it).  Decode (again) the parts whose loaded chunks did
-    // not all verify — or every part, without speculation.
+    // the part short / resilver reports it).  Decode again the parts whose loaded chunks did
+    // not all verify.
     std::vector<uint8_t> pres(n, uint8_t(1));
     bool any = false;
     for (size_t k = 0; k < b->n_parts; ++k) {
@@ -1829,7 +1762,7 @@ int verify_then_reconstruct(const cec_codec* c, const cec_part_batch* b,
             bad |= present_host[k * t + i] && !verified_host[k * t + i];
         }
         part_status[k] = good >= d ? CEC_OK : CEC_TOO_FEW_SHARDS_PRESENT;
-        if (good >= d && (bad || !speculate)) {
+        if (good >= d && bad) {
             std::copy(verified_host + k * t, verified_host + (k + 1) * t, pres.begin() + k * t);
             any = true;
         }

@@ -109,7 +109,10 @@ __device__ __forceinline__ void store_words(uint8_t* dst, uint64_t n, const uint
 // BE builds keep every chunk in the LDS ring as big-endian 32-bit words (SHA-256's message word
 // order): the encoder waves byte-swap while storing, so the SHA waves read message words
 // directly (16 fewer half-rate v_perm per 64-byte block).  GF(2^8) arithmetic is byte-wise, so
-// the encoders compute parity on their native words.  See fused_be() for where it pays.
+// the encoders compute parity on their native words.  It pays where the encoders run on a SIMD
+// with spare issue slots (the ENC3 build: C4 21.06 -> 20.47 ms) and costs where they share a
+// saturated SIMD with a SHA wave (RS(10,4) build: C2 42.63 -> 42.97 ms), so it is on for ENC3
+// only.
 template <int NW, bool BE = true>
 __device__ __forceinline__ void lds_store_words(uint8_t* dst, const uint32_t w[NW]) {
     if (!BE) {
@@ -156,9 +159,6 @@ __device__ __forceinline__ void ring_tail_words(const uint8_t* tp, uint32_t rem,
 // PMAX: parity rows (exact when a.p == PMAX; rows r >= a.p skipped by uniform guards).
 // Up to kMaxFusedData data inputs are held in registers per encoder thread (next step's
 // prefetch).  Aligned (16-byte) layouts only; others use the separate kernels.
-// MODE (timing attribution only, CEC_FUSED_MODE): 0 = the product; 1 = encoders skip the GF
-// multiply (parity = data chunk 0); 2 = encoders only join the barriers (SHA hashes whatever the
-// ring holds).  Modes 1 and 2 produce wrong parity/digests by design.
 // DT: data chunk count fixed at compile time (0 = a.d at run time, <= kMaxFusedData).
 // SW: SHA waves per workgroup, 4 (one per SIMD) or 8 (two per SIMD: batches with more chunks
 // than one wave per SIMD can hold, where two co-resident SHA waves turn the lone wave's
@@ -168,10 +168,12 @@ __device__ __forceinline__ void ring_tail_words(const uint8_t* tp, uint32_t rem,
 // carries ONE SHA wave where SIMDs 0-2 carry two: its spare issue slots absorb all the encoder
 // work, as waves 7 (an otherwise empty SHA slot) and 11 (tasks 0-63 and 64-127; needs
 // G*STEP/CW <= 128), while encoder waves 8-10 only build the product tables and join the
-// barriers.  The SIMDs with two SHA waves then carry no encoder work at all.
-template <int PMAX, int STEP, int MODE, int DT, int SW = 4, bool ENC3 = false, bool BE = false>
+// barriers.  The SIMDs with two SHA waves then carry no encoder work at all.  The ENC3 build
+// keeps the ring big-endian (lds_store_words).
+template <int PMAX, int STEP, int DT, int SW = 4, bool ENC3 = false>
 __global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams a) {
     static_assert(!ENC3 || SW == 8, "ENC3 needs the two-SHA-wave build");
+    constexpr bool BE = ENC3;
     constexpr uint32_t kSha = 64u * SW;
     constexpr int DMAX = DT ? DT : kMaxFusedData;
     constexpr int kEntry = PMAX <= 4 ? 4 : 8;
@@ -226,7 +228,7 @@ __global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams 
         uint32_t v[DMAX][NW];
         auto load_step = [&](uint32_t s) {
             const uint64_t x = uint64_t(s) * STEP + col * CW;
-            if (!has_task || x >= L || MODE == 2) return;
+            if (!has_task || x >= L) return;
             const uint64_t n = (L - x) < CW ? (L - x) : CW;
             const uint8_t* src = pb + x;  // per-lane pointer walked by chunk_stride: no
                                           // per-input 64-bit base held in SGPRs
@@ -264,7 +266,7 @@ __global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams 
         }
         auto emit_step = [&](uint32_t s, uint32_t slot) {
             const uint64_t x = uint64_t(s) * STEP + col * CW;
-            if (!has_task || x >= L || MODE == 2) return;
+            if (!has_task || x >= L) return;
             const uint64_t n = (L - x) < CW ? (L - x) : CW;
             uint8_t* lrow = ring + (size_t(slot) * rows + size_t(g) * t) * kRow + col * CW;
             uint32_t acc_lo[4 * NW], acc_hi[4 * NW];
@@ -273,53 +275,48 @@ __global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams 
 #pragma unroll
             for (int j = 0; j < DMAX; ++j)
                 if (uint32_t(j) < d) lds_store_words<NW, BE>(lrow + size_t(j) * kRow, v[j]);
-            if (MODE == 1) {
+            // Inputs in pairs: two lookups folded into the accumulator by one full-rate
+            // xor3.  Table j sits at LDS offset j*256*kEntry (an instruction offset); the
+            // entry index is one byte of the data word (byte select + scale: one SDWA op).
 #pragma unroll
-                for (int q = 0; q < NW; ++q) acc_lo[4 * q] = v[0][q];
-            } else {
-                // Inputs in pairs: two lookups folded into the accumulator by one full-rate
-                // xor3.  Table j sits at LDS offset j*256*kEntry (an instruction offset); the
-                // entry index is one byte of the data word (byte select + scale: one SDWA op).
+            for (int j = 0; j < DMAX; j += 2) {
+                if (j + 1 < DMAX && uint32_t(j + 1) < d) {
+                    const int j1 = j + 1 < DMAX ? j + 1 : j;
+                    const uint8_t* t0 = tabs + size_t(j) * 256 * kEntry;
+                    const uint8_t* t1 = tabs + size_t(j1) * 256 * kEntry;
 #pragma unroll
-                for (int j = 0; j < DMAX; j += 2) {
-                    if (j + 1 < DMAX && uint32_t(j + 1) < d) {
-                        const int j1 = j + 1 < DMAX ? j + 1 : j;
-                        const uint8_t* t0 = tabs + size_t(j) * 256 * kEntry;
-                        const uint8_t* t1 = tabs + size_t(j1) * 256 * kEntry;
+                    for (int q = 0; q < NW; ++q) {
 #pragma unroll
-                        for (int q = 0; q < NW; ++q) {
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                const uint32_t i0 = byte_scaled<kEntry>(v[j][q], k);
-                                const uint32_t i1 = byte_scaled<kEntry>(v[j1][q], k);
-                                if (kEntry == 4) {
-                                    acc_lo[4 * q + k] = xor3(
-                                        acc_lo[4 * q + k],
-                                        *reinterpret_cast<const uint32_t*>(t0 + i0),
-                                        *reinterpret_cast<const uint32_t*>(t1 + i1));
-                                } else {
-                                    const uint2 e0 = *reinterpret_cast<const uint2*>(t0 + i0);
-                                    const uint2 e1 = *reinterpret_cast<const uint2*>(t1 + i1);
-                                    acc_lo[4 * q + k] = xor3(acc_lo[4 * q + k], e0.x, e1.x);
-                                    acc_hi[4 * q + k] = xor3(acc_hi[4 * q + k], e0.y, e1.y);
-                                }
+                        for (int k = 0; k < 4; ++k) {
+                            const uint32_t i0 = byte_scaled<kEntry>(v[j][q], k);
+                            const uint32_t i1 = byte_scaled<kEntry>(v[j1][q], k);
+                            if (kEntry == 4) {
+                                acc_lo[4 * q + k] = xor3(
+                                    acc_lo[4 * q + k],
+                                    *reinterpret_cast<const uint32_t*>(t0 + i0),
+                                    *reinterpret_cast<const uint32_t*>(t1 + i1));
+                            } else {
+                                const uint2 e0 = *reinterpret_cast<const uint2*>(t0 + i0);
+                                const uint2 e1 = *reinterpret_cast<const uint2*>(t1 + i1);
+                                acc_lo[4 * q + k] = xor3(acc_lo[4 * q + k], e0.x, e1.x);
+                                acc_hi[4 * q + k] = xor3(acc_hi[4 * q + k], e0.y, e1.y);
                             }
                         }
-                    } else if (uint32_t(j) < d) {
-                        const uint8_t* t0 = tabs + size_t(j) * 256 * kEntry;
+                    }
+                } else if (uint32_t(j) < d) {
+                    const uint8_t* t0 = tabs + size_t(j) * 256 * kEntry;
 #pragma unroll
-                        for (int q = 0; q < NW; ++q) {
+                    for (int q = 0; q < NW; ++q) {
 #pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                const uint32_t i0 = byte_scaled<kEntry>(v[j][q], k);
-                                if (kEntry == 4) {
-                                    acc_lo[4 * q + k] ^=
-                                        *reinterpret_cast<const uint32_t*>(t0 + i0);
-                                } else {
-                                    const uint2 e0 = *reinterpret_cast<const uint2*>(t0 + i0);
-                                    acc_lo[4 * q + k] ^= e0.x;
-                                    acc_hi[4 * q + k] ^= e0.y;
-                                }
+                        for (int k = 0; k < 4; ++k) {
+                            const uint32_t i0 = byte_scaled<kEntry>(v[j][q], k);
+                            if (kEntry == 4) {
+                                acc_lo[4 * q + k] ^=
+                                    *reinterpret_cast<const uint32_t*>(t0 + i0);
+                            } else {
+                                const uint2 e0 = *reinterpret_cast<const uint2*>(t0 + i0);
+                                acc_lo[4 * q + k] ^= e0.x;
+                                acc_hi[4 * q + k] ^= e0.y;
                             }
                         }
                     }
@@ -412,78 +409,40 @@ __global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams 
     }
 }
 
-template <int PMAX, int STEP, int MODE, int DT, int SW = 4, bool ENC3 = false, bool BE = false>
+template <int PMAX, int STEP, int DT, int SW = 4, bool ENC3 = false>
 hipError_t launch_p(const FusedParams& a, hipStream_t s) {
     const size_t lds = size_t(2) * a.parts_per_wg * (a.d + a.p) * (STEP + 16);  // ring
     const size_t tabs = size_t(DT ? DT : kMaxFusedData) * 256 * (PMAX <= 4 ? 4 : 8);
     if (lds + tabs > 160 * 1024) return hipErrorInvalidValue;
     static const bool attr = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&encode_hash_kernel<PMAX, STEP, MODE, DT, SW, ENC3, BE>),
+        reinterpret_cast<const void*>(&encode_hash_kernel<PMAX, STEP, DT, SW, ENC3>),
         hipFuncAttributeMaxDynamicSharedMemorySize,
         int(160 * 1024 - size_t(DT ? DT : kMaxFusedData) * 256 * (PMAX <= 4 ? 4 : 8))) ==
         hipSuccess;
     if (!attr) return hipErrorInvalidValue;
     const uint32_t grid = (a.n_parts + a.parts_per_wg - 1) / a.parts_per_wg;
     clear_stale_error();
-    hipLaunchKernelGGL((encode_hash_kernel<PMAX, STEP, MODE, DT, SW, ENC3, BE>), dim3(grid),
+    hipLaunchKernelGGL((encode_hash_kernel<PMAX, STEP, DT, SW, ENC3>), dim3(grid),
                        dim3(64 * (SW + 4)), lds, s, a);
     return hipGetLastError();
 }
 
-// Wave priorities: 0 = none, 1 = encoder waves at s_setprio 1, 2 = SHA waves at s_setprio 1.
-// The build's default, or CEC_FUSED_PRIO=0/1/2 (dev knob, A/B).
-uint32_t fused_prio(uint32_t dflt) {
-    const int v = knobs().fused_prio;
-    return v >= 0 ? uint32_t(v) : dflt;
-}
-
-// Byte order of the LDS ring (BE = encoders store big-endian words, the SHA waves skip their
-// 16 byte-swaps per block).  It pays where the encoders run on a SIMD with spare issue slots
-// (the ENC3 build: C4 21.06 -> 20.47 ms) and costs where they share a saturated SIMD with a SHA
-// wave (RS(10,4) build: C2 42.63 -> 42.97 ms), so it is on for ENC3 only.  CEC_FUSED_BE=0/1
-// overrides (A/B).
-bool fused_be(bool dflt) {
-    const int v = knobs().fused_be;
-    return v >= 0 ? v == 1 : dflt;
-}
-
-// CEC_FUSED_ENC3=0 turns the SIMD-3 encoder placement of the two-SHA-wave build off (A/B).
-bool fused_enc3() { return knobs().fused_enc3; }
-
-// CEC_FUSED_MODE: 3 = the generic-d build on every shape it covers (correct output; A/B and
-// tests against the shape builds).  Modes 1 and 2 (timing attribution, wrong outputs by design)
-// exist only in the A/B build (-DCEC_AB_TOOLS, `make ab`): the product library ignores them.
-int fused_mode() {
-    const int m = knobs().fused_mode;
-#ifdef CEC_AB_TOOLS
-    return m;
-#else
-    return m == 3 ? 3 : 0;
-#endif
-}
+// CEC_FUSED_MODE (test knob): 3 = the generic-d build on every shape it covers (tests against
+// the shape builds); any other value is ignored.
+bool generic_build_forced() { return knobs().fused_mode == 3; }
 
 template <int STEP>
 hipError_t launch_step(const FusedParams& a, hipStream_t s) {
-    const int mode = fused_mode();
     if constexpr (STEP == 256) {
-#ifdef CEC_AB_TOOLS
-        if (mode == 1)
-            return a.p == 4 ? launch_p<4, STEP, 1, 0>(a, s) : launch_p<8, STEP, 1, 0>(a, s);
-        if (mode == 2)
-            return a.p == 4 ? launch_p<4, STEP, 2, 0>(a, s) : launch_p<8, STEP, 2, 0>(a, s);
-#endif
-        // mode 3: the generic-d build on every shape it covers (A/B and tests against the
-        // shape builds)
-        if (mode != 3 && a.d == 10 && a.p == 4 && a.len % col_width(10) == 0)
-            return fused_be(false) ? launch_p<4, STEP, 0, 10, 4, false, true>(a, s)
-                                   : launch_p<4, STEP, 0, 10, 4, false, false>(a, s);
+        if (!generic_build_forced() && a.d == 10 && a.p == 4 && a.len % col_width(10) == 0)
+            return launch_p<4, STEP, 10>(a, s);
     }
     if constexpr (STEP == 128) {
         if (a.d == 20) {  // RS(20, p <= 8); launch_encode_hash checked len % col_width(20)
-            return launch_p<8, STEP, 0, 20>(a, s);
+            return launch_p<8, STEP, 20>(a, s);
         }
     }
-    return a.p <= 4 ? launch_p<4, STEP, 0, 0>(a, s) : launch_p<8, STEP, 0, 0>(a, s);
+    return a.p <= 4 ? launch_p<4, STEP, 0>(a, s) : launch_p<8, STEP, 0>(a, s);
 }
 
 }  // namespace
@@ -517,19 +476,17 @@ hipError_t launch_encode_hash(const FusedParams& in, bool vec16, hipStream_t s) 
     // RS(20,p) batches with more chunks than one SHA wave per SIMD holds: two SHA waves per
     // SIMD (8 + 4 waves per workgroup), one workgroup per CU, 64-byte steps (the ring for 16
     // parts x 28 chunks then fits beside the 40 KB of tables), parts spread over every CU.
-    if (a.d == 20 && fused_mode() != 3) {
+    if (a.d == 20 && !generic_build_forced()) {
         const uint32_t cus = uint32_t(device_cus());
         if (uint64_t(a.n_parts) * t > uint64_t(cus) * kShaLanes) {
             const uint32_t cap = std::min(2 * kShaLanes / t, kEncThreads / (64u / 8u));
             const uint32_t want = uint32_t((uint64_t(a.n_parts) + cus - 1) / cus);
             a.parts_per_wg = std::min(cap, want);
-            a.enc_prio = fused_prio(1u);
+            a.enc_prio = 1u;  // encoder waves at s_setprio 1 (see the kernel's encoder branch)
             if (size_t(2) * a.parts_per_wg * t * (64 + 16) + size_t(20) * 256 * 8 <= 160 * 1024) {
-                if (fused_enc3() && a.parts_per_wg * t <= 7 * 64 &&
-                    a.parts_per_wg * (64u / 8u) <= 128)
-                    return fused_be(true) ? launch_p<8, 64, 0, 20, 8, true, true>(a, s)
-                                          : launch_p<8, 64, 0, 20, 8, true, false>(a, s);
-                return launch_p<8, 64, 0, 20, 8>(a, s);
+                if (a.parts_per_wg * t <= 7 * 64 && a.parts_per_wg * (64u / 8u) <= 128)
+                    return launch_p<8, 64, 20, 8, true>(a, s);
+                return launch_p<8, 64, 20, 8>(a, s);
             }
         }
     }
@@ -537,7 +494,7 @@ hipError_t launch_encode_hash(const FusedParams& in, bool vec16, hipStream_t s) 
     // else 128-byte steps (wide p = 8 stripes).
     const size_t tabs = size_t(a.d > uint32_t(kMaxFusedData) ? a.d : kMaxFusedData) * 256 *
                         (a.p <= 4 ? 4 : 8);
-    a.enc_prio = fused_prio(0u);
+    a.enc_prio = 0u;
     a.parts_per_wg = parts_per_group(t, 256);
     if (a.d <= uint32_t(kMaxFusedData) &&
         size_t(2) * a.parts_per_wg * t * (256 + 16) + tabs <= 160 * 1024)

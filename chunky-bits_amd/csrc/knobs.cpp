@@ -4,7 +4,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
-#include <cstring>
 #include <mutex>
 
 #include "chunky_ec.h"
@@ -44,32 +43,6 @@ Knobs* parse() {
         k->idle_staging_bytes = size_t(number("CEC_IDLE_STAGING_MIB", 1024)) << 20;
     k->multi_copy_threads = unsigned(
         std::min<unsigned long long>(std::max(number("CEC_MULTI_COPY_THREADS", 4), 1ull), 32ull));
-#ifdef CEC_AB_TOOLS
-    // The losing arms of finished A/B experiments (profiles/HISTORY.md): read only
-    // by the A/B build (`make ab`, tools/ab/libchunky_ec.so); the product library keeps every
-    // one of them at the measured winner.
-    if (const char* e = std::getenv("CEC_APPLY_TUNE"))
-        k->apply_tune = (std::strstr(e, "nt") ? 1 : 0) | (std::strstr(e, "g8") ? 2 : 0) |
-                        (std::strstr(e, "v1") ? 4 : 0);
-    k->apply_xcd = flag("CEC_APPLY_XCD", true);
-    if (const char* e = std::getenv("CEC_APPLY_BLOCKS_PER_CU")) k->apply_blocks_per_cu = std::atoi(e);
-    k->apply_rg_classes = flag("CEC_APPLY_RGCLS", true);
-    k->apply_cd = flag("CEC_APPLY_CD", true);
-    k->apply_tile = number("CEC_APPLY_TILE", 0);
-    if (const char* e = std::getenv("CEC_FUSED_PRIO"))
-        if (e[0] >= '0' && e[0] <= '2') k->fused_prio = e[0] - '0';
-    if (const char* e = std::getenv("CEC_FUSED_BE"))
-        if (e[0] == '0' || e[0] == '1') k->fused_be = e[0] - '0';
-    k->fused_enc3 = flag("CEC_FUSED_ENC3", true);
-    if (const char* e = std::getenv("CEC_COALESCE_D2H_WAIT"))
-        k->coalesce_d2h_host_wait = std::strcmp(e, "device") != 0;
-    k->coalesce_early_d2h = flag("CEC_COALESCE_EARLY_D2H", true);
-    if (const char* e = std::getenv("CEC_COALESCE_EARLY_H2D")) k->coalesce_early_h2d = e[0] == '1';
-    k->coalesce_adaptive = flag("CEC_COALESCE_ADAPT", true);
-    if (const char* e = std::getenv("CEC_SPEC_LDS_KIB")) k->spec_lds = uint32_t(std::atoi(e)) * 1024u;
-    k->read_speculate = flag("CEC_READ_SPECULATE", true);
-    k->verify_compact = flag("CEC_VERIFY_COMPACT", true);
-#endif
     return k;
 }
 

@@ -39,7 +39,7 @@ namespace {
 using namespace gf;
 
 constexpr int kApplyThreads = 256;
-constexpr uint64_t kApplyTile = 16384;  // default bytes of one part's column range per block
+constexpr uint64_t kApplyTile = 16384;  // bytes of one part's column range per block
 constexpr uint64_t kSpan = uint64_t(kApplyThreads) * 16u;  // bytes per block per column step
 constexpr uint32_t kMaxApplyRows = 8;
 
@@ -136,10 +136,16 @@ __device__ __forceinline__ void apply_column(uint8_t* pbase, uint64_t cs, uint64
 // One 16 KiB column tile of one part, rows [row0, row0 + RG) of its pattern record (n_out rows
 // in all).  Full column steps (kSpan*V bytes, aligned layout) take the V-wide path; the rest
 // (ragged end, unaligned layouts) the byte-granular single-column path.
-template <int RG, bool VEC, int GROUP, int V, bool NT>
+// VEC (16-byte aligned layout): two columns per lane per step, non-temporal loads and stores;
+// else one byte-granular column.  Both load 4 inputs before any is multiplied.  Measured on C2
+// encode (MI355X): non-temporal 10.79 ms, plain 11.20, one column 11.25, one column
+// non-temporal 11.15, groups of 8 11.26, non-temporal groups of 8 10.85.
+template <int RG, bool VEC>
 __device__ __forceinline__ void apply_tile(const ApplyParams& a, cu32* pat, uint32_t part,
                                            uint32_t tile, uint32_t n_out, uint32_t row0,
                                            uint32_t tile_bytes) {
+    constexpr int GROUP = 4, V = VEC ? 2 : 1;
+    constexpr bool NT = VEC;
     const uint32_t d = a.d;
     cu32* in_idx = pat + 1;
     cu32* out_idx = pat + 1 + d + row0;
@@ -167,8 +173,8 @@ __device__ __forceinline__ void apply_tile(const ApplyParams& a, cu32* pat, uint
 
 // ---- compile-time d: the same multiply with every input's loads issued one group ahead ----
 // With d a run-time value the column loop above waits for each group's loads before it multiplies
-// (`unroll 1`, no prefetch across groups).  For the compiled input counts (rs_apply_var_kernel's
-// CDG instantiations) the loop unrolls at compile time and group J0 + G's loads go out before
+// (`unroll 1`, no prefetch across groups).  For the compiled input count (rs_apply_var_kernel's
+// CD = 10 builds) the loop unrolls at compile time and group J0 + G's loads go out before
 // group J0's multiplies, as in the bit-sliced encoder.
 template <int D, int G, int J0, int V>
 __device__ __forceinline__ void vp_load(uint4 (&v)[G][V], const uint8_t* pbase, uint64_t cs,
@@ -289,7 +295,7 @@ __device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t n) {
 // grid.x = n_parts * tiles_per_part (one 16 KiB column tile of one part per block),
 // grid.y = row groups of exactly RG output rows starting at row_base.  xcd: block order of
 // xcd_block (else launch order).
-template <int RG, bool VEC, int GROUP, int V, bool NT>
+template <int RG, bool VEC>
 __global__ __launch_bounds__(kApplyThreads) void rs_apply_kernel(ApplyParams a,
                                                                  uint32_t tiles_per_part,
                                                                  uint32_t row_base, bool xcd,
@@ -299,8 +305,7 @@ __global__ __launch_bounds__(kApplyThreads) void rs_apply_kernel(ApplyParams a,
     const uint32_t tile = bx - lp * tiles_per_part;
     const uint32_t part = a.part_ids ? as_const(a.part_ids)[lp] : lp;
     cu32* pat = as_const(a.pat) + (a.part_pat ? as_const(a.part_pat)[lp] : 0u);
-    apply_tile<RG, VEC, GROUP, V, NT>(a, pat, part, tile, a.n_rows, row_base + blockIdx.y * RG,
-                                      tile_bytes);
+    apply_tile<RG, VEC>(a, pat, part, tile, a.n_rows, row_base + blockIdx.y * RG, tile_bytes);
 }
 
 // Reconstruct with mixed erasure counts in ONE launch: every listed part's pattern carries its
@@ -308,8 +313,13 @@ __global__ __launch_bounds__(kApplyThreads) void rs_apply_kernel(ApplyParams a,
 // to the exact-RG body, so no row is predicated inside the inner loop.  MAXRG is the batch's
 // largest row count rounded up to 2, 4 or 8 (host side): the kernel's register allocation is the
 // widest body's, so a 2-erasure batch compiled for 8 rows would run at half the occupancy.
-// CD > 0 (aligned non-temporal builds only): the batch's d equals CD (host-checked), every tile
-// takes apply_tile_cd with loads CDG inputs ahead.
+// CD > 0 (aligned builds only): the batch's d equals CD (host-checked), every tile takes
+// apply_tile_cd with loads kCdGroup inputs ahead.  Interleaved on one box with the residency
+// caps (profiles/r3_cap_ab/), against the run-time-d kernel: c3e2 8.07-8.09 vs 8.12-8.14 ms,
+// C3 9.64-9.68 vs 9.71-9.75 (groups of 2 and 10 measured the same as 5 without the caps,
+// profiles/r3_cd_ab/).
+constexpr int kCdGroup = 5;
+
 template <int RG, int MAXRG, typename F>
 __device__ __forceinline__ void rg_dispatch(uint32_t n, F&& f) {
     if (n == RG) f(std::integral_constant<int, RG>{});
@@ -318,7 +328,7 @@ __device__ __forceinline__ void rg_dispatch(uint32_t n, F&& f) {
     // every listed record against the launch's row class (capi.cpp reconstruct_batch)
 }
 
-template <bool VEC, int GROUP, int V, bool NT, int MAXRG, int CD = 0, int CDG = 0>
+template <bool VEC, int MAXRG, int CD = 0>
 __global__ __launch_bounds__(kApplyThreads) void rs_apply_var_kernel(ApplyParams a,
                                                                      uint32_t tiles_per_part,
                                                                      bool xcd, uint32_t tile_bytes) {
@@ -330,10 +340,10 @@ __global__ __launch_bounds__(kApplyThreads) void rs_apply_var_kernel(ApplyParams
     rg_dispatch<1, MAXRG>(pat[0], [&](auto rg) {
         constexpr int RG = decltype(rg)::value;
         if constexpr (CD > 0) {
-            static_assert(VEC && V == 2 && NT, "compile-time d: aligned non-temporal build");
-            apply_tile_cd<CD, RG, CDG>(a, pat, part, tile, RG, tile_bytes);
+            static_assert(VEC, "compile-time d: aligned build");
+            apply_tile_cd<CD, RG, kCdGroup>(a, pat, part, tile, RG, tile_bytes);
         } else {
-            apply_tile<RG, VEC, GROUP, V, NT>(a, pat, part, tile, RG, 0, tile_bytes);
+            apply_tile<RG, VEC>(a, pat, part, tile, RG, 0, tile_bytes);
         }
     });
 }
@@ -553,17 +563,6 @@ __global__ __launch_bounds__(256) void fill_kernel(FillParams a, bool aligned8) 
     }
 }
 
-// CEC_APPLY_TUNE (tuning knob, latched once: knobs.hpp; unset = "nt"): "nt" = non-temporal loads and
-// stores, "v1" = one 16-byte column per lane per step instead of two, "g8" = 8 inputs in
-// flight per lane instead of 4; any other string = plain loads, two columns, groups of 4.
-// Measured on C2 encode (tools/apply_ab.py, MI355X): nt 10.79 ms, plain 11.20, v1 11.25,
-// v1+nt 11.15, g8 11.26, nt+g8 10.85.
-int apply_tune() { return knobs().apply_tune; }
-
-// CEC_APPLY_XCD (A/B knob; unset = 1): 0 launches the apply kernels' blocks in
-// plain launch order instead of the XCD-aware order (xcd_block).
-bool apply_xcd() { return knobs().apply_xcd; }
-
 // LDS of one CU on the current device, cached per device: 160 KiB on gfx950 (MI355X), else
 // what the runtime reports (hipDeviceAttributeMaxSharedMemoryPerMultiprocessor); 0 when
 // unknown, which turns the residency caps below off rather than mis-sizing them.
@@ -600,13 +599,11 @@ uint32_t lds_per_cu() {
 // RS(20,8) encode no different (3 by registers).  The cap is an unused LDS reservation (160 KiB
 // per CU), on top of any the caller asked for, and only for grids of at least kCapMinBlocks
 // blocks (the device-resident batches it was measured on; the host pipelines' 256-part batches
-// share the chip with SHA-256 kernels and keep the register-bound occupancy).
-// CEC_APPLY_BLOCKS_PER_CU (A/B knob): n > 0 caps every apply launch at n blocks
-// per CU, 0 turns the cap off; unset = the per-kernel default `def_cap` (0 = none).
+// share the chip with SHA-256 kernels and keep the register-bound occupancy).  `cap` is the
+// launching kernel's measured blocks per CU (0 = none).
 constexpr uint64_t kCapMinBlocks = 65536;
-uint32_t apply_lds(uint32_t reserve, int def_cap, uint64_t n_blocks) {
-    const int knob = knobs().apply_blocks_per_cu;
-    const int n = knob >= 0 ? knob : (n_blocks >= kCapMinBlocks ? def_cap : 0);
+uint32_t apply_lds(uint32_t reserve, int cap, uint64_t n_blocks) {
+    const int n = n_blocks >= kCapMinBlocks ? cap : 0;
     const uint32_t cu_lds = lds_per_cu();
     if (n <= 0 || n > 16 || cu_lds == 0) return reserve;
     // floor(cu_lds / lds) == n; a cap the part's LDS cannot express (lds above the per-launch
@@ -616,52 +613,12 @@ uint32_t apply_lds(uint32_t reserve, int def_cap, uint64_t n_blocks) {
     return std::max(reserve, lds);
 }
 
-// CEC_APPLY_RGCLS (A/B knob; unset = 1): 0 runs every reconstruct batch on the
-// var kernel compiled for 8 rows instead of the batch's row class (2, 4 or 8).
-bool apply_rg_classes() { return knobs().apply_rg_classes; }
-
-// CEC_APPLY_CD (A/B knob; unset = 1): for d == 10 reconstruct batches, the
-// compile-time-d var kernel (apply_tile_cd, loads 5 inputs ahead); 0 = the run-time-d kernel.
-// Interleaved on one box with the residency caps (profiles/r3_cap_ab/): c3e2 8.07-8.09 vs
-// 8.12-8.14 ms, C3 9.64-9.68 vs 9.71-9.75 (groups of 2 and 10 measured the same as 5 without
-// the caps, profiles/r3_cd_ab/).
-bool apply_cd() { return knobs().apply_cd; }
-
-// CEC_APPLY_TILE (A/B knob): bytes of one part's column range per block, a
-// multiple of 8 KiB (one full two-column step of a block) up to 256 KiB; default `def`:
-// kApplyTile for rs_apply_kernel, kBsTile for the bit-sliced encoder and the mixed-pattern
-// reconstruct.  Measured interleaved on one box with the residency caps
-// (profiles/r3_tilecap_ab/, 8 / 16 / 32 KiB): RS(10,4) bit-sliced encode 9.46 / 9.72 / 9.86 ms,
-// c3e2 7.89 / 7.96 / 8.39, C3 9.20 / 9.35 / 9.61.  (Without the caps C3 had preferred 16 KiB,
-// profiles/r3_tile2_ab/.)
+// Bytes of one part's column range per block (a kernel argument): kApplyTile for
+// rs_apply_kernel, kBsTile for the bit-sliced encoder and the mixed-pattern reconstruct.
+// Measured interleaved on one box with the residency caps (profiles/r3_tilecap_ab/, 8 / 16 /
+// 32 KiB): RS(10,4) bit-sliced encode 9.46 / 9.72 / 9.86 ms, c3e2 7.89 / 7.96 / 8.39, C3 9.20 /
+// 9.35 / 9.61.  (Without the caps C3 had preferred 16 KiB, profiles/r3_tile2_ab/.)
 constexpr uint64_t kBsTile = 8192;
-uint64_t apply_tile_bytes(uint64_t def = kApplyTile) {
-    const uint64_t v = knobs().apply_tile;
-    return v && v % 8192 == 0 && v <= (256u << 10) ? v : def;
-}
-
-// Launch KERNEL<PRE... VEC, GROUP, V, NT> as picked by the tuning knob; layouts that are not
-// 16-byte aligned take the byte-granular instantiation.
-template <typename Launch>
-hipError_t dispatch_apply(bool vec16, Launch&& go) {
-    if (!vec16) return go(std::integral_constant<int, -1>{});
-    switch (apply_tune()) {
-        case 1: return go(std::integral_constant<int, 1>{});
-        case 2: return go(std::integral_constant<int, 2>{});
-        case 3: return go(std::integral_constant<int, 3>{});
-        case 4: return go(std::integral_constant<int, 4>{});
-        case 5: return go(std::integral_constant<int, 5>{});
-        default: return go(std::integral_constant<int, 0>{});
-    }
-}
-
-// tune code -> template arguments
-template <int K> struct Tune {
-    static constexpr bool kVec = K >= 0;
-    static constexpr int kGroup = K >= 0 && (K & 2) ? 8 : 4;
-    static constexpr int kV = K < 0 || (K & 4) ? 1 : 2;
-    static constexpr bool kNt = K >= 0 && (K & 1);
-};
 
 // Lets `kernel` reserve `bytes` of dynamic LDS (a host-side attribute; set on every such launch,
 // since the instantiations share one function-pointer type).
@@ -705,25 +662,22 @@ hipError_t for_part_ranges(const ApplyParams& a, uint64_t max_parts, Fn fn) {
 template <int RG>
 hipError_t launch_rg(const ApplyParams& a, uint32_t row_base, uint32_t groups, bool vec16,
                      hipStream_t s) {
-    const uint64_t tb = apply_tile_bytes();
+    const uint64_t tb = kApplyTile;
     const uint64_t tiles = (a.len + tb - 1) / tb;
     const uint64_t max_blocks = max_apply_blocks();
     if (tiles > max_blocks) return hipErrorInvalidValue;
     return for_part_ranges(a, max_blocks / tiles, [&](const ApplyParams& b) {
         const dim3 grid(uint32_t(b.n_parts * tiles), groups);
-        return dispatch_apply(vec16, [&](auto k) {
-            using T = Tune<decltype(k)::value>;
-            auto* kern = &rs_apply_kernel<RG, T::kVec, T::kGroup, T::kV, T::kNt>;
-            // 1-3 rows: 3 blocks per CU (RS(2,1) / RS(4,2) / RS(8,2) / RS(6,3) encode 1-2 %
-            // faster than by registers, profiles/r3_vperm_shapes_ab/); 4+ rows: no gain
-            const uint32_t lds =
-                apply_lds(b.lds_reserve, RG <= 3 ? 3 : 0, uint64_t(grid.x) * groups);
-            if (!allow_lds(kern, lds)) return hipErrorInvalidValue;
-            clear_stale_error();
-            hipLaunchKernelGGL(kern, grid, dim3(kApplyThreads), lds, s, b,
-                               uint32_t(tiles), row_base, apply_xcd(), uint32_t(tb));
-            return hipGetLastError();
-        });
+        // layouts that are not 16-byte aligned take the byte-granular build
+        auto* kern = vec16 ? &rs_apply_kernel<RG, true> : &rs_apply_kernel<RG, false>;
+        // 1-3 rows: 3 blocks per CU (RS(2,1) / RS(4,2) / RS(8,2) / RS(6,3) encode 1-2 %
+        // faster than by registers, profiles/r3_vperm_shapes_ab/); 4+ rows: no gain
+        const uint32_t lds = apply_lds(b.lds_reserve, RG <= 3 ? 3 : 0, uint64_t(grid.x) * groups);
+        if (!allow_lds(kern, lds)) return hipErrorInvalidValue;
+        clear_stale_error();
+        hipLaunchKernelGGL(kern, grid, dim3(kApplyThreads), lds, s, b, uint32_t(tiles), row_base,
+                           /*xcd=*/true, uint32_t(tb));
+        return hipGetLastError();
     });
 }
 
@@ -741,13 +695,13 @@ hipError_t launch_rows(const ApplyParams& a, uint32_t rg, uint32_t row_base, uin
     }
 }
 
-// CEC_APPLY_BS (A/B knob; unset = 1): 0 sends the compiled shapes' encodes to
+// CEC_APPLY_BS (test knob; unset = 1): 0 sends the compiled shapes' encodes to
 // the v_perm kernel too.
 bool apply_bs() { return knobs().apply_bs; }
 
 template <int D, int P>
 hipError_t launch_bs(const ApplyParams& a, hipStream_t s) {
-    const uint64_t tb = apply_tile_bytes(kBsTile);
+    const uint64_t tb = kBsTile;
     const uint64_t tiles = (a.len + tb - 1) / tb;
     const uint64_t max_blocks = max_apply_blocks();
     if (tiles > max_blocks) return hipErrorInvalidValue;
@@ -761,7 +715,7 @@ hipError_t launch_bs(const ApplyParams& a, hipStream_t s) {
         if (!allow_lds(kern, lds)) return hipErrorInvalidValue;
         clear_stale_error();
         hipLaunchKernelGGL(kern, dim3(uint32_t(n_blocks)), dim3(kApplyThreads), lds, s, b,
-                           uint32_t(tiles), apply_xcd(), uint32_t(tb));
+                           uint32_t(tiles), /*xcd=*/true, uint32_t(tb));
         return hipGetLastError();
     });
 }
@@ -823,16 +777,16 @@ hipError_t launch_rs_apply_var(const ApplyParams& a, bool vec16, hipStream_t s) 
     if (a.n_parts == 0 || a.len == 0) return hipSuccess;
     if (!a.part_ids || !a.part_pat) return hipErrorInvalidValue;
     if (a.n_rows > kMaxApplyRows) return hipErrorInvalidValue;
-    const uint64_t tb = apply_tile_bytes(kBsTile);  // 8 KiB with the caps (see kBsTile)
+    const uint64_t tb = kBsTile;  // 8 KiB with the caps (see kBsTile)
     const uint64_t tiles = (a.len + tb - 1) / tb;
     const uint64_t max_blocks = max_apply_blocks();
     if (tiles > max_blocks) return hipErrorInvalidValue;
     // not under a caller's LDS reservation: the read path's decode beside the SHA-256
-    // verification (capi.cpp decode_lds) loses with it (c3r 44.0-44.5 vs 42.6-42.8 ms,
+    // verification (capi.cpp kDecodeLds) loses with it (c3r 44.0-44.5 vs 42.6-42.8 ms,
     // profiles/r3_c3r_ab/): its loads run ahead into the SHA chains' bandwidth
-    const bool cd = apply_cd() && a.lds_reserve == 0;
+    const bool cd = a.lds_reserve == 0;
     const uint32_t rows = a.n_rows ? a.n_rows : kMaxApplyRows;
-    const int cls = !apply_rg_classes() ? 8 : rows <= 2 ? 2 : rows <= 4 ? 4 : 8;  // MAXRG
+    const int cls = rows <= 2 ? 2 : rows <= 4 ? 4 : 8;  // MAXRG
     return for_part_ranges(a, max_blocks / tiles, [&](const ApplyParams& b) {
         const dim3 grid(uint32_t(b.n_parts * tiles));
         // 2-row class: 2 blocks per CU, 4-row class: 3, 8-row: by registers (3)
@@ -841,28 +795,20 @@ hipError_t launch_rs_apply_var(const ApplyParams& a, bool vec16, hipStream_t s) 
             if (!allow_lds(kern, lds)) return hipErrorInvalidValue;
             clear_stale_error();
             hipLaunchKernelGGL(kern, grid, dim3(kApplyThreads), lds, s, b,
-                               uint32_t(tiles), apply_xcd(), uint32_t(tb));
+                               uint32_t(tiles), /*xcd=*/true, uint32_t(tb));
             return hipGetLastError();
         };
         auto by_class = [&](auto k2, auto k4, auto k8) {
             return cls == 2 ? go(k2) : cls == 4 ? go(k4) : go(k8);
         };
-        if (vec16 && apply_tune() == 1 && b.d == 10 && cd)
-            return by_class(&rs_apply_var_kernel<true, 4, 2, true, 2, 10, 5>,
-                            &rs_apply_var_kernel<true, 4, 2, true, 4, 10, 5>,
-                            &rs_apply_var_kernel<true, 4, 2, true, 8, 10, 5>);
-        return dispatch_apply(vec16, [&](auto k) {
-            using T = Tune<decltype(k)::value>;
-            // the default build (nt) and the byte-granular one get the row classes; the other
-            // tuning codes are A/B builds at the full 8 rows
-            constexpr bool classes = decltype(k)::value == 1 || decltype(k)::value == -1;
-            if constexpr (classes)
-                return by_class(&rs_apply_var_kernel<T::kVec, T::kGroup, T::kV, T::kNt, 2>,
-                                &rs_apply_var_kernel<T::kVec, T::kGroup, T::kV, T::kNt, 4>,
-                                &rs_apply_var_kernel<T::kVec, T::kGroup, T::kV, T::kNt, 8>);
-            else
-                return go(&rs_apply_var_kernel<T::kVec, T::kGroup, T::kV, T::kNt, 8>);
-        });
+        if (vec16 && b.d == 10 && cd)
+            return by_class(&rs_apply_var_kernel<true, 2, 10>, &rs_apply_var_kernel<true, 4, 10>,
+                            &rs_apply_var_kernel<true, 8, 10>);
+        if (vec16)
+            return by_class(&rs_apply_var_kernel<true, 2>, &rs_apply_var_kernel<true, 4>,
+                            &rs_apply_var_kernel<true, 8>);
+        return by_class(&rs_apply_var_kernel<false, 2>, &rs_apply_var_kernel<false, 4>,
+                        &rs_apply_var_kernel<false, 8>);
     });
 }
 

@@ -91,16 +91,16 @@ int cec_current_device(int* device);
 int cec_set_device(int device);
 /* NUMA node of a device's PCIe root (-1 when unknown). */
 int cec_device_numa_node(int device);
-/* Static build description, e.g. "chunky_ec gfx950 ab_tools=0".  The product library is always
- * ab_tools=0: the timing-attribution kernels (wrong outputs by design) exist only in the
- * separate A/B build used by tools/ (DESIGN.md §6.1). */
+/* Static build description: "chunky_ec gfx950 ab_tools=0".  There is one build of the library;
+ * the timing-attribution kernels of earlier A/B builds (wrong outputs by design) are gone
+ * (DESIGN.md §6.3). */
 const char* cec_build_info(void);
 /* Provenance: 16 hex digits, the hash of the sources the library was built from
  * (chunky-bits_amd/csrc/source_hash.py: every .cpp, .hip and .hpp file of csrc, its Makefile
  * and this header).  The Python binding refuses a library whose id differs from its shipped sources. */
 const char* cec_build_id(void);
-/* Environment knobs (CEC_APPLY_*, CEC_FUSED*, CEC_SHA_VARIANT, CEC_COALESCE_*, CEC_READ_*, ...;
- * DESIGN.md §4) are read ONCE, on the first call that needs one, into an immutable snapshot;
+/* Environment knobs (CEC_APPLY_*, CEC_FUSED*, CEC_SHA_VARIANT, CEC_COALESCE_*, ...;
+ * DESIGN.md §6.3) are read ONCE, on the first call that needs one, into an immutable snapshot;
  * no launch path calls getenv (the reference drives the hot path from tokio worker threads,
  * where getenv racing a setenv is undefined behaviour).  Test-only: re-read them now (a test
  * that sets a knob calls this after setting it and again after restoring it).  No Rust binding

@@ -200,8 +200,8 @@ def test_write_pipeline_and_multi_argument_checks_precede_device_use():
 
 
 def test_product_library_has_no_attribution_kernels():
-    """The A/B attribution modes (wrong outputs by design) are compiled only into the separate
-    tools/ab build: the product library reports ab_tools=0."""
+    """The A/B attribution modes (wrong outputs by design) are not part of the library: it
+    reports ab_tools=0."""
     import chunky_ec as ce
     assert ce.build_info().startswith("chunky_ec gfx950 ab_tools=0")
 

@@ -893,12 +893,10 @@ def test_verify_batch_flags(variant, knob_env):
     assert torch.equal(ok.cpu(), want)
 
 
-@pytest.mark.parametrize("speculate", ["1"])  # CEC_READ_SPECULATE=0: A/B build only
-def test_read_batch_restores_data_and_reports_undecodable_parts(speculate, knob_env):
-    """file_part.rs:86-129 batched.  speculate=1: the decode runs from the loaded chunks
-    alongside verification and is redone for parts with a failed chunk; 0: verify, then decode
-    (CEC_READ_SPECULATE A/B knob).  Both must give the verified decode."""
-    knob_env.set("CEC_READ_SPECULATE", speculate)
+def test_read_batch_restores_data_and_reports_undecodable_parts():
+    """file_part.rs:86-129 batched.  The decode runs from the loaded chunks alongside
+    verification and is redone for parts with a failed chunk: it must give the verified
+    decode."""
     d, p, L, n = 10, 4, 4096 + 5, 12
     rs, buf, batch, dig = _encoded_batch(d, p, L, n, 41)
     t = d + p
@@ -961,12 +959,10 @@ def test_read_batch_present_flag_values():
 
 
 @pytest.mark.parametrize("variant", ["1", "2"])  # compacted item list in both SHA kernels
-@pytest.mark.parametrize("speculate", ["1"])  # CEC_READ_SPECULATE=0: A/B build only
-def test_read_batch_random_patterns_vs_oracle(speculate, variant, knob_env):
+def test_read_batch_random_patterns_vs_oracle(variant, knob_env):
     knob_env.set("CEC_SHA_VARIANT", variant)
     """d random chunks loaded per part (reader.rs / file_part.rs:86-122), a few corrupted;
     the rebuilt data chunks equal the oracle's reconstruct_data from the verified chunks."""
-    knob_env.set("CEC_READ_SPECULATE", speculate)
     d, p, L, n = 10, 4, 1 << 12, 64
     rs, buf, batch, dig = _encoded_batch(d, p, L, n, 43)
     t = d + p
@@ -1021,12 +1017,10 @@ def test_resilver_batch_cluster_style():
     assert torch.equal(buf, ref)
 
 
-@pytest.mark.parametrize("speculate", ["1"])  # CEC_READ_SPECULATE=0: A/B build only
-def test_resilver_batch_random_patterns_with_corruption(speculate, knob_env):
+def test_resilver_batch_random_patterns_with_corruption():
     """FilePart::resilver compute (file_part.rs:253-308) batched: random loaded sets (d..d+p),
     some loaded chunks corrupted (including ones the speculative decode uses); every decodable
     part ends with all d+p chunks equal to the written ones, flags mark the bad chunks."""
-    knob_env.set("CEC_READ_SPECULATE", speculate)
     d, p, L, n = 6, 3, 2048 + 7, 40
     rs, buf, batch, dig = _encoded_batch(d, p, L, n, 61)
     t = d + p
