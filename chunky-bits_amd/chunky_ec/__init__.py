@@ -124,6 +124,11 @@ _sig("cec_reconstruct_data", [_vp, ctypes.POINTER(_u8p), _szp, _u8p, ctypes.c_si
 _sig("cec_sha256", [_u8p, ctypes.c_size_t, _u8p])
 _sig("cec_sha256_many", [ctypes.POINTER(_u8p), _szp, ctypes.c_size_t, _u8p])
 _sig("cec_part_encode", [_vp, _u8p, ctypes.c_size_t, _u8p, _u8p, _szp])
+_sig("cec_parts_encode", [_vp, ctypes.POINTER(_u8p), _szp, ctypes.c_size_t, ctypes.POINTER(_u8p),
+                          _u8p, _szp])
+_sig("cec_ragged_stride", [ctypes.c_size_t], ctypes.c_size_t)
+_sig("cec_ragged_layout", [ctypes.c_size_t, _szp, ctypes.c_size_t, _szp, _szp])
+_sig("cec_encode_hash_ragged", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _vp, _vp])
 _sig("cec_coalesce_stats", [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
      None)
 _sig("cec_encode_batch", [_vp, ctypes.POINTER(PartBatchStruct), _vp])
@@ -498,6 +503,36 @@ def part_encode(codec: ReedSolomon, data_buf, length: int) -> EncodedPart:
     )
 
 
+def parts_encode(codec: ReedSolomon, bufs: Sequence) -> List[EncodedPart]:
+    """:func:`part_encode` for parts of unrelated lengths in ONE engine call
+    (``cec_parts_encode``): part k is the whole of ``bufs[k]``, read as it is -- the engine pads
+    to ``d * chunksize`` with zeros in its own staging.  Results equal ``part_encode(codec,
+    bufs[k], len(bufs[k]))`` part by part."""
+    d, p = codec.data_shard_count(), codec.parity_shard_count()
+    n = len(bufs)
+    if n == 0:
+        return []
+    keep: list = []
+    lens = [_nbytes(b) for b in bufs]
+    Ls = [(ln + d - 1) // d for ln in lens]
+    ptrs = (_u8p * n)(*[_buf_ptr(b, keep) for b in bufs])
+    c_lens = (ctypes.c_size_t * n)(*lens)
+    pars = [(ctypes.c_uint8 * max(p * L, 1))() for L in Ls]
+    par_ptrs = (_u8p * n)(*[ctypes.cast(x, _u8p) for x in pars])
+    dig = (ctypes.c_uint8 * (32 * (d + p) * n))()
+    cs = (ctypes.c_size_t * n)()
+    _check(_lib.cec_parts_encode(codec.handle, ptrs, c_lens, n, par_ptrs, dig, cs))
+    draw = bytes(dig)
+    out = []
+    for k in range(n):
+        raw, L, d0 = bytes(pars[k]), Ls[k], 32 * (d + p) * k
+        out.append(EncodedPart(
+            chunksize=cs[k],
+            parity=[raw[i * L:(i + 1) * L] for i in range(p)],
+            hashes=[Sha256Hash(draw[d0 + 32 * i:d0 + 32 * (i + 1)]) for i in range(d + p)]))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # Device-resident batches
 # ---------------------------------------------------------------------------------------------
@@ -546,6 +581,36 @@ def encode_hash_batch(codec: ReedSolomon, batch: PartBatch, digests_ptr: int,
     s = batch.struct()
     _check(_lib.cec_encode_hash_batch(codec.handle, ctypes.byref(s), digests_ptr,
                                       _stream_ptr(stream)))
+
+
+def ragged_stride(chunk_len: int) -> int:
+    """Chunk stride of a ragged batch: ``chunk_len`` rounded up to 16."""
+    return _lib.cec_ragged_stride(chunk_len)
+
+
+def ragged_layout(total_shards: int, chunk_lens: Sequence[int]):
+    """The packed ragged layout of parts with these chunk lengths: ``(part_offsets,
+    total_bytes)``; part k's chunk i is at ``part_offsets[k] + i * ragged_stride(chunk_lens[k])``."""
+    n = len(chunk_lens)
+    lens = (ctypes.c_size_t * max(n, 1))(*chunk_lens)
+    offs = (ctypes.c_size_t * max(n, 1))()
+    total = ctypes.c_size_t(0)
+    _check(_lib.cec_ragged_layout(total_shards, lens, n, offs, ctypes.byref(total)))
+    return list(offs[:n]), total.value
+
+
+def encode_hash_ragged(codec: ReedSolomon, base_ptr: int, part_offsets: Sequence[int],
+                       chunk_lens: Sequence[int], digests_ptr: int, stream=None) -> None:
+    """encode_sep + SHA-256 of all d+p chunks of parts of different chunk lengths, one launch
+    sequence (``cec_encode_hash_ragged``): device memory at ``base_ptr`` in the layout of
+    :func:`ragged_layout`, digests ``[n][d+p][32]`` at ``digests_ptr``."""
+    n = len(chunk_lens)
+    if len(part_offsets) != n:
+        raise ValueError("part_offsets and chunk_lens differ in length")
+    offs = (ctypes.c_size_t * max(n, 1))(*part_offsets)
+    lens = (ctypes.c_size_t * max(n, 1))(*chunk_lens)
+    _check(_lib.cec_encode_hash_ragged(codec.handle, base_ptr, offs, lens, n, digests_ptr,
+                                       _stream_ptr(stream)))
 
 
 def sha256_batch(batch: PartBatch, first_chunk: int, n_chunks: int, digests_ptr: int,

@@ -21,6 +21,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -1172,6 +1173,245 @@ void coalesce_stats(uint64_t* calls, uint64_t* launches) {
     if (launches) *launches = g_launches.load();
 }
 
+// ------------------------------------------------------------------------------------------
+// Ragged batches (cec_encode_hash_ragged, cec_parts_encode): parts of different chunk lengths,
+// part k's chunk i at base + off[k] + i * stride(L_k), stride = L rounded up to 16.
+// ------------------------------------------------------------------------------------------
+constexpr size_t kRaggedAlign = 16;
+
+// L rounded up to 16; false when that overflows.
+bool ragged_stride(size_t L, size_t* out) {
+    if (L > SIZE_MAX - (kRaggedAlign - 1)) return false;
+    *out = (L + kRaggedAlign - 1) / kRaggedAlign * kRaggedAlign;
+    return true;
+}
+
+// The packed layout: part k+1 directly behind part k.
+int ragged_layout(size_t t, const size_t* lens, size_t n, size_t* offs, size_t* total) {
+    size_t off = 0;
+    for (size_t k = 0; k < n; ++k) {
+        if (lens[k] == 0) return CEC_EMPTY_SHARD;
+        size_t cs = 0, span = 0;
+        if (!ragged_stride(lens[k], &cs) || __builtin_mul_overflow(t, cs, &span) ||
+            span > SIZE_MAX - off)
+            return CEC_ERR_INVALID_ARGUMENT;
+        offs[k] = off;
+        off += span;
+    }
+    *total = off;
+    return CEC_OK;
+}
+
+// Every argument check of cec_encode_hash_ragged (no device use); *units = the launch's work
+// units.
+int ragged_check(const cec_codec* c, const uint8_t* base, const size_t* offs, const size_t* lens,
+                 size_t n, uint64_t* units) {
+    const size_t t = c->d + c->p;
+    size_t items = 0;  // SHA-256 items are 32-bit (checked before the arrays are walked)
+    if (__builtin_mul_overflow(n, t, &items) || items > 0xFFFFFFFFull)
+        return CEC_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < n; ++k)
+        if (lens[k] == 0) return CEC_EMPTY_SHARD;
+    if (reinterpret_cast<uintptr_t>(base) % kRaggedAlign) return CEC_ERR_INVALID_ARGUMENT;
+    const uint64_t unit = ragged_unit_bytes(), max_units = ragged_max_units();
+    uint64_t total = 0;
+    size_t end = 0;  // first byte behind the parts so far
+    for (size_t k = 0; k < n; ++k) {
+        size_t cs = 0, span = 0;
+        if (offs[k] % kRaggedAlign || offs[k] < end) return CEC_ERR_INVALID_ARGUMENT;
+        if (!ragged_stride(lens[k], &cs) || __builtin_mul_overflow(t, cs, &span) ||
+            span > SIZE_MAX - offs[k])
+            return CEC_ERR_INVALID_ARGUMENT;
+        end = offs[k] + span;
+        total += (uint64_t(lens[k] - 1)) / unit + 1;
+        if (total > max_units) return CEC_ERR_INVALID_ARGUMENT;  // never a silent wrap
+    }
+    *units = total;
+    return CEC_OK;
+}
+
+// The launches of a checked ragged batch on `s`: one upload of the per-part words (prefix array
+// of work units, offsets and lengths, the SHA-256 item list), the GF(2^8) kernel, the SHA-256
+// kernel.  The host arrays are copied into the scratch buffer's page-locked mirror before this
+// returns.
+int ragged_launch(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* lens, size_t n,
+                  uint64_t units, uint8_t* digests, hipStream_t s) {
+    const size_t t = c->d + c->p, items = n * t;
+    uint32_t* drec = nullptr;
+    CEC_TRY(c->encode_record(&drec));
+    // [ptrs u64 x items][lens u64 x items][order u32 x items][units u32 x n+1][parts u32 x 4n]
+    const size_t o_len = items * 8, o_ord = o_len + items * 8, o_units = o_ord + items * 4,
+                 o_parts = o_units + (n + 1) * 4, bytes = o_parts + n * 16;
+    Scratch sc;  // released on s behind the launches below
+    CEC_TRY(sc.acquire(bytes, s));
+    uint64_t* h_ptr = reinterpret_cast<uint64_t*>(sc.host());
+    uint64_t* h_len = reinterpret_cast<uint64_t*>(sc.host() + o_len);
+    uint32_t* h_ord = reinterpret_cast<uint32_t*>(sc.host() + o_ord);
+    uint32_t* h_units = reinterpret_cast<uint32_t*>(sc.host() + o_units);
+    uint32_t* h_parts = reinterpret_cast<uint32_t*>(sc.host() + o_parts);
+    const uint64_t unit = ragged_unit_bytes();
+    uint64_t acc = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const uint64_t L = lens[k], cs = (L + kRaggedAlign - 1) / kRaggedAlign * kRaggedAlign;
+        h_units[k] = uint32_t(acc);
+        acc += (L - 1) / unit + 1;
+        h_parts[4 * k + 0] = uint32_t(offs[k]);
+        h_parts[4 * k + 1] = uint32_t(uint64_t(offs[k]) >> 32);
+        h_parts[4 * k + 2] = uint32_t(L);
+        h_parts[4 * k + 3] = uint32_t(L >> 32);
+        for (size_t i = 0; i < t; ++i) {
+            h_ptr[k * t + i] = reinterpret_cast<uint64_t>(base + offs[k] + i * cs);
+            h_len[k * t + i] = L;
+        }
+    }
+    h_units[n] = uint32_t(acc);
+    // A SHA-256 wave runs as long as its longest lane: hand the chains out longest first, so the
+    // 64 of a wave have similar lengths.  Digests land at their item's place whatever the order.
+    std::vector<uint32_t> order(n);
+    for (size_t k = 0; k < n; ++k) order[k] = uint32_t(k);
+    std::stable_sort(order.begin(), order.end(),
+                     [&](uint32_t x, uint32_t y) { return lens[x] > lens[y]; });
+    for (size_t q = 0; q < n; ++q)
+        for (size_t i = 0; i < t; ++i) h_ord[q * t + i] = uint32_t(order[q] * t + i);
+    HIP_TRY(hipMemcpyAsync(sc.dev(), sc.host(), bytes, hipMemcpyHostToDevice, s));
+    RaggedParams a{};
+    a.base = base;
+    a.pat = drec;
+    a.units = reinterpret_cast<const uint32_t*>(sc.dev() + o_units);
+    a.parts = reinterpret_cast<const uint32_t*>(sc.dev() + o_parts);
+    a.n_parts = uint32_t(n);
+    a.total_units = uint32_t(units);
+    a.d = uint32_t(c->d);
+    a.n_rows = uint32_t(c->p);
+    HIP_TRY(launch_rs_encode_ragged(a, s));
+    ShaParams h{};
+    h.ptrs = reinterpret_cast<const uint64_t*>(sc.dev());
+    h.lens = reinterpret_cast<const uint64_t*>(sc.dev() + o_len);
+    h.n_parts = uint32_t(items);
+    h.n_chunks = 1;
+    h.digests = digests;
+    h.items = reinterpret_cast<const uint32_t*>(sc.dev() + o_ord);
+    h.n_items = uint32_t(items);
+    HIP_TRY(launch_sha256(h, true, s));
+    return CEC_OK;
+}
+
+// Arenas of cec_parts_encode: one per call in flight (pinned staging + device buffer + stream,
+// as the coalescer's leaders take), kept for the life of the process.
+class ArenaPool {
+   public:
+    Arena* take(int device) {
+        std::lock_guard<std::mutex> lk(mu_);
+        auto& v = free_[device];
+        if (v.empty()) {
+            all_.push_back(std::make_unique<Arena>());
+            all_.back()->dev.device = device;
+            return all_.back().get();
+        }
+        Arena* a = v.back();
+        v.pop_back();
+        return a;
+    }
+    void give(int device, Arena* a) {
+        std::lock_guard<std::mutex> lk(mu_);
+        free_[device].push_back(a);
+    }
+
+   private:
+    std::mutex mu_;
+    std::vector<std::unique_ptr<Arena>> all_;
+    std::map<int, std::vector<Arena*>> free_;
+};
+
+ArenaPool& ragged_arenas() {
+    static ArenaPool* pool = new ArenaPool();
+    return *pool;
+}
+
+// fn(k) for k < n on up to 8 threads: one per 16 MiB of `bytes` moved, so a call of a few small
+// parts never starts one.
+template <typename Fn>
+void for_parts(size_t n, size_t bytes, Fn fn) {
+    const size_t nt = std::min<size_t>({size_t(8), bytes / (size_t(16) << 20), n});
+    if (nt <= 1) {
+        for (size_t k = 0; k < n; ++k) fn(k);
+        return;
+    }
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (size_t k; (k = next.fetch_add(1, std::memory_order_relaxed)) < n;) fn(k);
+    };
+    std::vector<std::thread> th;
+    for (size_t i = 1; i < nt; ++i) th.emplace_back(work);
+    work();
+    for (auto& x : th) x.join();
+}
+
+// One round of cec_parts_encode: parts [0, n) of these arrays, packed, moved, encoded and hashed
+// together, results copied out.
+int parts_round(cec_codec* c, Arena& a, const uint8_t* const* bufs, const size_t* lengths,
+                size_t n, uint8_t* const* parity_outs, uint8_t* digests_out,
+                const size_t* chunk_lens) {
+    const size_t d = c->d, p = c->p, t = d + p;
+    std::vector<size_t> offs(n);
+    size_t total = 0;
+    CEC_TRY(ragged_layout(t, chunk_lens, n, offs.data(), &total));
+    uint64_t units = 0;
+    CEC_TRY(ragged_check(c, nullptr, offs.data(), chunk_lens, n, &units));
+    const size_t cap = coalesce_max_bytes();
+    CEC_TRY(a.in.reserve(total, cap / d * t + t * kRaggedAlign));
+    CEC_TRY(a.out.reserve(n * t * 32, cap / 8));
+    const size_t dig_bytes = round_up(n * t * 32, kChunkAlign);
+    CEC_TRY(ctx_reserve(a.dev, dig_bytes + total));
+    uint8_t* ddig = a.dev.dbuf;
+    uint8_t* dbase = a.dev.dbuf + dig_bytes;
+    uint8_t* stage = a.in.ptr;
+    size_t in_bytes = 0;
+    for (size_t k = 0; k < n; ++k) in_bytes += lengths[k];
+    // data chunk j of part k = bytes [j*L, (j+1)*L) of the caller's `length` bytes, zeros behind
+    for_parts(n, in_bytes, [&](size_t k) {
+        const size_t L = chunk_lens[k], cs = round_up(L, kRaggedAlign), len = lengths[k];
+        for (size_t j = 0; j < d; ++j) {
+            uint8_t* dst = stage + offs[k] + j * cs;
+            const size_t b0 = j * L, have = b0 < len ? std::min(L, len - b0) : 0;
+            if (have) std::memcpy(dst, bufs[k] + b0, have);
+            if (have < L) std::memset(dst + have, 0, L - have);
+        }
+    });
+    hipStream_t s = a.dev.stream;
+    const size_t last_cs = round_up(chunk_lens[n - 1], kRaggedAlign);
+    HIP_TRY(hipMemcpyAsync(dbase, stage, offs[n - 1] + d * last_cs, hipMemcpyHostToDevice, s));
+    CEC_TRY(ragged_launch(c, dbase, offs.data(), chunk_lens, n, units, ddig, s));
+    // The parity spans come back into the staging at their own offsets.  Neighbouring parts share
+    // a copy (the data chunks between their parity travel along) until the data in between is
+    // worth a copy call of its own (256 KiB: a few microseconds of the link either way).
+    constexpr size_t kGap = size_t(256) << 10;
+    for (size_t k = 0; k < n;) {
+        const size_t cs0 = round_up(chunk_lens[k], kRaggedAlign);
+        const size_t from = offs[k] + d * cs0;
+        size_t to = offs[k] + t * cs0;
+        size_t q = k + 1;
+        for (; q < n; ++q) {
+            const size_t cs = round_up(chunk_lens[q], kRaggedAlign);
+            if (d * cs >= kGap) break;
+            to = offs[q] + t * cs;
+        }
+        HIP_TRY(hipMemcpyAsync(stage + from, dbase + from, to - from, hipMemcpyDeviceToHost, s));
+        k = q;
+    }
+    HIP_TRY(hipMemcpyAsync(a.out.ptr, ddig, n * t * 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    size_t out_bytes = 0;
+    for (size_t k = 0; k < n; ++k) out_bytes += p * chunk_lens[k];
+    for_parts(n, out_bytes, [&](size_t k) {
+        const size_t L = chunk_lens[k], cs = round_up(L, kRaggedAlign);
+        for (size_t i = 0; i < p; ++i)
+            std::memcpy(parity_outs[k] + i * L, stage + offs[k] + (d + i) * cs, L);
+    });
+    std::memcpy(digests_out, a.out.ptr, n * t * 32);
+    return CEC_OK;
+}
+
 int batch_ok(const cec_part_batch* b) {
     if (!b || !b->base) return CEC_ERR_INVALID_ARGUMENT;
     return CEC_OK;
@@ -1349,6 +1589,93 @@ int cec_part_encode(const cec_codec* cc, const uint8_t* data_buf, size_t length,
                                   digests_out));
     *chunksize = L;
     return CEC_OK;
+}
+
+int cec_parts_encode(const cec_codec* cc, const uint8_t* const* data_bufs, const size_t* lengths,
+                     size_t n_parts, uint8_t* const* parity_outs, uint8_t* digests_out,
+                     size_t* chunksizes) {
+    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
+    if (n_parts == 0) return CEC_OK;
+    if (!data_bufs || !lengths || !parity_outs || !digests_out || !chunksizes)
+        return CEC_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < n_parts; ++k)
+        if (lengths[k] == 0) return CEC_EMPTY_SHARD;
+    for (size_t k = 0; k < n_parts; ++k)
+        if (!data_bufs[k] || !parity_outs[k]) return CEC_ERR_INVALID_ARGUMENT;
+    cec_codec* c = const_cast<cec_codec*>(cc);
+    const size_t d = c->d, t = c->d + c->p;
+    // Rounds of at most CEC_COALESCE_MAX_MIB of (padded) data chunks, a larger part alone; every
+    // round is checked before the first one runs, so an error leaves the outputs untouched.
+    std::vector<size_t> L(n_parts), round_end;
+    const size_t cap = coalesce_max_bytes();
+    size_t bytes = 0, first = 0;
+    for (size_t k = 0; k < n_parts; ++k) {
+        L[k] = (lengths[k] - 1) / d + 1;
+        size_t cs = 0, b = 0;
+        if (!ragged_stride(L[k], &cs) || __builtin_mul_overflow(d, cs, &b))
+            return CEC_ERR_INVALID_ARGUMENT;
+        if (k > first && (b > cap || bytes > cap - b)) {
+            round_end.push_back(k);
+            first = k;
+            bytes = 0;
+        }
+        bytes += std::min(b, cap);
+    }
+    round_end.push_back(n_parts);
+    {
+        std::vector<size_t> offs(n_parts);
+        size_t k0 = 0;
+        for (size_t k1 : round_end) {
+            size_t total = 0;
+            uint64_t units = 0;
+            CEC_TRY(ragged_layout(t, L.data() + k0, k1 - k0, offs.data(), &total));
+            CEC_TRY(ragged_check(c, nullptr, offs.data(), L.data() + k0, k1 - k0, &units));
+            k0 = k1;
+        }
+    }
+    int dev = 0;
+    CEC_TRY(current_device(&dev));
+    Arena* arena = ragged_arenas().take(dev);
+    int st = CEC_OK;
+    size_t k0 = 0;
+    for (size_t k1 : round_end) {
+        st = parts_round(c, *arena, data_bufs + k0, lengths + k0, k1 - k0, parity_outs + k0,
+                         digests_out + k0 * t * 32, L.data() + k0);
+        if (st != CEC_OK) break;
+        k0 = k1;
+    }
+    if (st != CEC_OK && arena->dev.stream) {  // nothing of a failed round stays in flight
+        (void)hipStreamSynchronize(arena->dev.stream);
+        (void)hipGetLastError();
+    }
+    ragged_arenas().give(dev, arena);
+    if (st != CEC_OK) return st;
+    for (size_t k = 0; k < n_parts; ++k) chunksizes[k] = L[k];
+    return CEC_OK;
+}
+
+size_t cec_ragged_stride(size_t chunk_len) {
+    size_t cs = 0;
+    return ragged_stride(chunk_len, &cs) ? cs : 0;
+}
+
+int cec_ragged_layout(size_t total_shards, const size_t* chunk_lens, size_t n_parts,
+                      size_t* part_offsets, size_t* total_bytes) {
+    if (!total_bytes || total_shards == 0) return CEC_ERR_INVALID_ARGUMENT;
+    if (n_parts && (!chunk_lens || !part_offsets)) return CEC_ERR_INVALID_ARGUMENT;
+    return ragged_layout(total_shards, chunk_lens, n_parts, part_offsets, total_bytes);
+}
+
+int cec_encode_hash_ragged(const cec_codec* cc, uint8_t* base, const size_t* part_offsets,
+                           const size_t* chunk_lens, size_t n_parts, uint8_t* digests,
+                           void* stream) {
+    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
+    if (n_parts == 0) return CEC_OK;
+    if (!base || !part_offsets || !chunk_lens || !digests) return CEC_ERR_INVALID_ARGUMENT;
+    uint64_t units = 0;
+    CEC_TRY(ragged_check(cc, base, part_offsets, chunk_lens, n_parts, &units));
+    return ragged_launch(const_cast<cec_codec*>(cc), base, part_offsets, chunk_lens, n_parts,
+                         units, digests, static_cast<hipStream_t>(stream));
 }
 
 void cec_coalesce_stats(uint64_t* calls, uint64_t* launches) {

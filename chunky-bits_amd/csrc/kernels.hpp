@@ -98,6 +98,26 @@ bool bs_encode_matches(uint32_t d, uint32_t p, const uint8_t* parity_rows);
 // checks this against the host records before every launch.
 hipError_t launch_rs_apply_var(const ApplyParams& a, bool vec16, hipStream_t s);
 uint32_t max_var_rows();
+
+// encode_sep over a ragged batch: part k's chunk i (d data then p parity) at
+// base + off[k] + i * stride(L_k), stride(L) = L rounded up to 16, base and off[k] multiples of
+// 16.  One wave per work unit (ragged_unit_bytes() of one part's columns); `units` is the prefix
+// array over the parts' unit counts (units[0] = 0, units[n_parts] = total_units) and `parts`
+// holds {off lo, off hi, L lo, L hi} per part (device memory, read as wave-uniform words).
+// Exactly L_k bytes of each parity chunk are written.
+struct RaggedParams {
+    uint8_t* base;
+    const uint32_t* pat;    // the codec's encode record
+    const uint32_t* units;  // [n_parts + 1]
+    const uint32_t* parts;  // [n_parts][4]
+    uint32_t n_parts;
+    uint32_t total_units;
+    uint32_t d;
+    uint32_t n_rows;
+};
+hipError_t launch_rs_encode_ragged(const RaggedParams& a, hipStream_t s);
+uint64_t ragged_unit_bytes();
+uint64_t ragged_max_units();  // most units one launch can address (grid and index limits)
 bool fused_supported(uint32_t d, uint32_t p);
 bool fused_covers(uint32_t d, uint32_t p, uint64_t len);
 hipError_t launch_encode_hash(const FusedParams& a, bool vec16, hipStream_t s);

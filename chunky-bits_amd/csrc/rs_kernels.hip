@@ -7,6 +7,8 @@
 //                       HBM-bound: algorithmic bytes per part = (d + n_out) * len.
 //  rs_apply_var_kernel  the same for a reconstruct batch whose parts miss different numbers of
 //                       chunks: one launch, each block dispatched on its pattern's row count.
+//  rs_apply_ragged_kernel  encode_sep for parts of different chunk lengths, one launch: one
+//                       wave per 4 KiB of a part's columns, found through a prefix array.
 //  fill_kernel          counter-based synthetic bytes for benchmarks/tests.
 //
 // GF multiply: no GF instruction exists, so a product c*x of four packed bytes is three
@@ -346,6 +348,66 @@ __global__ __launch_bounds__(kApplyThreads) void rs_apply_var_kernel(ApplyParams
             apply_tile<RG, VEC>(a, pat, part, tile, RG, 0, tile_bytes);
         }
     });
+}
+
+// ------------------------------------------------------------------------------------------
+// Ragged batch: parts whose chunk lengths differ, one launch.
+//
+// Part k's chunk i is at base + off[k] + i * stride(L_k), stride(L) = L rounded up to 16, base and
+// off[k] multiples of 16: every chunk starts 16-byte aligned and only its last column is partial.
+// The work unit is one WAVE's kRaggedUnit (4 KiB) column range of one part: a wave finds its
+// part with a binary search over the host-built prefix array of units (scalar loads, the wave
+// number made uniform with readfirstlane), then walks its unit in 1 KiB steps (64 lanes x one
+// 16-byte column) through apply_column.  The four waves of a workgroup are independent, so a
+// batch of thousands of sub-kilobyte parts spends one wave per part, and a 1 MiB chunk is 256
+// units that stream full 16-byte columns whatever the lengths of its neighbours.  Only the last
+// step of a part diverges: lanes with a whole column take the vector path, the one lane with the
+// chunk's last 1..15 bytes the byte path, lanes past the end nothing.
+// Plain (not non-temporal) loads: the SHA-256 launch behind it reads the same chunks again.
+// ------------------------------------------------------------------------------------------
+constexpr uint64_t kRaggedUnit = 4096;                  // bytes of one chunk's columns per wave
+constexpr uint64_t kRaggedStep = 64u * 16u;             // bytes per wave per column step
+constexpr uint32_t kRaggedWaves = kApplyThreads / 64;   // units per workgroup
+
+// grid.x = ceil(total_units / kRaggedWaves), grid.y = row groups of exactly RG rows from row_base.
+template <int RG>
+__global__ __launch_bounds__(kApplyThreads) void rs_apply_ragged_kernel(RaggedParams a,
+                                                                        uint32_t row_base) {
+    const uint32_t u = __builtin_amdgcn_readfirstlane(blockIdx.x * kRaggedWaves +
+                                                      (threadIdx.x >> 6));
+    if (u >= a.total_units) return;  // wave-uniform
+    cu32* pre = as_const(a.units);
+    uint32_t lo = 0, hi = a.n_parts;  // pre[lo] <= u < pre[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (pre[mid] <= u) lo = mid;
+        else hi = mid;
+    }
+    cu32* pm = as_const(a.parts) + size_t(lo) * 4;
+    const uint64_t off = uint64_t(pm[0]) | (uint64_t(pm[1]) << 32);
+    const uint64_t len = uint64_t(pm[2]) | (uint64_t(pm[3]) << 32);
+    const uint64_t cs = (len + 15) & ~uint64_t(15);
+    uint8_t* pbase = a.base + off;
+    const uint32_t d = a.d, n_out = a.n_rows, row0 = row_base + blockIdx.y * RG;
+    cu32* pat = as_const(a.pat);
+    cu32* in_idx = pat + 1;
+    cu32* out_idx = pat + 1 + d + row0;
+    cu32* tab = pat + 1 + d + n_out + size_t(row0) * kTabWords;
+    const uint32_t tab_stride = n_out * kTabWords;
+    const uint64_t x0 = uint64_t(u - pre[lo]) * kRaggedUnit;
+    const uint64_t x1 = x0 + kRaggedUnit < len ? x0 + kRaggedUnit : len;
+    const uint64_t lane_x = uint64_t(threadIdx.x & 63u) * 16u;
+#pragma unroll 1
+    for (uint64_t xb = x0; xb < x1; xb += kRaggedStep) {  // wave-uniform
+        const uint64_t x = xb + lane_x;
+        if (x + 16 <= len) {  // every lane of a step that is not the part's last
+            apply_column<RG, true, 4, 1, false>(pbase, cs, x, len - x, d, tab_stride, in_idx,
+                                                out_idx, tab);
+        } else if (x < len) {
+            apply_column<RG, false, 4, 1, false>(pbase, cs, x, len - x, d, tab_stride, in_idx,
+                                                 out_idx, tab);
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -813,6 +875,49 @@ hipError_t launch_rs_apply_var(const ApplyParams& a, bool vec16, hipStream_t s) 
 }
 
 uint32_t max_var_rows() { return kMaxApplyRows; }
+
+uint64_t ragged_unit_bytes() { return kRaggedUnit; }
+uint64_t ragged_max_units() { return kMaxApplyBlocks * kRaggedWaves; }
+
+namespace {
+
+template <int RG>
+hipError_t launch_ragged_rg(const RaggedParams& a, uint32_t row_base, uint32_t groups,
+                            hipStream_t s) {
+    const dim3 grid((a.total_units + kRaggedWaves - 1) / kRaggedWaves, groups);
+    clear_stale_error();
+    hipLaunchKernelGGL(rs_apply_ragged_kernel<RG>, grid, dim3(kApplyThreads), 0, s, a, row_base);
+    return hipGetLastError();
+}
+
+hipError_t launch_ragged_rows(const RaggedParams& a, uint32_t rg, uint32_t row_base,
+                              uint32_t groups, hipStream_t s) {
+    switch (rg) {
+        case 1: return launch_ragged_rg<1>(a, row_base, groups, s);
+        case 2: return launch_ragged_rg<2>(a, row_base, groups, s);
+        case 3: return launch_ragged_rg<3>(a, row_base, groups, s);
+        case 4: return launch_ragged_rg<4>(a, row_base, groups, s);
+        case 5: return launch_ragged_rg<5>(a, row_base, groups, s);
+        case 6: return launch_ragged_rg<6>(a, row_base, groups, s);
+        case 7: return launch_ragged_rg<7>(a, row_base, groups, s);
+        default: return launch_ragged_rg<8>(a, row_base, groups, s);
+    }
+}
+
+}  // namespace
+
+// Row groups as launch_rs_apply: up to kMaxApplyRows rows (every compiled shape) is one launch.
+hipError_t launch_rs_encode_ragged(const RaggedParams& a, hipStream_t s) {
+    if (a.n_parts == 0 || a.n_rows == 0 || a.total_units == 0) return hipSuccess;
+    if (a.total_units > ragged_max_units()) return hipErrorInvalidValue;
+    const uint32_t full = a.n_rows / kMaxApplyRows, rem = a.n_rows % kMaxApplyRows;
+    if (full) {
+        const hipError_t e = launch_ragged_rows(a, kMaxApplyRows, 0, full, s);
+        if (e != hipSuccess) return e;
+    }
+    if (rem) return launch_ragged_rows(a, rem, full * kMaxApplyRows, 1, s);
+    return hipSuccess;
+}
 
 
 hipError_t launch_fill(const FillParams& a, hipStream_t s) {

@@ -141,6 +141,32 @@ pub mod sys {
             digests_out: *mut u8,
             chunksize: *mut usize,
         ) -> c_int;
+        pub fn cec_parts_encode(
+            codec: *const cec_codec,
+            data_bufs: *const *const u8,
+            lengths: *const usize,
+            n_parts: usize,
+            parity_outs: *const *mut u8,
+            digests_out: *mut u8,
+            chunksizes: *mut usize,
+        ) -> c_int;
+        pub fn cec_ragged_stride(chunk_len: usize) -> usize;
+        pub fn cec_ragged_layout(
+            total_shards: usize,
+            chunk_lens: *const usize,
+            n_parts: usize,
+            part_offsets: *mut usize,
+            total_bytes: *mut usize,
+        ) -> c_int;
+        pub fn cec_encode_hash_ragged(
+            codec: *const cec_codec,
+            base: *mut u8,
+            part_offsets: *const usize,
+            chunk_lens: *const usize,
+            n_parts: usize,
+            digests: *mut u8,
+            stream: *mut c_void,
+        ) -> c_int;
         pub fn cec_encode_batch(
             codec: *const cec_codec,
             batch: *const cec_part_batch,
@@ -707,6 +733,104 @@ pub fn part_encode(
         })
         .collect();
     Ok((chunksize, parity, digests))
+}
+
+/// One part of [`parts_encode`]: (chunksize, parity chunks, d+p digests), as [`part_encode`].
+pub type EncodedPart = (usize, Vec<Vec<u8>>, Vec<[u8; 32]>);
+
+/// [`part_encode`] for parts of unrelated lengths in one engine call (`cec_parts_encode`): part k
+/// is the whole of `bufs[k]`, read as it is (the engine zero-pads to `d * chunksize` in its own
+/// staging).  Results equal `part_encode(codec, bufs[k], bufs[k].len())` part by part.
+pub fn parts_encode(codec: &ReedSolomon, bufs: &[&[u8]]) -> Result<Vec<EncodedPart>, CecError> {
+    if bufs.is_empty() {
+        return Ok(Vec::new());
+    }
+    let d = codec.data_shard_count();
+    let p = codec.parity_shard_count();
+    let n = bufs.len();
+    let ptrs: Vec<*const u8> = bufs.iter().map(|b| b.as_ptr()).collect();
+    let lens: Vec<usize> = bufs.iter().map(|b| b.len()).collect();
+    let ls: Vec<usize> = lens.iter().map(|&len| (len + d - 1) / d).collect();
+    let mut parity: Vec<Vec<u8>> = ls.iter().map(|&l| vec![0u8; p * l]).collect();
+    let parity_ptrs: Vec<*mut u8> = parity.iter_mut().map(|v| v.as_mut_ptr()).collect();
+    let mut digests = vec![0u8; 32 * (d + p) * n];
+    let mut chunksizes = vec![0usize; n];
+    check(unsafe {
+        sys::cec_parts_encode(
+            codec.raw,
+            ptrs.as_ptr(),
+            lens.as_ptr(),
+            n,
+            parity_ptrs.as_ptr(),
+            digests.as_mut_ptr(),
+            chunksizes.as_mut_ptr(),
+        )
+    })?;
+    Ok(parity
+        .iter()
+        .zip(ls.iter())
+        .zip(chunksizes.iter())
+        .zip(digests.chunks(32 * (d + p)))
+        .map(|(((par, &l), &cs), dig)| {
+            let chunks = par.chunks(l.max(1)).map(|c| c.to_vec()).take(p).collect();
+            let hashes = dig
+                .chunks(32)
+                .map(|c| {
+                    let mut a = [0u8; 32];
+                    a.copy_from_slice(c);
+                    a
+                })
+                .collect();
+            (cs, chunks, hashes)
+        })
+        .collect())
+}
+
+/// Chunk stride of a ragged batch: `chunk_len` rounded up to 16 (`cec_ragged_stride`).
+pub fn ragged_stride(chunk_len: usize) -> usize {
+    unsafe { sys::cec_ragged_stride(chunk_len) }
+}
+
+/// The packed ragged layout (`cec_ragged_layout`) of parts of `total_shards` chunks with these
+/// chunk lengths: (part offsets, total bytes).
+pub fn ragged_layout(total_shards: usize, chunk_lens: &[usize]) -> Result<(Vec<usize>, usize), CecError> {
+    let mut offs = vec![0usize; chunk_lens.len()];
+    let mut total = 0usize;
+    check(unsafe {
+        sys::cec_ragged_layout(total_shards, chunk_lens.as_ptr(), chunk_lens.len(), offs.as_mut_ptr(), &mut total)
+    })?;
+    Ok((offs, total))
+}
+
+/// `cec_encode_hash_ragged`: encode_sep + SHA-256 of all d+p chunks of parts of different chunk
+/// lengths in device memory, asynchronous on `stream`.
+///
+/// # Safety
+/// `base` and `digests` must be device pointers covering the layout the offsets and lengths
+/// describe and `[n][d+p][32]` bytes; `stream` a HIP stream of the current device or null.
+pub unsafe fn encode_hash_ragged(
+    codec: &ReedSolomon,
+    base: *mut u8,
+    part_offsets: &[usize],
+    chunk_lens: &[usize],
+    digests: *mut u8,
+    stream: *mut c_void,
+) -> Result<(), CecError> {
+    if part_offsets.len() != chunk_lens.len() {
+        return Err(CecError::Engine(EngineError {
+            code: 101,
+            message: "part_offsets and chunk_lens differ in length".to_string(),
+        }));
+    }
+    check(sys::cec_encode_hash_ragged(
+        codec.raw,
+        base,
+        part_offsets.as_ptr(),
+        chunk_lens.as_ptr(),
+        chunk_lens.len(),
+        digests,
+        stream,
+    ))
 }
 
 /// Batched `FileWriteBuilder::write` compute (writer.rs:166-231): `depth` slots of

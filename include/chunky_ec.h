@@ -187,6 +187,20 @@ int cec_sha256_many(const uint8_t* const* bufs, const size_t* lens, size_t n, ui
 int cec_part_encode(const cec_codec* codec, const uint8_t* data_buf, size_t length,
                     uint8_t* parity_out, uint8_t* digests_out, size_t* chunksize);
 
+/* cec_part_encode for n_parts parts of unrelated lengths in one call (a directory of small
+ * files, the short last parts of many files): part k is lengths[k] bytes at data_bufs[k] and
+ * ONLY those bytes are read -- the engine zero-pads to d*L_k (L_k = ceil(lengths[k] / d)) in its
+ * own staging.  parity_outs[k] receives p*L_k bytes (chunk i at + i*L_k), digests_out is
+ * [n_parts][d+p][32], chunksizes[k] = L_k.  The parts are packed in the cec_ragged_layout
+ * layout and encoded and hashed together (cec_encode_hash_ragged); a call with more than
+ * CEC_COALESCE_MAX_MIB of parts runs in several rounds, a single larger part alone.  Results
+ * are byte-identical to n_parts calls of cec_part_encode.  Any lengths[k] == 0 ->
+ * CEC_EMPTY_SHARD before anything is written; n_parts == 0 -> CEC_OK.  Concurrent calls are
+ * allowed. */
+int cec_parts_encode(const cec_codec* codec, const uint8_t* const* data_bufs,
+                     const size_t* lengths, size_t n_parts, uint8_t* const* parity_outs,
+                     uint8_t* digests_out, size_t* chunksizes);
+
 /* Per-call coalescing.  Concurrent cec_part_encode calls with the same codec and chunk length
  * (and concurrent cec_sha256 / cec_sha256_many calls) on the same device are gathered into one
  * launch: the first caller waits up to CEC_COALESCE_US microseconds (environment, default 200,
@@ -219,6 +233,31 @@ int cec_encode_batch(const cec_codec* codec, const cec_part_batch* batch, void* 
  * digests: device buffer of n_parts*(d+p)*32 bytes, part-major, chunks in order. */
 int cec_encode_hash_batch(const cec_codec* codec, const cec_part_batch* batch, uint8_t* digests,
                           void* stream);
+
+/* Ragged batch: parts whose chunk lengths differ, encoded and hashed in one launch sequence.
+ * Part k's chunk i (d data then p parity, in order) is chunk_lens[k] bytes at
+ *   base + part_offsets[k] + i * cec_ragged_stride(chunk_lens[k])
+ * with base and every offset a multiple of 16, so every chunk starts 16-byte aligned.
+ * cec_ragged_stride: chunk_len rounded up to 16.  cec_ragged_layout: the packed layout of
+ * n_parts parts of total_shards (= d+p) chunks each: part_offsets[k] (ascending, multiples of
+ * 16, part k+1 directly behind part k) and *total_bytes, the buffer size it needs;
+ * CEC_EMPTY_SHARD for a zero chunk length, CEC_ERR_INVALID_ARGUMENT for null pointers,
+ * total_shards == 0 or a size that overflows size_t.
+ * cec_encode_hash_ragged: encode_sep + SHA-256 of all d+p chunks of every part
+ * (write_with_encoder's compute); exactly chunk_lens[k] bytes of each parity chunk are written,
+ * never the padding up to the stride or anything between parts.  base and digests
+ * ([n_parts][d+p][32]) are DEVICE pointers; part_offsets and chunk_lens are HOST arrays, copied
+ * before the call returns.  Asynchronous on `stream`.  Errors, all before any device use: null
+ * pointer -> CEC_ERR_INVALID_ARGUMENT; any chunk_lens[k] == 0 -> CEC_EMPTY_SHARD; base or an
+ * offset not a multiple of 16, parts not ascending and disjoint (part_offsets[k+1] <
+ * part_offsets[k] + (d+p)*stride(chunk_lens[k])), or counts beyond the kernels' 32-bit indices
+ * -> CEC_ERR_INVALID_ARGUMENT.  n_parts == 0 -> CEC_OK, nothing launched. */
+size_t cec_ragged_stride(size_t chunk_len);
+int cec_ragged_layout(size_t total_shards, const size_t* chunk_lens, size_t n_parts,
+                      size_t* part_offsets, size_t* total_bytes);
+int cec_encode_hash_ragged(const cec_codec* codec, uint8_t* base, const size_t* part_offsets,
+                           const size_t* chunk_lens, size_t n_parts, uint8_t* digests,
+                           void* stream);
 
 /* SHA-256 of chunks [first_chunk, first_chunk + n_chunks) of every part.
  * digests: device buffer, digest of (part k, chunk first_chunk + c) at (k*n_chunks + c)*32. */

@@ -461,13 +461,20 @@ class ChunkStore {
     static Location location_of(const Sha256Hash& hash) { return "sha256-" + hash.to_string(); }
     Location write_shard(const Sha256Hash& hash, Bytes bytes) {
         Location loc = location_of(hash);
+        if (log_) log_->push_back(loc);
         if (!discard_) store_[loc] = std::move(bytes);
         return loc;
     }
     Location write_shard(const Sha256Hash& hash, const uint8_t* bytes, size_t n) {
-        if (discard_) return location_of(hash);  // no copy of bytes nobody keeps
+        if (discard_) {  // no copy of bytes nobody keeps
+            if (log_) log_->push_back(location_of(hash));
+            return location_of(hash);
+        }
         return write_shard(hash, Bytes(bytes, bytes + n));
     }
+    // Every later write_shard appends its location to *log, in call order (nullptr: stop).  The
+    // caller keeps *log alive while it is set.
+    void log_writes(std::vector<Location>* log) { log_ = log; }
     // Put bytes at any location (a replica elsewhere, a stale copy in tests).
     void put(const Location& loc, Bytes bytes) { store_[loc] = std::move(bytes); }
     std::optional<Bytes> read(const Location& loc) const {
@@ -494,6 +501,7 @@ class ChunkStore {
    private:
     std::map<Location, Bytes> store_;
     bool discard_ = false;
+    std::vector<Location>* log_ = nullptr;
 };
 
 // file::Chunk (chunk.rs:10-17): the hash of one chunk and the locations of its copies, in order.
@@ -1623,6 +1631,92 @@ class FileWriteBuilder {
         return file;
     }
     FileReference write(const Bytes& b, ChunkStore& dest) const { return write(b.data(), b.size(), dest); }
+
+    // write() for many files in one go: result[f] equals write(files[f].first, files[f].second,
+    // dest) -- same parts, chunksize, digests, stored chunks and length (an empty file has no
+    // parts) -- and the chunks reach dest.write_shard in file, part, chunk order.  The full parts
+    // of a file with at least two of them still go through write_full_parts when batch() is set;
+    // every other part of every file (whole small files, short last parts) is gathered, in
+    // windows of at most kManyWindowBytes, into ragged batches: one cec_parts_encode call per
+    // window, its pointers straight into the callers' bytes (the engine pads in its own staging).
+    static constexpr size_t kManyWindowBytes = size_t(256) << 20;
+    std::vector<FileReference> write_many(
+        const std::vector<std::pair<const uint8_t*, size_t>>& files, ChunkStore& dest) const {
+        if (concurrency_ <= 1) throw std::invalid_argument("concurrency must be > 1");  // :128
+        const ReedSolomon encoder(data_, parity_);
+        const size_t d = data_, p = parity_, t = d + p, part_cap = data_ * chunk_size_;
+        std::vector<FileReference> out(files.size());
+        struct Pending {
+            size_t file;
+            const uint8_t* bytes;
+            size_t length;
+        };
+        std::vector<Pending> pend;
+        size_t pend_bytes = 0;
+        auto flush = [&] {
+            const size_t n = pend.size();
+            if (n == 0) return;
+            std::vector<const uint8_t*> bufs(n);
+            std::vector<size_t> lengths(n), chunksizes(n);
+            std::vector<Bytes> parity(n);
+            std::vector<uint8_t*> parity_ptrs(n);
+            std::vector<uint8_t> digests(n * t * 32);
+            for (size_t k = 0; k < n; ++k) {
+                bufs[k] = pend[k].bytes;
+                lengths[k] = pend[k].length;
+                parity[k].resize(p * ((pend[k].length + d - 1) / d));
+                parity_ptrs[k] = parity[k].data();
+            }
+            detail::check(cec_parts_encode(encoder.raw(), bufs.data(), lengths.data(), n,
+                                           parity_ptrs.data(), digests.data(), chunksizes.data()));
+            Bytes edge;  // a data chunk that reaches past the file's bytes, zero padded
+            for (size_t k = 0; k < n; ++k) {
+                const size_t L = chunksizes[k], len = pend[k].length;
+                FilePart part;
+                part.chunksize = L;
+                for (size_t i = 0; i < t; ++i) {
+                    std::array<uint8_t, 32> h{};
+                    std::memcpy(h.data(), &digests[(k * t + i) * 32], 32);
+                    Chunk c{Sha256Hash(h), {}};
+                    const uint8_t* src;
+                    if (i >= d) {
+                        src = &parity[k][(i - d) * L];
+                    } else if ((i + 1) * L <= len) {
+                        src = pend[k].bytes + i * L;
+                    } else {
+                        edge.assign(L, 0);
+                        if (i * L < len) std::memcpy(edge.data(), pend[k].bytes + i * L, len - i * L);
+                        src = edge.data();
+                    }
+                    c.locations.push_back(dest.write_shard(c.hash, src, L));
+                    (i < d ? part.data : part.parity).push_back(std::move(c));
+                }
+                out[pend[k].file].parts.push_back(std::move(part));
+            }
+            pend.clear();
+            pend_bytes = 0;
+        };
+        for (size_t f = 0; f < files.size(); ++f) {
+            const uint8_t* bytes = files[f].first;
+            const size_t n = files[f].second;
+            const size_t full = n / part_cap;
+            size_t off = 0;
+            if (batch_ && full >= 2) {
+                flush();  // earlier files' parts reach dest before this file's
+                write_full_parts(encoder, bytes, full, dest, out[f]);
+                off = full * part_cap;
+            }
+            for (; off < n; off += part_cap) {
+                const size_t length = std::min(part_cap, n - off);
+                if (!pend.empty() && pend_bytes + length > kManyWindowBytes) flush();
+                pend.push_back({f, bytes + off, length});
+                pend_bytes += length;
+            }
+            out[f].length = n;
+        }
+        flush();
+        return out;
+    }
 
    public:
     // The page-locked windows of the calling thread's batched writes (see release_thread_buffers).

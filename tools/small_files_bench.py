@@ -1,0 +1,244 @@
+"""Small files through the write path's compute: per-part calls against one ragged batch.
+
+Host-staged workload (default): files from seed 1, sizes log-uniform in [1 KiB, 4 MiB], 4096 of
+them (about 2 GiB), cut into parts of d x 1 MiB as FileWriteBuilder does, for RS(3,2) and
+RS(10,4).  Three arms produce the same parts:
+
+  a  the per-part way: cec_part_encode per part from 10 and from 256 threads (the padded copy of
+     each part that call needs is made before the clock starts)
+  b  one cec_parts_encode call over all parts, straight from the files' bytes
+  c  the CPU oracle (the crate's path restated in C) on 16 threads
+
+Every arm is warmed up, then the arms alternate three times in one process; the device is
+synchronised before each clock reading.  Reported: GB/s of file bytes and parts/s per repeat.
+All arms' digests must agree (asserted).
+
+--device: 4096 x RS(10,4) x 64 KiB parts, device resident: cec_encode_hash_ragged with uniform
+lengths against cec_encode_hash_batch on the same bytes; both times and the ratio.
+
+    python tools/small_files_bench.py [--files 4096] [--repeats 3] [--shapes 3,2:10,4]
+    python tools/small_files_bench.py --device"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "chunky-bits_amd"))
+import torch  # noqa: E402
+import chunky_ec as ce  # noqa: E402
+import oracle  # noqa: E402
+
+CHUNK = 1 << 20
+U8P = ctypes.POINTER(ctypes.c_uint8)
+
+
+def make_files(n_files, seed=1):
+    """(pool, [(offset, size)]): file f is pool[offset : offset + size]."""
+    rng = np.random.default_rng(seed)
+    sizes = np.exp(rng.uniform(np.log(1 << 10), np.log(4 << 20), n_files)).astype(np.int64)
+    pool = rng.integers(0, 256, (64 << 20) + (4 << 20), dtype=np.uint8)
+    offs = rng.integers(0, 64 << 20, n_files)
+    return pool, [(int(o), int(s)) for o, s in zip(offs, sizes)]
+
+
+def cut_parts(files, d):
+    """Every file's parts, in file order: (offset into the pool, length)."""
+    cap = d * CHUNK
+    parts = []
+    for off, size in files:
+        for at in range(0, size, cap):
+            parts.append((off + at, min(cap, size - at)))
+    return parts
+
+
+class Workload:
+    def __init__(self, pool, files, d, p):
+        self.d, self.p, self.t = d, p, d + p
+        self.rs = ce.ReedSolomon(d, p)
+        self.pool = pool
+        self.parts = cut_parts(files, d)
+        self.n = len(self.parts)
+        self.file_bytes = sum(s for _, s in files)
+        self.L = [(ln + d - 1) // d for _, ln in self.parts]
+        base = pool.ctypes.data
+        self.ptrs = (U8P * self.n)(*[ctypes.cast(base + o, U8P) for o, _ in self.parts])
+        self.lens = (ctypes.c_size_t * self.n)(*[ln for _, ln in self.parts])
+        # outputs (reused by every arm and repeat)
+        self.par_off = np.concatenate([[0], np.cumsum([p * L for L in self.L])])
+        self.parity = np.zeros(int(self.par_off[-1]), np.uint8)
+        pb = self.parity.ctypes.data
+        self.par_ptrs = (U8P * self.n)(*[ctypes.cast(pb + int(o), U8P)
+                                         for o in self.par_off[:-1]])
+        self.chunksizes = (ctypes.c_size_t * self.n)()
+        # arm a / c input: each part zero padded to d * L (the copy cec_part_encode's callers make)
+        self.pad_off = np.concatenate([[0], np.cumsum([d * L for L in self.L])])
+        self.padded = np.zeros(int(self.pad_off[-1]), np.uint8)
+        for k, (o, ln) in enumerate(self.parts):
+            at = int(self.pad_off[k])
+            self.padded[at:at + ln] = pool[o:o + ln]
+
+    def digests(self):
+        return np.zeros((self.n, self.t, 32), np.uint8)
+
+    def _one(self, fn, dig, k):
+        cs = ctypes.c_size_t(0)
+        src = ctypes.cast(self.padded.ctypes.data + int(self.pad_off[k]), U8P)
+        par = ctypes.cast(self.parity.ctypes.data + int(self.par_off[k]), U8P)
+        out = ctypes.cast(dig.ctypes.data + k * self.t * 32, U8P)
+        st = fn(src, self.parts[k][1], par, out, ctypes.byref(cs))
+        assert st == 0 and cs.value == self.L[k], (st, k)
+
+    def arm_percall(self, threads, count=None):
+        dig = self.digests()
+        h = self.rs.handle
+
+        def fn(src, ln, par, out, cs):
+            return ce._lib.cec_part_encode(h, src, ln, par, out, cs)
+        with ThreadPoolExecutor(threads) as ex:
+            list(ex.map(lambda k: self._one(fn, dig, k), range(count or self.n)))
+        return dig
+
+    def arm_ragged(self, count=None):
+        dig = self.digests()
+        ce._check(ce._lib.cec_parts_encode(self.rs.handle, self.ptrs, self.lens, count or self.n,
+                                           self.par_ptrs, dig.ctypes.data_as(U8P),
+                                           self.chunksizes))
+        return dig
+
+    def arm_cpu(self, threads=16, count=None):
+        dig = self.digests()
+        lib = oracle.lib()
+        d, p = self.d, self.p
+
+        def fn(src, ln, par, out, cs):
+            return lib.or_part_encode(d, p, src, ln, par, out, cs)
+        with ThreadPoolExecutor(threads) as ex:
+            list(ex.map(lambda k: self._one(fn, dig, k), range(count or self.n)))
+        return dig
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def host_staged(args):
+    pool, files = make_files(args.files)
+    results = []
+    for shape in args.shapes.split(":"):
+        d, p = (int(x) for x in shape.split(","))
+        w = Workload(pool, files, d, p)
+        print(f"== RS({d},{p}) chunk 1 MiB: {len(files)} files, {w.file_bytes / 2**30:.2f} GiB, "
+              f"{w.n} parts, {len(set(w.L))} distinct chunk lengths", flush=True)
+        arms = [("a: part_encode x 10 threads", lambda c=None: w.arm_percall(10, c)),
+                ("a: part_encode x 256 threads", lambda c=None: w.arm_percall(256, c)),
+                ("b: one parts_encode call", lambda c=None: w.arm_ragged(c)),
+                ("c: CPU oracle x 16 threads", lambda c=None: w.arm_cpu(16, c))]
+        warm = min(w.n, 512)
+        for name, fn in arms:  # warm-up: b on the whole input (its staging is sized by it)
+            sec, _ = timed(lambda: fn(None if name.startswith("b") else warm))
+            print(f"   warm-up {name}: {sec:.3f} s", flush=True)
+        secs = {name: [] for name, _ in arms}
+        ref = None
+        for rep in range(args.repeats):
+            for name, fn in arms:
+                sec, dig = timed(fn)
+                secs[name].append(sec)
+                if ref is None:
+                    ref = dig
+                assert np.array_equal(dig, ref), f"digests of '{name}' differ"
+                print(f"   repeat {rep + 1} {name}: {sec:.3f} s  "
+                      f"{w.file_bytes / sec / 1e9:7.2f} GB/s  {w.n / sec:9.0f} parts/s", flush=True)
+        hl = [h.hex() for h in (ref[0, 0].tobytes(), ref[-1, -1].tobytes())]
+        print(f"   digests agree across all arms and repeats (first {hl[0][:16]}, "
+              f"last {hl[1][:16]})")
+        row = {"d": d, "p": p, "files": len(files), "parts": w.n, "file_bytes": w.file_bytes,
+               "seconds": secs,
+               "gbps": {k: [w.file_bytes / s / 1e9 for s in v] for k, v in secs.items()}}
+        a, b = secs["a: part_encode x 256 threads"], secs["b: one parts_encode call"]
+        spread = max(max(a) - min(a), max(b) - min(b))
+        row["b_vs_a256"] = {"a_best_s": min(a), "b_worst_s": max(b), "spread_s": spread,
+                            "b_wins_by_more_than_spread": max(b) + spread < min(a)}
+        print(f"   b vs a(256): a best {min(a):.3f} s, b worst {max(b):.3f} s, largest spread "
+              f"{spread:.3f} s -> b wins by more than the spread: "
+              f"{row['b_vs_a256']['b_wins_by_more_than_spread']}", flush=True)
+        results.append(row)
+        del w
+    print(json.dumps({"tool": "small_files_bench", "mode": "host", "results": results}))
+
+
+def device_mode(args):
+    d, p, n, L = 10, 4, 4096, 65536
+    t = d + p
+    dev = torch.device("cuda", 0)
+    rs = ce.ReedSolomon(d, p)
+    buf = torch.zeros((n, t, L), dtype=torch.uint8, device=dev)
+    batch = ce.PartBatch.from_tensor(buf, L)
+    ce.fill_synthetic(batch, d, 1)
+    dig_u = torch.zeros((n, t, 32), dtype=torch.uint8, device=dev)
+    dig_r = torch.zeros_like(dig_u)
+    offs, total = ce.ragged_layout(t, [L] * n)
+    assert total == buf.numel()
+    lens = [L] * n
+
+    def uniform():
+        ce.encode_hash_batch(rs, batch, dig_u.data_ptr())
+
+    def ragged():
+        ce.encode_hash_ragged(rs, buf.data_ptr(), offs, lens, dig_r.data_ptr())
+
+    def run(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    for fn in (uniform, ragged):
+        run(fn)
+    uniform()
+    torch.cuda.synchronize()
+    parity = buf[:, d:].clone()
+    ragged()
+    torch.cuda.synchronize()
+    assert torch.equal(parity, buf[:, d:]) and torch.equal(dig_u, dig_r), "results differ"
+    ms = {"encode_hash_batch": [], "encode_hash_ragged": []}
+    for rep in range(args.repeats):
+        ms["encode_hash_batch"].append(run(uniform))
+        ms["encode_hash_ragged"].append(run(ragged))
+    print(f"== device resident, {n} x RS({d},{p}) x {L} B ({n * d * L / 2**30:.2f} GiB of data)")
+    for k, v in ms.items():
+        print(f"   {k}: " + "  ".join(f"{x:.3f} ms" for x in v))
+    ratio = min(ms["encode_hash_ragged"]) / min(ms["encode_hash_batch"])
+    print(f"   ragged / uniform (best of {args.repeats}): {ratio:.3f}   (same parity, same digests)")
+    print(json.dumps({"tool": "small_files_bench", "mode": "device", "ms": ms, "ratio": ratio}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=4096)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--shapes", default="3,2:10,4")
+    ap.add_argument("--device", action="store_true")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a GPU"
+    if args.device:
+        device_mode(args)
+    else:
+        host_staged(args)
+
+
+if __name__ == "__main__":
+    main()
