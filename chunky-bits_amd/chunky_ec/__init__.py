@@ -129,6 +129,13 @@ _sig("cec_parts_encode", [_vp, ctypes.POINTER(_u8p), _szp, ctypes.c_size_t, ctyp
 _sig("cec_ragged_stride", [ctypes.c_size_t], ctypes.c_size_t)
 _sig("cec_ragged_layout", [ctypes.c_size_t, _szp, ctypes.c_size_t, _szp, _szp])
 _sig("cec_encode_hash_ragged", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _vp, _vp])
+_sig("cec_reconstruct_ragged", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, ctypes.c_int, _vp])
+_sig("cec_read_ragged", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp, _u8p,
+                         ctypes.POINTER(ctypes.c_int), _vp])
+_sig("cec_resilver_ragged", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp, _u8p,
+                             ctypes.POINTER(ctypes.c_int), _vp])
+_sig("cec_parts_read", [_vp, ctypes.POINTER(_u8p), _szp, ctypes.c_size_t, _u8p, _u8p, ctypes.c_int,
+                        _u8p, ctypes.POINTER(ctypes.c_int)])
 _sig("cec_coalesce_stats", [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
      None)
 _sig("cec_encode_batch", [_vp, ctypes.POINTER(PartBatchStruct), _vp])
@@ -661,6 +668,117 @@ def resilver_batch(codec: ReedSolomon, batch: PartBatch, present, expected_ptr: 
                    stream=None):
     """FilePart::resilver compute: verify all chunks, rebuild missing data and parity."""
     return _verify_rebuild(_lib.cec_resilver_batch, codec, batch, present, expected_ptr, stream)
+
+
+def _ragged_args(part_offsets, chunk_lens):
+    n = len(chunk_lens)
+    if len(part_offsets) != n:
+        raise ValueError("part_offsets and chunk_lens differ in length")
+    return ((ctypes.c_size_t * max(n, 1))(*part_offsets),
+            (ctypes.c_size_t * max(n, 1))(*chunk_lens), n)
+
+
+def reconstruct_ragged(codec: ReedSolomon, base_ptr: int, part_offsets: Sequence[int],
+                       chunk_lens: Sequence[int], present, data_only: bool, stream=None) -> None:
+    """:func:`reconstruct_batch` over parts of different chunk lengths
+    (``cec_reconstruct_ragged``): device memory at ``base_ptr`` in the layout of
+    :func:`ragged_layout`, ``present`` host flags ``n*(d+p)``."""
+    offs, lens, n = _ragged_args(part_offsets, chunk_lens)
+    pres = bytes(present)
+    assert len(pres) == n * codec.total_shard_count()
+    _check(_lib.cec_reconstruct_ragged(codec.handle, base_ptr, offs, lens, n,
+                                       ctypes.cast(ctypes.c_char_p(pres), _u8p),
+                                       1 if data_only else 0, _stream_ptr(stream)))
+
+
+def _verify_rebuild_ragged(fn, codec, base_ptr, part_offsets, chunk_lens, present, expected_ptr,
+                           stream):
+    offs, lens, n = _ragged_args(part_offsets, chunk_lens)
+    items = n * codec.total_shard_count()
+    pres = bytes(present)
+    assert len(pres) == items
+    verified = (ctypes.c_uint8 * max(items, 1))()
+    status = (ctypes.c_int * max(n, 1))()
+    _check(fn(codec.handle, base_ptr, offs, lens, n, ctypes.cast(ctypes.c_char_p(pres), _u8p),
+              expected_ptr, verified, status, _stream_ptr(stream)))
+    return bytes(verified)[:items], list(status)[:n]
+
+
+def read_ragged(codec: ReedSolomon, base_ptr: int, part_offsets: Sequence[int],
+                chunk_lens: Sequence[int], present, expected_ptr: int, stream=None):
+    """:func:`read_batch` over parts of different chunk lengths (``cec_read_ragged``).
+    Returns (verified flags, per-part status)."""
+    return _verify_rebuild_ragged(_lib.cec_read_ragged, codec, base_ptr, part_offsets,
+                                  chunk_lens, present, expected_ptr, stream)
+
+
+def resilver_ragged(codec: ReedSolomon, base_ptr: int, part_offsets: Sequence[int],
+                    chunk_lens: Sequence[int], present, expected_ptr: int, stream=None):
+    """:func:`resilver_batch` over parts of different chunk lengths (``cec_resilver_ragged``)."""
+    return _verify_rebuild_ragged(_lib.cec_resilver_ragged, codec, base_ptr, part_offsets,
+                                  chunk_lens, present, expected_ptr, stream)
+
+
+def parts_read(codec: ReedSolomon, parts: Sequence[Sequence], expected: Sequence,
+               data_only: bool = True):
+    """The read counterpart of :func:`parts_encode` (``cec_parts_read``): verify and rebuild
+    parts of unrelated chunk lengths in ONE engine call.  ``parts[k]`` lists the d+p chunks of
+    part k: bytes-like for a loaded chunk, a ``(bytes-like, PRESENT_VERIFIED)`` pair for one an
+    earlier pass verified, ``None`` for a missing one; every loaded chunk of a part has the
+    part's chunk length.  ``expected[k]`` is the part's d+p digests (32 bytes each).  Returns
+    ``(chunks, verified, status)``: ``chunks[k][i]`` is the loaded chunk as given when it
+    verified, the rebuilt chunk as ``bytes``, or ``None`` where there is neither (missing parity
+    under ``data_only``, what did not verify in a part whose status is
+    ``TOO_FEW_SHARDS_PRESENT``); ``verified`` the flags ``n*(d+p)``; ``status`` per part."""
+    d, t = codec.data_shard_count(), codec.total_shard_count()
+    n = len(parts)
+    if n == 0:
+        return [], b"", []
+    lens, flags, ptrs, slots = [], bytearray(n * t), [], {}
+    for k, chunks in enumerate(parts):
+        if len(chunks) != t:
+            raise ValueError(f"part {k}: {len(chunks)} chunks, the codec has {t}")
+        loaded = [c[0] if isinstance(c, tuple) else c for c in chunks]
+        sizes = {_nbytes(c) for c in loaded if c is not None}
+        if len(sizes) != 1:
+            raise ValueError(f"part {k}: loaded chunks of sizes {sorted(sizes)}")
+        L = sizes.pop()
+        lens.append(L)
+        for i, c in enumerate(chunks):
+            if c is None and i >= d and data_only:
+                ptrs.append(_u8p())  # never filled
+                continue
+            # the engine's own copy: a loaded chunk that fails verification is rebuilt in place
+            slot = (ctypes.c_uint8 * max(L, 1))()
+            if c is not None:
+                flags[k * t + i] = c[1] if isinstance(c, tuple) else 1
+                ctypes.memmove(slot, bytes(loaded[i]), L)
+            slots[(k, i)] = slot
+            ptrs.append(ctypes.cast(slot, _u8p))
+    exp = b"".join(bytes(h) for part in expected for h in part)
+    if len(exp) != n * t * 32:
+        raise ValueError("expected: d+p digests of 32 bytes per part")
+    verified = (ctypes.c_uint8 * (n * t))()
+    status = (ctypes.c_int * n)()
+    pres = bytes(flags)
+    _check(_lib.cec_parts_read(codec.handle, (_u8p * (n * t))(*ptrs),
+                               (ctypes.c_size_t * n)(*lens), n,
+                               ctypes.cast(ctypes.c_char_p(pres), _u8p),
+                               ctypes.cast(ctypes.c_char_p(exp), _u8p), 1 if data_only else 0,
+                               verified, status))
+    out = []
+    for k, chunks in enumerate(parts):
+        row = []
+        for i, c in enumerate(chunks):
+            fillable = i < d or not data_only
+            if verified[k * t + i]:
+                row.append(c[0] if isinstance(c, tuple) else c)
+            elif status[k] == OK and fillable:
+                row.append(bytes(slots[(k, i)])[:lens[k]])
+            else:
+                row.append(None)
+        out.append(row)
+    return out, bytes(verified), list(status)
 
 
 def fill_synthetic(batch: PartBatch, n_chunks: int, seed: int, stream=None) -> None:

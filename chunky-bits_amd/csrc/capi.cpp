@@ -1760,46 +1760,58 @@ int cec_encode_hash_batch(const cec_codec* cc, const cec_part_batch* b, uint8_t*
     return CEC_OK;
 }
 
-// cec_reconstruct_batch with each decode block reserving lds_reserve bytes of LDS (see
-// ApplyParams::lds_reserve).
-static int reconstruct_batch(const cec_codec* cc, const cec_part_batch* b, const uint8_t* present,
-                             int data_only, void* stream, uint32_t lds_reserve) {
-    if (!cc || !present) return CEC_ERR_INVALID_ARGUMENT;
-    CEC_TRY(batch_ok(b));
-    if (b->n_parts == 0) return CEC_OK;
-    if (b->chunk_len == 0) return CEC_EMPTY_SHARD;
-    if (b->n_parts > 0xFFFFFFFFull) return CEC_ERR_INVALID_ARGUMENT;
-    cec_codec* c = const_cast<cec_codec*>(cc);
-    const size_t d = c->d, t = c->d + c->p;
-    // Validate every part before launching anything.
-    for (size_t k = 0; k < b->n_parts; ++k) {
+}  // extern "C"
+
+namespace {
+
+// The host half of a batched reconstruct, shared by the uniform and the ragged layout: the parts
+// that need a rebuild grouped by erasure pattern, one decode record per pattern, the patterns
+// bucketed by output-row count, and per bucket the launch lists.
+// words = [records...][launch lists: part_ids..., part_pat...].  Patterns of up to max_var_rows()
+// rows (every RS(10,4) erasure set) share ONE launch that dispatches on each part's row count;
+// wider patterns get a row-group launch per row count.
+struct DecodePlan {
+    struct Launch {
+        uint32_t n_out;  // 0: per-part row counts (the shared launch)
+        size_t ids;      // word offset of part_ids; part_pat follows at ids + count
+        size_t count;
+    };
+    std::vector<uint32_t> words;
+    std::vector<Launch> launches;  // empty: nothing to rebuild
+    uint32_t var_rows = 0;         // the shared launch's widest pattern: its kernel's row class
+};
+
+// CEC_TOO_FEW_SHARDS_PRESENT when a part has some but fewer than d chunks present.
+int check_present(size_t d, size_t t, const uint8_t* present, size_t n_parts) {
+    for (size_t k = 0; k < n_parts; ++k) {
         size_t n_present = 0;
         for (size_t i = 0; i < t; ++i) n_present += present[k * t + i] ? 1 : 0;
         if (n_present != t && n_present < d) return CEC_TOO_FEW_SHARDS_PRESENT;
     }
+    return CEC_OK;
+}
+
+void plan_decode(cec_codec* c, const uint8_t* present, size_t n_parts, bool data_only,
+                 DecodePlan* plan) {
+    const size_t t = c->d + c->p;
     // Group parts by pattern; bucket patterns by output-row count.
     std::map<PatternKey, std::pair<uint32_t, std::vector<uint32_t>>> groups;  // key -> (n_out, parts)
-    for (size_t k = 0; k < b->n_parts; ++k) {
+    for (size_t k = 0; k < n_parts; ++k) {
         const uint8_t* pr = present + k * t;
         size_t n_present = 0;
         for (size_t i = 0; i < t; ++i) n_present += pr[i] ? 1 : 0;
         if (n_present == t) continue;
-        PatternKey key = make_key(pr, t, data_only != 0);
+        PatternKey key = make_key(pr, t, data_only);
         auto& g = groups[key];
         g.second.push_back(uint32_t(k));
     }
-    if (groups.empty()) return CEC_OK;
-    // words = [records...][launch lists: part_ids..., part_pat...].  Patterns of up to
-    // max_var_rows() rows (every RS(10,4) erasure set) share ONE launch that dispatches on each
-    // part's row count; wider patterns get a row-group launch per row count.
-    std::vector<uint32_t> words;
+    std::vector<uint32_t>& words = plan->words;
     std::map<uint32_t, std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> buckets;
-    uint32_t var_rows = 0;  // the shared launch's widest pattern: its kernel's row class
     for (auto& kv : groups) {
         auto rec = c->decode_record(kv.first);
         const uint32_t n_out = (*rec)[0];
         if (n_out == 0) continue;  // data_only: only parity missing, nothing to do
-        if (n_out <= max_var_rows()) var_rows = std::max(var_rows, n_out);
+        if (n_out <= max_var_rows()) plan->var_rows = std::max(plan->var_rows, n_out);
         const uint32_t off = uint32_t(words.size());
         words.insert(words.end(), rec->begin(), rec->end());
         auto& bk = buckets[n_out <= max_var_rows() ? 0u : n_out];  // 0 = the shared launch
@@ -1808,53 +1820,133 @@ static int reconstruct_batch(const cec_codec* cc, const cec_part_batch* b, const
             bk.second.push_back(off);
         }
     }
-    if (buckets.empty()) return CEC_OK;
-    struct Launch {
-        uint32_t n_out;  // 0: per-part row counts (launch_rs_apply_var)
-        size_t ids;      // word offset of part_ids
-        size_t count;
-    };
-    std::vector<Launch> launches;
     for (auto& kv : buckets) {
-        launches.push_back({kv.first, words.size(), kv.second.first.size()});
+        plan->launches.push_back({kv.first, words.size(), kv.second.first.size()});
         words.insert(words.end(), kv.second.first.begin(), kv.second.first.end());
         words.insert(words.end(), kv.second.second.begin(), kv.second.second.end());
     }
+}
+
+// The shared launch's row class must cover every record it lists (the kernels skip a wider
+// pattern without writing its chunks: kernels.hpp launch_rs_apply_var).
+int check_row_class(const DecodePlan& plan, const DecodePlan::Launch& l, uint32_t n_rows,
+                    const char* who) {
+    const uint32_t* pat_off = plan.words.data() + l.ids + l.count;
+    for (size_t q = 0; q < l.count; ++q)
+        if (plan.words[pat_off[q]] == 0 || plan.words[pat_off[q]] > n_rows) {
+            g_last_error = std::string(who) + ": a listed pattern is wider than its launch";
+            return CEC_ERR_INVALID_ARGUMENT;
+        }
+    return CEC_OK;
+}
+
+// cec_reconstruct_batch with each decode block reserving lds_reserve bytes of LDS (see
+// ApplyParams::lds_reserve).
+int reconstruct_batch(const cec_codec* cc, const cec_part_batch* b, const uint8_t* present,
+                      int data_only, void* stream, uint32_t lds_reserve) {
+    if (!cc || !present) return CEC_ERR_INVALID_ARGUMENT;
+    CEC_TRY(batch_ok(b));
+    if (b->n_parts == 0) return CEC_OK;
+    if (b->chunk_len == 0) return CEC_EMPTY_SHARD;
+    if (b->n_parts > 0xFFFFFFFFull) return CEC_ERR_INVALID_ARGUMENT;
+    cec_codec* c = const_cast<cec_codec*>(cc);
+    const size_t d = c->d, t = c->d + c->p;
+    // Validate every part before launching anything.
+    CEC_TRY(check_present(d, t, present, b->n_parts));
+    DecodePlan plan;
+    plan_decode(c, present, b->n_parts, data_only != 0, &plan);
+    if (plan.launches.empty()) return CEC_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint32_t* dwords = nullptr;
     Scratch scratch;  // released on s behind the launches below
-    CEC_TRY(upload_words(words, s, scratch, &dwords));
+    CEC_TRY(upload_words(plan.words, s, scratch, &dwords));
     const bool vec = aligned16(b->base, b->part_stride, b->chunk_stride);
     int status = CEC_OK;
-    for (size_t i = 0; i < launches.size() && status == CEC_OK; ++i) {
+    for (size_t i = 0; i < plan.launches.size() && status == CEC_OK; ++i) {
+        const DecodePlan::Launch& l = plan.launches[i];
         ApplyParams a{};
         a.base = b->base;
         a.part_stride = b->part_stride;
         a.chunk_stride = b->chunk_stride;
         a.len = b->chunk_len;
         a.pat = dwords;
-        a.part_ids = dwords + launches[i].ids;
-        a.part_pat = dwords + launches[i].ids + launches[i].count;
-        a.n_parts = uint32_t(launches[i].count);
+        a.part_ids = dwords + l.ids;
+        a.part_pat = dwords + l.ids + l.count;
+        a.n_parts = uint32_t(l.count);
         a.d = uint32_t(d);
-        a.n_rows = launches[i].n_out ? launches[i].n_out : var_rows;
-        if (!launches[i].n_out) {
-            // the shared launch's row class must cover every record it lists (the kernel skips
-            // a wider pattern without writing its chunks: kernels.hpp launch_rs_apply_var)
-            const uint32_t* pat_off = words.data() + launches[i].ids + launches[i].count;
-            for (size_t q = 0; q < launches[i].count; ++q)
-                if (words[pat_off[q]] == 0 || words[pat_off[q]] > a.n_rows) {
-                    g_last_error = "reconstruct_batch: a listed pattern is wider than its launch";
-                    return CEC_ERR_INVALID_ARGUMENT;
-                }
-        }
+        a.n_rows = l.n_out ? l.n_out : plan.var_rows;
+        if (!l.n_out) CEC_TRY(check_row_class(plan, l, a.n_rows, "reconstruct_batch"));
         a.lds_reserve = lds_reserve;
-        hipError_t e = launches[i].n_out ? launch_rs_apply(a, vec, s)
-                                         : launch_rs_apply_var(a, vec, s);
+        hipError_t e = l.n_out ? launch_rs_apply(a, vec, s) : launch_rs_apply_var(a, vec, s);
         if (e != hipSuccess) status = hip_fail(e, "launch_rs_apply");
     }
     return status;
 }
+
+// The launches of cec_reconstruct_ragged for a checked layout (ragged_check) and checked flags
+// (check_present), on `s`.  Only the parts the plan lists reach the device: per launch a compact
+// {off, L} array and the prefix array over those parts' work units, behind the plan's words in
+// one scratch buffer whose page-locked mirror holds the copy of the host arrays.
+int reconstruct_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* lens,
+                       size_t n, const uint8_t* present, bool data_only, hipStream_t s) {
+    DecodePlan plan;
+    plan_decode(c, present, n, data_only, &plan);
+    if (plan.launches.empty()) return CEC_OK;
+    size_t listed = 0;
+    for (const auto& l : plan.launches) {
+        if (!l.n_out) CEC_TRY(check_row_class(plan, l, plan.var_rows, "reconstruct_ragged"));
+        listed += l.count;
+    }
+    // [plan words][per launch: units u32 x (count + 1), parts u32 x 4 count]
+    const size_t n_words = plan.words.size() + listed * 5 + plan.launches.size();
+    Scratch sc;  // released on s behind the launches below
+    CEC_TRY(sc.acquire(n_words * sizeof(uint32_t), s));
+    uint32_t* h = reinterpret_cast<uint32_t*>(sc.host());
+    uint32_t* dwords = reinterpret_cast<uint32_t*>(sc.dev());
+    std::memcpy(h, plan.words.data(), plan.words.size() * sizeof(uint32_t));
+    const uint64_t unit = ragged_unit_bytes();
+    std::vector<RaggedParams> params;
+    size_t at = plan.words.size();
+    for (const auto& l : plan.launches) {
+        const uint32_t* ids = plan.words.data() + l.ids;
+        uint32_t* h_units = h + at;
+        uint32_t* h_parts = h + at + l.count + 1;
+        uint64_t acc = 0;  // at most the whole batch's units, which ragged_check bounded
+        for (size_t q = 0; q < l.count; ++q) {
+            const uint64_t off = offs[ids[q]], L = lens[ids[q]];
+            h_units[q] = uint32_t(acc);
+            acc += (L - 1) / unit + 1;
+            h_parts[4 * q + 0] = uint32_t(off);
+            h_parts[4 * q + 1] = uint32_t(off >> 32);
+            h_parts[4 * q + 2] = uint32_t(L);
+            h_parts[4 * q + 3] = uint32_t(L >> 32);
+        }
+        h_units[l.count] = uint32_t(acc);
+        RaggedParams a{};
+        a.base = base;
+        a.pat = dwords;
+        a.units = dwords + at;
+        a.parts = dwords + at + l.count + 1;
+        a.part_pat = dwords + l.ids + l.count;
+        a.n_parts = uint32_t(l.count);
+        a.total_units = uint32_t(acc);
+        a.d = uint32_t(c->d);
+        a.n_rows = l.n_out ? l.n_out : plan.var_rows;
+        params.push_back(a);
+        at += l.count * 5 + 1;
+    }
+    HIP_TRY(hipMemcpyAsync(dwords, h, n_words * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    for (size_t i = 0; i < params.size(); ++i) {
+        const hipError_t e = plan.launches[i].n_out ? launch_rs_encode_ragged(params[i], s)
+                                                    : launch_rs_reconstruct_ragged(params[i], s);
+        if (e != hipSuccess) return hip_fail(e, "launch_rs_reconstruct_ragged");
+    }
+    return CEC_OK;
+}
+
+}  // namespace
+
+extern "C" {
 
 int cec_reconstruct_batch(const cec_codec* c, const cec_part_batch* b, const uint8_t* present,
                           int data_only, void* stream) {
@@ -2112,6 +2204,285 @@ int cec_resilver_batch(const cec_codec* c, const cec_part_batch* b, const uint8_
                        void* stream) {
     return verify_then_reconstruct(c, b, present, expected, verified, part_status, false,
                                    static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Ragged read (cec_reconstruct_ragged, cec_read_ragged, cec_resilver_ragged, cec_parts_read)
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// Shared body of cec_read_ragged / cec_resilver_ragged for a checked layout: on `s` the SHA-256
+// list launch in verify mode over the chunks that need hashing (longest first, so the 64 chains of
+// a wave have similar lengths; ok and expected indexed by k*(d+p)+i), the readback of the flags
+// (the one wait), then the rebuild of every decodable part from its first d verified chunks.
+// No speculative decode beside the verification: the chains of a ragged batch are short and
+// nobody has measured whether it pays (not built).
+int read_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* lens, size_t n,
+                const uint8_t* present, const uint8_t* expected, uint8_t* verified,
+                int* part_status, bool data_only, hipStream_t s) {
+    const size_t d = c->d, t = c->d + c->p, items = n * t;
+    std::vector<uint32_t> order;
+    for (size_t i = 0; i < items; ++i)
+        if (needs_hash(present[i])) order.push_back(uint32_t(i));
+    std::stable_sort(order.begin(), order.end(),
+                     [&](uint32_t x, uint32_t y) { return lens[x / t] > lens[y / t]; });
+    // [ptrs u64 x items][lens u64 x items][order u32 x hashed][ok u8 x items]
+    const size_t o_len = items * 8, o_ord = o_len + items * 8, o_ok = o_ord + order.size() * 4,
+                 bytes = o_ok + items;
+    Scratch sc;  // released on s behind the readback
+    CEC_TRY(sc.acquire(bytes, s));
+    uint8_t* ok = sc.dev() + o_ok;
+    HIP_TRY(hipMemsetAsync(ok, 0, items, s));
+    if (!order.empty()) {
+        uint64_t* h_ptr = reinterpret_cast<uint64_t*>(sc.host());
+        uint64_t* h_len = reinterpret_cast<uint64_t*>(sc.host() + o_len);
+        for (uint32_t it : order) {  // unlisted items are never looked at
+            const size_t k = it / t, i = it % t;
+            const size_t cs = (lens[k] + kRaggedAlign - 1) / kRaggedAlign * kRaggedAlign;
+            h_ptr[it] = reinterpret_cast<uint64_t>(base + offs[k] + i * cs);
+            h_len[it] = lens[k];
+        }
+        std::memcpy(sc.host() + o_ord, order.data(), order.size() * 4);
+        HIP_TRY(hipMemcpyAsync(sc.dev(), sc.host(), o_ok, hipMemcpyHostToDevice, s));
+        ShaParams h{};
+        h.ptrs = reinterpret_cast<const uint64_t*>(sc.dev());
+        h.lens = reinterpret_cast<const uint64_t*>(sc.dev() + o_len);
+        h.n_parts = uint32_t(items);
+        h.n_chunks = 1;
+        h.expected = expected;
+        h.ok = ok;
+        h.items = reinterpret_cast<const uint32_t*>(sc.dev() + o_ord);
+        h.n_items = uint32_t(order.size());
+        const hipError_t e = launch_sha256(h, true, s);
+        if (e != hipSuccess) return hip_fail(e, "launch_sha256 (ragged verify)");
+    }
+    // the flags come back through the mirror, behind the words that went up
+    HIP_TRY(hipMemcpyAsync(sc.host() + o_ok, ok, items, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::memcpy(verified, sc.host() + o_ok, items);
+    for (size_t i = 0; i < items; ++i)  // verified by an earlier pass: trusted, not hashed again
+        if (present[i] == CEC_PRESENT_VERIFIED) verified[i] = 1;
+    // Parts with fewer than d verified chunks cannot be decoded: all ones, so the plan skips them.
+    std::vector<uint8_t> pres(items, uint8_t(1));
+    for (size_t k = 0; k < n; ++k) {
+        size_t good = 0;
+        for (size_t i = 0; i < t; ++i) good += verified[k * t + i] ? 1 : 0;
+        part_status[k] = good >= d ? CEC_OK : CEC_TOO_FEW_SHARDS_PRESENT;
+        if (good >= d) std::copy(verified + k * t, verified + (k + 1) * t, pres.begin() + k * t);
+    }
+    return reconstruct_ragged(c, base, offs, lens, n, pres.data(), data_only, s);
+}
+
+// Every check of cec_read_ragged / cec_resilver_ragged, then the work.
+int read_ragged_checked(const cec_codec* cc, uint8_t* base, const size_t* offs, const size_t* lens,
+                        size_t n, const uint8_t* present, const uint8_t* expected,
+                        uint8_t* verified, int* part_status, bool data_only, void* stream) {
+    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
+    if (n == 0) return CEC_OK;
+    if (!base || !offs || !lens || !present || !expected || !verified || !part_status)
+        return CEC_ERR_INVALID_ARGUMENT;
+    uint64_t units = 0;
+    CEC_TRY(ragged_check(cc, base, offs, lens, n, &units));
+    int dev = 0;
+    CEC_TRY(current_device(&dev));
+    return read_ragged(const_cast<cec_codec*>(cc), base, offs, lens, n, present, expected,
+                       verified, part_status, data_only, static_cast<hipStream_t>(stream));
+}
+
+// Copies of the byte ranges [from[q], to[q]) (ascending, disjoint) between the staging and the
+// device arena, which share their offsets.  Neighbouring ranges share one copy, with what lies
+// between them travelling along, until the gap is worth a copy call of its own (parts_round's
+// 256 KiB rule).
+int copy_spans(uint8_t* stage, uint8_t* dbase, const std::vector<std::pair<size_t, size_t>>& spans,
+               bool to_device, hipStream_t s) {
+    constexpr size_t kGap = size_t(256) << 10;
+    for (size_t q = 0; q < spans.size();) {
+        const size_t from = spans[q].first;
+        size_t to = spans[q].second;
+        for (++q; q < spans.size() && spans[q].first - to < kGap; ++q) to = spans[q].second;
+        if (to_device)
+            HIP_TRY(hipMemcpyAsync(dbase + from, stage + from, to - from, hipMemcpyHostToDevice, s));
+        else
+            HIP_TRY(hipMemcpyAsync(stage + from, dbase + from, to - from, hipMemcpyDeviceToHost, s));
+    }
+    return CEC_OK;
+}
+
+// Whether the call fills slot i of a part when it is not among the verified chunks.
+inline bool fills_slot(size_t i, size_t d, bool data_only) { return i < d || !data_only; }
+
+// One round of cec_parts_read: parts [0, n) of these arrays.  The loaded chunks are packed into
+// the arena in the cec_ragged_layout layout and moved up, verified and rebuilt as in
+// cec_read_ragged, and only the rebuilt chunks come back, into the caller's slots.
+int parts_read_round(cec_codec* c, Arena& a, uint8_t* const* shards, const size_t* chunk_lens,
+                     size_t n, const uint8_t* present, const uint8_t* expected, bool data_only,
+                     uint8_t* verified, int* part_status) {
+    const size_t d = c->d, t = c->d + c->p, items = n * t;
+    std::vector<size_t> offs(n);
+    size_t total = 0;
+    CEC_TRY(ragged_layout(t, chunk_lens, n, offs.data(), &total));
+    const size_t cap = coalesce_max_bytes();
+    CEC_TRY(a.in.reserve(total, cap / d * t + t * kRaggedAlign));
+    CEC_TRY(a.out.reserve(items * 32, cap / 8));
+    const size_t dig_bytes = round_up(items * 32, kChunkAlign);
+    CEC_TRY(ctx_reserve(a.dev, dig_bytes + total));
+    uint8_t* dexp = a.dev.dbuf;
+    uint8_t* dbase = a.dev.dbuf + dig_bytes;
+    uint8_t* stage = a.in.ptr;
+    hipStream_t s = a.dev.stream;
+    std::vector<std::pair<size_t, size_t>> spans;
+    size_t in_bytes = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const size_t L = chunk_lens[k], cs = round_up(L, kRaggedAlign);
+        for (size_t i = 0; i < t; ++i)
+            if (present[k * t + i]) {
+                spans.emplace_back(offs[k] + i * cs, offs[k] + i * cs + L);
+                in_bytes += L;
+            }
+    }
+    for_parts(n, in_bytes, [&](size_t k) {
+        const size_t L = chunk_lens[k], cs = round_up(L, kRaggedAlign);
+        for (size_t i = 0; i < t; ++i)
+            if (present[k * t + i]) std::memcpy(stage + offs[k] + i * cs, shards[k * t + i], L);
+    });
+    std::memcpy(a.out.ptr, expected, items * 32);
+    HIP_TRY(hipMemcpyAsync(dexp, a.out.ptr, items * 32, hipMemcpyHostToDevice, s));
+    CEC_TRY(copy_spans(stage, dbase, spans, true, s));
+    CEC_TRY(read_ragged(c, dbase, offs.data(), chunk_lens, n, present, dexp, verified,
+                        part_status, data_only, s));
+    // what the rebuild wrote: in a decodable part, every slot of the mode that did not verify
+    spans.clear();
+    size_t out_bytes = 0;
+    for (size_t k = 0; k < n; ++k) {
+        if (part_status[k] != CEC_OK) continue;
+        const size_t L = chunk_lens[k], cs = round_up(L, kRaggedAlign);
+        for (size_t i = 0; i < t; ++i)
+            if (!verified[k * t + i] && fills_slot(i, d, data_only)) {
+                spans.emplace_back(offs[k] + i * cs, offs[k] + i * cs + L);
+                out_bytes += L;
+            }
+    }
+    CEC_TRY(copy_spans(stage, dbase, spans, false, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for_parts(n, out_bytes, [&](size_t k) {
+        if (part_status[k] != CEC_OK) return;
+        const size_t L = chunk_lens[k], cs = round_up(L, kRaggedAlign);
+        for (size_t i = 0; i < t; ++i)
+            if (!verified[k * t + i] && fills_slot(i, d, data_only))
+                std::memcpy(shards[k * t + i], stage + offs[k] + i * cs, L);
+    });
+    return CEC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cec_reconstruct_ragged(const cec_codec* cc, uint8_t* base, const size_t* part_offsets,
+                           const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                           int data_only, void* stream) {
+    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
+    if (n_parts == 0) return CEC_OK;
+    if (!base || !part_offsets || !chunk_lens || !present) return CEC_ERR_INVALID_ARGUMENT;
+    uint64_t units = 0;
+    CEC_TRY(ragged_check(cc, base, part_offsets, chunk_lens, n_parts, &units));
+    CEC_TRY(check_present(cc->d, cc->d + cc->p, present, n_parts));
+    int dev = 0;
+    CEC_TRY(current_device(&dev));
+    return reconstruct_ragged(const_cast<cec_codec*>(cc), base, part_offsets, chunk_lens, n_parts,
+                              present, data_only != 0, static_cast<hipStream_t>(stream));
+}
+
+int cec_read_ragged(const cec_codec* c, uint8_t* base, const size_t* part_offsets,
+                    const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                    const uint8_t* expected, uint8_t* verified, int* part_status, void* stream) {
+    return read_ragged_checked(c, base, part_offsets, chunk_lens, n_parts, present, expected,
+                               verified, part_status, true, stream);
+}
+
+int cec_resilver_ragged(const cec_codec* c, uint8_t* base, const size_t* part_offsets,
+                        const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                        const uint8_t* expected, uint8_t* verified, int* part_status,
+                        void* stream) {
+    return read_ragged_checked(c, base, part_offsets, chunk_lens, n_parts, present, expected,
+                               verified, part_status, false, stream);
+}
+
+int cec_parts_read(const cec_codec* cc, uint8_t* const* shards, const size_t* chunk_lens,
+                   size_t n_parts, const uint8_t* present, const uint8_t* expected, int data_only,
+                   uint8_t* verified, int* part_status) {
+    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
+    if (n_parts == 0) return CEC_OK;
+    if (!shards || !chunk_lens || !present || !expected || !verified || !part_status)
+        return CEC_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < n_parts; ++k)
+        if (chunk_lens[k] == 0) return CEC_EMPTY_SHARD;
+    cec_codec* c = const_cast<cec_codec*>(cc);
+    const size_t d = c->d, t = c->d + c->p;
+    size_t items = 0;
+    if (__builtin_mul_overflow(n_parts, t, &items) || items > 0xFFFFFFFFull)
+        return CEC_ERR_INVALID_ARGUMENT;
+    // A loaded chunk needs its bytes; a part that can be decoded (d or more chunks loaded) needs
+    // memory behind every slot the mode fills.
+    for (size_t k = 0; k < n_parts; ++k) {
+        size_t loaded = 0;
+        for (size_t i = 0; i < t; ++i) loaded += present[k * t + i] ? 1 : 0;
+        for (size_t i = 0; i < t; ++i) {
+            const bool need = present[k * t + i] || (loaded >= d && fills_slot(i, d, data_only != 0));
+            if (need && !shards[k * t + i]) {
+                g_last_error = "cec_parts_read: a chunk slot that is read or filled is NULL";
+                return CEC_ERR_INVALID_ARGUMENT;
+            }
+        }
+    }
+    // Rounds as cec_parts_encode cuts them: at most CEC_COALESCE_MAX_MIB of (padded) data-chunk
+    // bytes, a larger part alone; every round is checked before the first one runs.
+    std::vector<size_t> round_end;
+    const size_t cap = coalesce_max_bytes();
+    size_t bytes = 0, first = 0;
+    for (size_t k = 0; k < n_parts; ++k) {
+        size_t cs = 0, b = 0;
+        if (!ragged_stride(chunk_lens[k], &cs) || __builtin_mul_overflow(d, cs, &b))
+            return CEC_ERR_INVALID_ARGUMENT;
+        if (k > first && (b > cap || bytes > cap - b)) {
+            round_end.push_back(k);
+            first = k;
+            bytes = 0;
+        }
+        bytes += std::min(b, cap);
+    }
+    round_end.push_back(n_parts);
+    {
+        std::vector<size_t> offs(n_parts);
+        size_t k0 = 0;
+        for (size_t k1 : round_end) {
+            size_t total = 0;
+            uint64_t units = 0;
+            CEC_TRY(ragged_layout(t, chunk_lens + k0, k1 - k0, offs.data(), &total));
+            CEC_TRY(ragged_check(c, nullptr, offs.data(), chunk_lens + k0, k1 - k0, &units));
+            k0 = k1;
+        }
+    }
+    int dev = 0;
+    CEC_TRY(current_device(&dev));
+    Arena* arena = ragged_arenas().take(dev);
+    int st = CEC_OK;
+    size_t k0 = 0;
+    for (size_t k1 : round_end) {
+        st = parts_read_round(c, *arena, shards + k0 * t, chunk_lens + k0, k1 - k0,
+                              present + k0 * t, expected + k0 * t * 32, data_only != 0,
+                              verified + k0 * t, part_status + k0);
+        if (st != CEC_OK) break;
+        k0 = k1;
+    }
+    if (st != CEC_OK && arena->dev.stream) {  // nothing of a failed round stays in flight
+        (void)hipStreamSynchronize(arena->dev.stream);
+        (void)hipGetLastError();
+    }
+    ragged_arenas().give(dev, arena);
+    return st;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -105,17 +105,29 @@ uint32_t max_var_rows();
 // array over the parts' unit counts (units[0] = 0, units[n_parts] = total_units) and `parts`
 // holds {off lo, off hi, L lo, L hi} per part (device memory, read as wave-uniform words).
 // Exactly L_k bytes of each parity chunk are written.
+// Reconstruct: the listed parts are a compact selection of the batch (those that need a rebuild),
+// `parts` / `units` describe the listed parts only, and listed part lp uses the pattern record at
+// pat + part_pat[lp] (word offsets into one uploaded block of records).
 struct RaggedParams {
     uint8_t* base;
-    const uint32_t* pat;    // the codec's encode record
+    const uint32_t* pat;    // the codec's encode record, or the block of decode records
     const uint32_t* units;  // [n_parts + 1]
     const uint32_t* parts;  // [n_parts][4]
+    const uint32_t* part_pat;  // [n_parts] or null: every part uses the record at pat
     uint32_t n_parts;
     uint32_t total_units;
     uint32_t d;
     uint32_t n_rows;
 };
+// Every listed part through all a.n_rows rows of its record (part_pat: records that share that
+// row count), in row groups of up to max_var_rows(): the encode, and reconstruct patterns wider
+// than max_var_rows().
 hipError_t launch_rs_encode_ragged(const RaggedParams& a, hipStream_t s);
+// Reconstruct of listed parts whose records carry their own row count (1..max_var_rows()), one
+// launch.  a.part_pat is required; a.n_rows selects the row class (2, 4 or 8) and MUST be at
+// least the widest listed record's row count, or 0 (the 8-row class): a wider record's part is
+// skipped in the kernel.  The caller (capi.cpp reconstruct_ragged) checks the host records first.
+hipError_t launch_rs_reconstruct_ragged(const RaggedParams& a, hipStream_t s);
 uint64_t ragged_unit_bytes();
 uint64_t ragged_max_units();  // most units one launch can address (grid and index limits)
 bool fused_supported(uint32_t d, uint32_t p);

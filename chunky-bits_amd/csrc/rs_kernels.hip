@@ -9,6 +9,8 @@
 //                       chunks: one launch, each block dispatched on its pattern's row count.
 //  rs_apply_ragged_kernel  encode_sep for parts of different chunk lengths, one launch: one
 //                       wave per 4 KiB of a part's columns, found through a prefix array.
+//  rs_reconstruct_ragged_kernel  reconstruct for such parts: a pattern record per listed part,
+//                       mixed erasure counts in one launch.
 //  fill_kernel          counter-based synthetic bytes for benchmarks/tests.
 //
 // GF multiply: no GF instruction exists, so a product c*x of four packed bytes is three
@@ -369,32 +371,30 @@ constexpr uint64_t kRaggedUnit = 4096;                  // bytes of one chunk's 
 constexpr uint64_t kRaggedStep = 64u * 16u;             // bytes per wave per column step
 constexpr uint32_t kRaggedWaves = kApplyThreads / 64;   // units per workgroup
 
-// grid.x = ceil(total_units / kRaggedWaves), grid.y = row groups of exactly RG rows from row_base.
-template <int RG>
-__global__ __launch_bounds__(kApplyThreads) void rs_apply_ragged_kernel(RaggedParams a,
-                                                                        uint32_t row_base) {
-    const uint32_t u = __builtin_amdgcn_readfirstlane(blockIdx.x * kRaggedWaves +
-                                                      (threadIdx.x >> 6));
-    if (u >= a.total_units) return;  // wave-uniform
-    cu32* pre = as_const(a.units);
-    uint32_t lo = 0, hi = a.n_parts;  // pre[lo] <= u < pre[hi]
+// The part that owns work unit u: pre[lo] <= u < pre[lo + 1] (wave-uniform scalar loads).
+__device__ __forceinline__ uint32_t ragged_find(cu32* pre, uint32_t n_parts, uint32_t u) {
+    uint32_t lo = 0, hi = n_parts;  // pre[lo] <= u < pre[hi]
     while (hi - lo > 1) {
         const uint32_t mid = lo + (hi - lo) / 2;
         if (pre[mid] <= u) lo = mid;
         else hi = mid;
     }
-    cu32* pm = as_const(a.parts) + size_t(lo) * 4;
+    return lo;
+}
+
+// One 4 KiB unit (columns from x0) of the part described by pm = {off lo, off hi, L lo, L hi}:
+// rows [row0, row0 + RG) of the record `pat`, n_out rows in all.
+template <int RG>
+__device__ __forceinline__ void ragged_unit(uint8_t* base, cu32* pm, uint64_t x0, uint32_t d,
+                                            cu32* pat, uint32_t n_out, uint32_t row0) {
     const uint64_t off = uint64_t(pm[0]) | (uint64_t(pm[1]) << 32);
     const uint64_t len = uint64_t(pm[2]) | (uint64_t(pm[3]) << 32);
     const uint64_t cs = (len + 15) & ~uint64_t(15);
-    uint8_t* pbase = a.base + off;
-    const uint32_t d = a.d, n_out = a.n_rows, row0 = row_base + blockIdx.y * RG;
-    cu32* pat = as_const(a.pat);
+    uint8_t* pbase = base + off;
     cu32* in_idx = pat + 1;
     cu32* out_idx = pat + 1 + d + row0;
     cu32* tab = pat + 1 + d + n_out + size_t(row0) * kTabWords;
     const uint32_t tab_stride = n_out * kTabWords;
-    const uint64_t x0 = uint64_t(u - pre[lo]) * kRaggedUnit;
     const uint64_t x1 = x0 + kRaggedUnit < len ? x0 + kRaggedUnit : len;
     const uint64_t lane_x = uint64_t(threadIdx.x & 63u) * 16u;
 #pragma unroll 1
@@ -408,6 +408,50 @@ __global__ __launch_bounds__(kApplyThreads) void rs_apply_ragged_kernel(RaggedPa
                                                  out_idx, tab);
         }
     }
+}
+
+// grid.x = ceil(total_units / kRaggedWaves), grid.y = row groups of exactly RG rows from row_base.
+// Every listed part uses the record at pat + part_pat[lp] (null: the one record at pat, the
+// encode), all of a.n_rows rows.
+template <int RG>
+__global__ __launch_bounds__(kApplyThreads) void rs_apply_ragged_kernel(RaggedParams a,
+                                                                        uint32_t row_base) {
+    const uint32_t u = __builtin_amdgcn_readfirstlane(blockIdx.x * kRaggedWaves +
+                                                      (threadIdx.x >> 6));
+    if (u >= a.total_units) return;  // wave-uniform
+    cu32* pre = as_const(a.units);
+    const uint32_t lo = ragged_find(pre, a.n_parts, u);
+    cu32* pat = as_const(a.pat) + (a.part_pat ? as_const(a.part_pat)[lo] : 0u);
+    ragged_unit<RG>(a.base, as_const(a.parts) + size_t(lo) * 4,
+                    uint64_t(u - pre[lo]) * kRaggedUnit, a.d, pat, a.n_rows,
+                    row_base + blockIdx.y * RG);
+}
+
+// Ragged reconstruct: the listed parts are the ones that need a rebuild, each
+// with its own pattern record at pat + part_pat[lp] (inputs = its first d present chunks, outputs
+// = its missing chunks), so parts that miss different numbers of chunks share ONE launch.  The
+// wave reads its record's row count (word 0: a scalar load, wave-uniform) and branches to the
+// exact-RG body as rs_apply_var_kernel does per block; MAXRG is the row class (2, 4 or 8) the
+// host picked from the widest listed record, and a record outside 1..MAXRG writes nothing (the
+// host refuses such a list before launching).  Exactly L_k bytes of each rebuilt chunk are
+// written: present chunks, the padding up to the stride and unlisted parts are never stored to.
+// Plain loads, as the encode (the verification in front of it has just read the same chunks), and
+// plain stores: what is rebuilt is read next, by the copy back to the host or the caller's
+// consumer, and nothing here streams far enough past the L2 for a non-temporal hint to matter.
+template <int MAXRG>
+__global__ __launch_bounds__(kApplyThreads) void rs_reconstruct_ragged_kernel(RaggedParams a) {
+    const uint32_t u = __builtin_amdgcn_readfirstlane(blockIdx.x * kRaggedWaves +
+                                                      (threadIdx.x >> 6));
+    if (u >= a.total_units) return;  // wave-uniform
+    cu32* pre = as_const(a.units);
+    const uint32_t lo = ragged_find(pre, a.n_parts, u);
+    cu32* pat = as_const(a.pat) + as_const(a.part_pat)[lo];
+    cu32* pm = as_const(a.parts) + size_t(lo) * 4;
+    const uint64_t x0 = uint64_t(u - pre[lo]) * kRaggedUnit;
+    rg_dispatch<1, MAXRG>(pat[0], [&](auto rg) {
+        constexpr int RG = decltype(rg)::value;
+        ragged_unit<RG>(a.base, pm, x0, a.d, pat, RG, 0);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -919,6 +963,23 @@ hipError_t launch_rs_encode_ragged(const RaggedParams& a, hipStream_t s) {
     return hipSuccess;
 }
 
+// Listed parts with a record each of 1..kMaxApplyRows rows: one launch, in the row class of
+// a.n_rows (the widest listed record; 0 = unknown, the 8-row class).
+hipError_t launch_rs_reconstruct_ragged(const RaggedParams& a, hipStream_t s) {
+    if (a.n_parts == 0 || a.total_units == 0) return hipSuccess;
+    if (!a.part_pat || a.n_rows > kMaxApplyRows) return hipErrorInvalidValue;
+    if (a.total_units > ragged_max_units()) return hipErrorInvalidValue;
+    const uint32_t rows = a.n_rows ? a.n_rows : kMaxApplyRows;
+    const dim3 grid((a.total_units + kRaggedWaves - 1) / kRaggedWaves);
+    clear_stale_error();
+    if (rows <= 2)
+        hipLaunchKernelGGL(rs_reconstruct_ragged_kernel<2>, grid, dim3(kApplyThreads), 0, s, a);
+    else if (rows <= 4)
+        hipLaunchKernelGGL(rs_reconstruct_ragged_kernel<4>, grid, dim3(kApplyThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL(rs_reconstruct_ragged_kernel<8>, grid, dim3(kApplyThreads), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_fill(const FillParams& a, hipStream_t s) {
     const uint64_t n_inst = uint64_t(a.n_parts) * a.n_chunks;

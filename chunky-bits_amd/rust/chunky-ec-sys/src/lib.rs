@@ -167,6 +167,51 @@ pub mod sys {
             digests: *mut u8,
             stream: *mut c_void,
         ) -> c_int;
+        pub fn cec_parts_read(
+            codec: *const cec_codec,
+            shards: *const *mut u8,
+            chunk_lens: *const usize,
+            n_parts: usize,
+            present: *const u8,
+            expected: *const u8,
+            data_only: c_int,
+            verified: *mut u8,
+            part_status: *mut c_int,
+        ) -> c_int;
+        pub fn cec_reconstruct_ragged(
+            codec: *const cec_codec,
+            base: *mut u8,
+            part_offsets: *const usize,
+            chunk_lens: *const usize,
+            n_parts: usize,
+            present: *const u8,
+            data_only: c_int,
+            stream: *mut c_void,
+        ) -> c_int;
+        pub fn cec_read_ragged(
+            codec: *const cec_codec,
+            base: *mut u8,
+            part_offsets: *const usize,
+            chunk_lens: *const usize,
+            n_parts: usize,
+            present: *const u8,
+            expected: *const u8,
+            verified: *mut u8,
+            part_status: *mut c_int,
+            stream: *mut c_void,
+        ) -> c_int;
+        pub fn cec_resilver_ragged(
+            codec: *const cec_codec,
+            base: *mut u8,
+            part_offsets: *const usize,
+            chunk_lens: *const usize,
+            n_parts: usize,
+            present: *const u8,
+            expected: *const u8,
+            verified: *mut u8,
+            part_status: *mut c_int,
+            stream: *mut c_void,
+        ) -> c_int;
         pub fn cec_encode_batch(
             codec: *const cec_codec,
             batch: *const cec_part_batch,
@@ -831,6 +876,127 @@ pub unsafe fn encode_hash_ragged(
         digests,
         stream,
     ))
+}
+
+/// `cec_reconstruct_ragged`: `reconstruct` (`data_only` false) / `reconstruct_data` (true) of parts
+/// of different chunk lengths in device memory, asynchronous on `stream`.  `present` holds
+/// `n * (d+p)` flags.
+///
+/// # Safety
+/// `base` must be a device pointer covering the layout the offsets and lengths describe;
+/// `stream` a HIP stream of the current device or null.
+pub unsafe fn reconstruct_ragged(
+    codec: &ReedSolomon,
+    base: *mut u8,
+    part_offsets: &[usize],
+    chunk_lens: &[usize],
+    present: &[u8],
+    data_only: bool,
+    stream: *mut c_void,
+) -> Result<(), CecError> {
+    let t = codec.data_shard_count() + codec.parity_shard_count();
+    if part_offsets.len() != chunk_lens.len() || present.len() != chunk_lens.len() * t {
+        return Err(CecError::Engine(EngineError {
+            code: 101,
+            message: "part_offsets, chunk_lens and present differ in length".to_string(),
+        }));
+    }
+    check(sys::cec_reconstruct_ragged(
+        codec.raw,
+        base,
+        part_offsets.as_ptr(),
+        chunk_lens.as_ptr(),
+        chunk_lens.len(),
+        present.as_ptr(),
+        data_only as c_int,
+        stream,
+    ))
+}
+
+/// `cec_read_ragged` (`resilver` false) / `cec_resilver_ragged` (true): verify the loaded chunks
+/// of parts of different chunk lengths against `expected` (device, `[n][d+p][32]`), then rebuild
+/// every decodable part from its first d verified chunks.  Returns (verified flags, per-part
+/// status).
+///
+/// # Safety
+/// As [`reconstruct_ragged`]; `expected` must be a device pointer to `n * (d+p) * 32` bytes.
+pub unsafe fn read_ragged(
+    codec: &ReedSolomon,
+    base: *mut u8,
+    part_offsets: &[usize],
+    chunk_lens: &[usize],
+    present: &[u8],
+    expected: *const u8,
+    resilver: bool,
+    stream: *mut c_void,
+) -> Result<(Vec<u8>, Vec<c_int>), CecError> {
+    let t = codec.data_shard_count() + codec.parity_shard_count();
+    let n = chunk_lens.len();
+    if part_offsets.len() != n || present.len() != n * t {
+        return Err(CecError::Engine(EngineError {
+            code: 101,
+            message: "part_offsets, chunk_lens and present differ in length".to_string(),
+        }));
+    }
+    let mut verified = vec![0u8; n * t];
+    let mut status = vec![0 as c_int; n];
+    let call = if resilver { sys::cec_resilver_ragged } else { sys::cec_read_ragged };
+    check(call(
+        codec.raw,
+        base,
+        part_offsets.as_ptr(),
+        chunk_lens.as_ptr(),
+        n,
+        present.as_ptr(),
+        expected,
+        verified.as_mut_ptr(),
+        status.as_mut_ptr(),
+        stream,
+    ))?;
+    Ok((verified, status))
+}
+
+/// `cec_parts_read`: the read counterpart of [`parts_encode`].  `shards[k * (d+p) + i]` is a
+/// loaded chunk (`present` flag nonzero) of `chunk_lens[k]` bytes, or a buffer of that size the
+/// engine fills when it rebuilds the chunk (missing data under `data_only`, every missing chunk
+/// otherwise); `expected` is `[n][d+p][32]`.  Returns (verified flags, per-part status).
+pub fn parts_read(
+    codec: &ReedSolomon,
+    shards: &mut [&mut [u8]],
+    chunk_lens: &[usize],
+    present: &[u8],
+    expected: &[u8],
+    data_only: bool,
+) -> Result<(Vec<u8>, Vec<c_int>), CecError> {
+    let t = codec.data_shard_count() + codec.parity_shard_count();
+    let n = chunk_lens.len();
+    if shards.len() != n * t
+        || present.len() != n * t
+        || expected.len() != n * t * 32
+        || !shards.iter().enumerate().all(|(q, s)| s.len() >= chunk_lens[q / t])
+    {
+        return Err(CecError::Engine(EngineError {
+            code: 101,
+            message: "shards, chunk_lens, present and expected differ in length".to_string(),
+        }));
+    }
+    let ptrs: Vec<*mut u8> = shards.iter_mut().map(|s| s.as_mut_ptr()).collect();
+    let mut verified = vec![0u8; n * t];
+    let mut status = vec![0 as c_int; n];
+    check(unsafe {
+        sys::cec_parts_read(
+            codec.raw,
+            ptrs.as_ptr(),
+            chunk_lens.as_ptr(),
+            n,
+            present.as_ptr(),
+            expected.as_ptr(),
+            data_only as c_int,
+            verified.as_mut_ptr(),
+            status.as_mut_ptr(),
+        )
+    })?;
+    Ok((verified, status))
 }
 
 /// Batched `FileWriteBuilder::write` compute (writer.rs:166-231): `depth` slots of

@@ -201,6 +201,25 @@ int cec_parts_encode(const cec_codec* codec, const uint8_t* const* data_bufs,
                      const size_t* lengths, size_t n_parts, uint8_t* const* parity_outs,
                      uint8_t* digests_out, size_t* chunksizes);
 
+/* The read counterpart of cec_parts_encode: FilePart::read_with_context's compute (data_only =
+ * 1) or FilePart::resilver's (0) for n_parts parts of unrelated chunk lengths in one call.
+ * shards[k*(d+p)+i] follows cec_reconstruct's shard array: a loaded chunk (present[k*(d+p)+i]
+ * != 0, CEC_PRESENT_VERIFIED = trusted, not hashed) is chunk_lens[k] bytes that are read; a slot
+ * the crate would fill (missing data under data_only, every missing chunk otherwise) is caller
+ * memory of chunk_lens[k] bytes that is written, and NULL there, in a part with d or more chunks
+ * loaded, -> CEC_ERR_INVALID_ARGUMENT; other slots are not looked at.  expected is a HOST array
+ * [n_parts][d+p][32]; verified and part_status as cec_read_ragged.  The loaded chunks are packed
+ * in the cec_ragged_layout layout, moved up, verified and rebuilt as in cec_read_ragged /
+ * cec_resilver_ragged, and only the rebuilt chunks come back.  A loaded chunk that failed
+ * verification in a decodable part counts as missing: it is rebuilt into its own slot if the
+ * mode fills that slot.  A part reported CEC_TOO_FEW_SHARDS_PRESENT has nothing written.  A call
+ * with more than CEC_COALESCE_MAX_MIB of parts runs in several rounds, a single larger part
+ * alone.  Any chunk_lens[k] == 0 -> CEC_EMPTY_SHARD before anything is written; n_parts == 0 ->
+ * CEC_OK.  Concurrent calls are allowed. */
+int cec_parts_read(const cec_codec* codec, uint8_t* const* shards, const size_t* chunk_lens,
+                   size_t n_parts, const uint8_t* present, const uint8_t* expected,
+                   int data_only, uint8_t* verified, int* part_status);
+
 /* Per-call coalescing.  Concurrent cec_part_encode calls with the same codec and chunk length
  * (and concurrent cec_sha256 / cec_sha256_many calls) on the same device are gathered into one
  * launch: the first caller waits up to CEC_COALESCE_US microseconds (environment, default 200,
@@ -307,6 +326,39 @@ int cec_read_batch(const cec_codec* codec, const cec_part_batch* batch, const ui
 int cec_resilver_batch(const cec_codec* codec, const cec_part_batch* batch,
                        const uint8_t* present, const uint8_t* expected, uint8_t* verified,
                        int* part_status, void* stream);
+
+/* The read side of the ragged batch (layout and argument rules of cec_encode_hash_ragged: base
+ * DEVICE, part_offsets / chunk_lens HOST arrays copied before the call returns).
+ * cec_reconstruct_ragged: cec_reconstruct_batch over parts of different chunk lengths.
+ * present: HOST array of n_parts*(d+p) flags.  A part with some but fewer than d chunks present
+ * -> CEC_TOO_FEW_SHARDS_PRESENT, nothing launched; parts with nothing missing (data_only: no
+ * data chunk missing) are skipped; the others are rebuilt from their first d present chunks, all
+ * erasure counts up to 8 in one launch.  Exactly chunk_lens[k] bytes of each rebuilt chunk are
+ * written: never the padding up to the stride, the space between parts, a present chunk or a
+ * skipped part.  Asynchronous on `stream`.
+ * cec_read_ragged / cec_resilver_ragged: cec_read_batch / cec_resilver_batch over that layout.
+ * expected: DEVICE [n_parts][d+p][32]; verified (n_parts*(d+p)) and part_status (n_parts) are
+ * HOST outputs with the meanings of cec_read_batch; CEC_PRESENT_VERIFIED chunks are trusted and
+ * not hashed.  On `stream`: the verification (the chunks to hash, longest first), the readback
+ * of its flags (the one wait), then the rebuild of every decodable part from its first d
+ * VERIFIED chunks, queued when the call returns.  No speculative decode.  A part reported
+ * CEC_TOO_FEW_SHARDS_PRESENT keeps its loaded chunks and nothing of it is written; the call
+ * itself returns CEC_OK when only parts fail.
+ * Errors, all before any device use and in this order: null pointer ->
+ * CEC_ERR_INVALID_ARGUMENT (n_parts == 0 with a codec -> CEC_OK, nothing launched); any
+ * chunk_lens[k] == 0 -> CEC_EMPTY_SHARD; then the layout errors of cec_encode_hash_ragged ->
+ * CEC_ERR_INVALID_ARGUMENT; then cec_reconstruct_ragged's CEC_TOO_FEW_SHARDS_PRESENT; then
+ * CEC_ERR_NO_DEVICE. */
+int cec_reconstruct_ragged(const cec_codec* codec, uint8_t* base, const size_t* part_offsets,
+                           const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                           int data_only, void* stream);
+int cec_read_ragged(const cec_codec* codec, uint8_t* base, const size_t* part_offsets,
+                    const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                    const uint8_t* expected, uint8_t* verified, int* part_status, void* stream);
+int cec_resilver_ragged(const cec_codec* codec, uint8_t* base, const size_t* part_offsets,
+                        const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                        const uint8_t* expected, uint8_t* verified, int* part_status,
+                        void* stream);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Host-staged write pipeline (FileWriteBuilder::write's part loop, writer.rs:166-231)      */

@@ -793,6 +793,70 @@ struct FileReference {
             parts_per_batch, depth, devices);
         return out;
     }
+    // read() for many files in one go: result[f] equals files[f]->read(src, parts_per_batch,
+    // depth, devices), and the same ErasureError is thrown where a read() would throw.  Runs of
+    // two or more parts of one shape still go through read_run when parts_per_batch is set; every
+    // other part of every file (whole small files, short last parts, every part when
+    // parts_per_batch is 0) is gathered per (d, p), in windows of at most kManyWindowBytes, into
+    // ragged batches: one cec_parts_read call per window and retry round.  The retry rule inside
+    // a window is read_with_context's: d chunks drawn per part, data first; after a round only
+    // the parts reported TooFewShardsPresent load their failed chunks' next copy or further
+    // chunks and go up again, their verified chunks flagged CEC_PRESENT_VERIFIED (no carry pool
+    // on this path: those chunks travel again); TooFewShardsPresent when a part's copies run out.
+    // Data chunks are loaded into, and rebuilt into, their place in the result.
+    static constexpr size_t kManyWindowBytes = size_t(256) << 20;
+    static std::vector<Bytes> read_many(const std::vector<const FileReference*>& files,
+                                        const ChunkStore& src, size_t parts_per_batch = 0,
+                                        size_t depth = 4, const std::vector<int>& devices = {}) {
+        struct Pending {
+            const FilePart* part;
+            uint8_t* out;  // the part's d*L bytes in its file's result
+        };
+        struct Window {
+            std::vector<Pending> parts;
+            size_t bytes = 0;
+        };
+        std::vector<Bytes> out(files.size());
+        std::map<std::pair<size_t, size_t>, Window> windows;  // per (d, p)
+        auto flush = [&](size_t d, size_t p, Window& w) {
+            read_window(src, d, p, w.parts);
+            w.parts.clear();
+            w.bytes = 0;
+        };
+        for (size_t f = 0; f < files.size(); ++f) {
+            const FileReference& file = *files[f];
+            uint64_t total = 0;
+            for (const FilePart& part : file.parts) total += part.len_bytes();
+            out[f].resize(static_cast<size_t>(total));
+            std::vector<size_t> at(file.parts.size() + 1, 0);
+            for (size_t k = 0; k < file.parts.size(); ++k)
+                at[k + 1] = at[k] + file.parts[k].len_bytes();
+            file.for_runs(parts_per_batch, [&](size_t k0, size_t n) {
+                if (n >= 2) {
+                    size_t pos = at[k0];
+                    auto emit = [&](const uint8_t* b, size_t m) {
+                        detail::parallel_copy(out[f].data() + pos, b, m);
+                        pos += m;
+                    };
+                    file.read_run(src, k0, n, parts_per_batch, depth, devices, emit);
+                    return;
+                }
+                const FilePart& part = file.parts[k0];
+                Window& w = windows[{part.data.size(), part.parity.size()}];
+                if (!w.parts.empty() && w.bytes + part.len_bytes() > kManyWindowBytes)
+                    flush(part.data.size(), part.parity.size(), w);
+                w.parts.push_back({&part, out[f].data() + at[k0]});
+                w.bytes += part.len_bytes();
+            });
+        }
+        for (auto& kv : windows)
+            if (!kv.second.parts.empty()) flush(kv.first.first, kv.first.second, kv.second);
+        for (size_t f = 0; f < files.size(); ++f)
+            if (files[f]->length && *files[f]->length < out[f].size())
+                out[f].resize(static_cast<size_t>(*files[f]->length));
+        return out;
+    }
+
     // FileReadBuilder's reader (reader.rs:40-75) as a stream: the file's bytes in order (the
     // last part truncated to `length`, file_reference.rs:49-56) handed to sink(bytes, n) piece by
     // piece — a batched window of parts at a time, straight from the page-locked buffer the
@@ -904,6 +968,76 @@ struct FileReference {
                 ++run;
             fn(k, run);
             k += run;
+        }
+    }
+
+    // One window of read_many: parts of one (d, p) and any chunk lengths, verified and rebuilt by
+    // one cec_parts_read call per retry round; part q's data lands at parts[q].out.
+    template <typename Pending>
+    static void read_window(const ChunkStore& src, size_t d, size_t p,
+                            const std::vector<Pending>& parts) {
+        const size_t t = d + p, n = parts.size();
+        const ReedSolomon codec(d, p);
+        std::vector<uint8_t> good(n * t), tried(n * t), exhausted(n * t);
+        std::vector<size_t> cursor(n * t), have(n);
+        std::vector<Bytes> parity(n * p);  // the loaded parity copies (never handed out)
+        std::vector<size_t> active(n);
+        for (size_t q = 0; q < n; ++q) active[q] = q;
+        auto slot = [&](size_t q, size_t i) {
+            const size_t L = parts[q].part->chunksize;
+            if (i < d) return parts[q].out + i * L;
+            Bytes& b = parity[q * p + (i - d)];
+            if (b.size() != L) b.resize(L);
+            return b.data();
+        };
+        while (!active.empty()) {
+            const size_t m = active.size();
+            std::vector<uint8_t*> shards(m * t, nullptr);
+            std::vector<size_t> lens(m);
+            std::vector<uint8_t> present(m * t, 0), expected(m * t * 32), verified(m * t, 0);
+            std::vector<int> status(m, 0);
+            for (size_t a = 0; a < m; ++a) {
+                const size_t q = active[a];
+                const FilePart& part = *parts[q].part;
+                const size_t L = part.chunksize;
+                lens[a] = L;
+                uint8_t* gq = &good[q * t];
+                size_t added = 0;
+                for (size_t i : detail::draw_order(gq, &tried[q * t], &exhausted[q * t], t)) {
+                    if (have[q] + added >= d) break;
+                    tried[q * t + i] = 1;
+                    const Bytes* b =
+                        detail::next_copy(src, part.chunk(i), cursor[q * t + i], L, &cursor[q * t + i]);
+                    if (!b) {
+                        exhausted[q * t + i] = 1;
+                        continue;
+                    }
+                    std::memcpy(slot(q, i), b->data(), L);
+                    present[a * t + i] = 1;
+                    ++added;
+                }
+                if (added == 0) throw ErasureError(Error::TooFewShardsPresent);
+                for (size_t i = 0; i < t; ++i) {
+                    if (gq[i]) present[a * t + i] = CEC_PRESENT_VERIFIED;
+                    // data slots are the result's own bytes; parity is read only when loaded
+                    if (i < d || present[a * t + i]) shards[a * t + i] = slot(q, i);
+                    std::memcpy(&expected[(a * t + i) * 32], part.chunk(i).hash.digest().data(), 32);
+                }
+            }
+            detail::check(cec_parts_read(codec.raw(), shards.data(), lens.data(), m, present.data(),
+                                         expected.data(), 1, verified.data(), status.data()));
+            std::vector<size_t> still;
+            for (size_t a = 0; a < m; ++a) {
+                const size_t q = active[a];
+                for (size_t i = 0; i < t; ++i)
+                    if (verified[a * t + i] && !good[q * t + i]) {
+                        good[q * t + i] = 1;
+                        ++have[q];
+                    }
+                if (status[a] == CEC_TOO_FEW_SHARDS_PRESENT) still.push_back(q);
+                else if (status[a] != CEC_OK) detail::check(status[a]);
+            }
+            active.swap(still);
         }
     }
 

@@ -16,8 +16,24 @@ All arms' digests must agree (asserted).
 --device: 4096 x RS(10,4) x 64 KiB parts, device resident: cec_encode_hash_ragged with uniform
 lengths against cec_encode_hash_batch on the same bytes; both times and the ratio.
 
+--read: the read side on the same seeded files and shapes.  Every part is stored as the oracle
+encodes it and its data chunk k % d is erased, so every part is decoded from d - 1 data chunks and
+the first parity chunk:
+
+  a  the per-part way from 10 and from 256 threads: cec_sha256_many over the d loaded chunks,
+     the digests compared, then cec_reconstruct_data
+  b  one cec_parts_read call over all parts
+  c  the CPU oracle on 16 threads (SHA-256 of the d loaded chunks, reconstruct_data)
+
+All arms' rebuilt chunks must equal the erased ones (asserted).
+
+--device --read: 4096 x RS(10,4) x 64 KiB, two erasures per part, device resident:
+cec_reconstruct_ragged with uniform lengths against cec_reconstruct_batch on the same bytes.
+
     python tools/small_files_bench.py [--files 4096] [--repeats 3] [--shapes 3,2:10,4]
-    python tools/small_files_bench.py --device"""
+    python tools/small_files_bench.py --device
+    python tools/small_files_bench.py --read
+    python tools/small_files_bench.py --device --read"""
 import argparse
 import ctypes
 import json
@@ -177,6 +193,204 @@ def host_staged(args):
     print(json.dumps({"tool": "small_files_bench", "mode": "host", "results": results}))
 
 
+class ReadWorkload:
+    """The parts of `files` as the oracle stores them (d data + p parity chunks of L_k bytes,
+    digests), data chunk k % d of part k erased; d - 1 data chunks and parity chunk 0 are loaded."""
+
+    def __init__(self, pool, files, d, p):
+        self.d, self.p, self.t = d, p, d + p
+        self.rs = ce.ReedSolomon(d, p)
+        self.parts = cut_parts(files, d)
+        self.n = n = len(self.parts)
+        self.file_bytes = sum(s for _, s in files)
+        self.L = [(ln + d - 1) // d for _, ln in self.parts]
+        t = self.t
+        self.off = np.concatenate([[0], np.cumsum([t * L for L in self.L])])
+        self.store = np.zeros(int(self.off[-1]), np.uint8)  # part k: t chunks of L_k from off[k]
+        self.expected = np.zeros((n, t, 32), np.uint8)
+        lib = oracle.lib()
+        sb, eb = self.store.ctypes.data, self.expected.ctypes.data
+
+        def encode(k):
+            o, ln = self.parts[k]
+            at, L = int(self.off[k]), self.L[k]
+            self.store[at:at + ln] = pool[o:o + ln]
+            cs = ctypes.c_size_t(0)
+            st = lib.or_part_encode(d, p, ctypes.cast(sb + at, U8P), ln,
+                                    ctypes.cast(sb + at + d * L, U8P),
+                                    ctypes.cast(eb + k * t * 32, U8P), ctypes.byref(cs))
+            assert st == 0 and cs.value == L
+        with ThreadPoolExecutor(16) as ex:
+            list(ex.map(encode, range(n)))
+        self.erased = [k % d for k in range(n)]
+        self.loaded = [[i for i in range(d) if i != self.erased[k]] + [d] for k in range(n)]
+        # the erased chunks, kept aside and wiped in the store
+        self.out_off = np.concatenate([[0], np.cumsum(self.L)])
+        self.want = np.zeros(int(self.out_off[-1]), np.uint8)
+        for k in range(n):
+            at = int(self.off[k]) + self.erased[k] * self.L[k]
+            self.want[int(self.out_off[k]):int(self.out_off[k + 1])] = self.store[at:at + self.L[k]]
+            self.store[at:at + self.L[k]] = 0
+        self.out = np.zeros_like(self.want)  # every arm rebuilds into here
+        ob = self.out.ctypes.data
+        # pointer tables, made before any clock starts
+        null = U8P()
+        self.flags = np.zeros((n, t), np.uint8)
+        slots = []
+        for k in range(n):
+            at, L = int(self.off[k]), self.L[k]
+            row = [null] * t
+            for i in self.loaded[k]:
+                row[i] = ctypes.cast(sb + at + i * L, U8P)
+                self.flags[k, i] = 1
+            row[self.erased[k]] = ctypes.cast(ob + int(self.out_off[k]), U8P)
+            slots.append(row)
+        self.all_ptrs = (U8P * (n * t))(*[x for row in slots for x in row])
+        self.all_lens = (ctypes.c_size_t * n)(*self.L)
+        self.part_ptrs = [(U8P * t)(*row) for row in slots]
+        self.part_lens = [(ctypes.c_size_t * t)(*([L] * t)) for L in self.L]
+        self.hash_ptrs = [(U8P * d)(*[slots[k][i] for i in self.loaded[k]]) for k in range(n)]
+        self.hash_lens = [(ctypes.c_size_t * d)(*([L] * d)) for L in self.L]
+        self.verified = np.zeros((n, t), np.uint8)
+        self.status = (ctypes.c_int * n)()
+
+    def _check_digests(self, k, dig):
+        want = self.expected[k, self.loaded[k]]
+        assert np.array_equal(dig.reshape(self.d, 32), want), k
+
+    def arm_percall(self, threads, count=None):
+        h, d, t = self.rs.handle, self.d, self.t
+
+        def one(k):
+            dig = np.zeros(d * 32, np.uint8)
+            st = ce._lib.cec_sha256_many(self.hash_ptrs[k], self.hash_lens[k], d,
+                                         dig.ctypes.data_as(U8P))
+            assert st == 0, (st, k)
+            self._check_digests(k, dig)
+            pres = (ctypes.c_uint8 * t)(*self.flags[k])
+            st = ce._lib.cec_reconstruct_data(h, self.part_ptrs[k], self.part_lens[k], pres, t)
+            assert st == 0, (st, k)
+        with ThreadPoolExecutor(threads) as ex:
+            list(ex.map(one, range(count or self.n)))
+
+    def arm_ragged(self, count=None):
+        n = count or self.n
+        ce._check(ce._lib.cec_parts_read(
+            self.rs.handle, self.all_ptrs, self.all_lens, n, self.flags.ctypes.data_as(U8P),
+            self.expected.ctypes.data_as(U8P), 1, self.verified.ctypes.data_as(U8P), self.status))
+        assert all(s == 0 for s in self.status[:n])
+        assert np.array_equal(self.verified[:n], self.flags[:n])
+
+    def arm_cpu(self, threads=16, count=None):
+        lib = oracle.lib()
+        d, p, t = self.d, self.p, self.t
+
+        def one(k):
+            dig = np.zeros(d * 32, np.uint8)
+            for j in range(d):
+                lib.or_sha256(self.hash_ptrs[k][j], self.L[k],
+                              ctypes.cast(dig.ctypes.data + 32 * j, U8P))
+            self._check_digests(k, dig)
+            pres = (ctypes.c_uint8 * t)(*self.flags[k])
+            lens = (ctypes.c_size_t * t)(*[self.L[k] if f else 0 for f in self.flags[k]])
+            st = lib.or_rs_reconstruct(d, p, self.part_ptrs[k], lens, pres, t, 1)
+            assert st == 0, (st, k)
+        with ThreadPoolExecutor(threads) as ex:
+            list(ex.map(one, range(count or self.n)))
+
+
+def host_read(args):
+    pool, files = make_files(args.files)
+    results = []
+    for shape in args.shapes.split(":"):
+        d, p = (int(x) for x in shape.split(","))
+        w = ReadWorkload(pool, files, d, p)
+        print(f"== read RS({d},{p}) chunk 1 MiB: {len(files)} files, "
+              f"{w.file_bytes / 2**30:.2f} GiB, {w.n} parts, one data chunk of each erased",
+              flush=True)
+        arms = [("a: sha256_many + reconstruct_data x 10 threads", lambda c=None: w.arm_percall(10, c)),
+                ("a: sha256_many + reconstruct_data x 256 threads",
+                 lambda c=None: w.arm_percall(256, c)),
+                ("b: one parts_read call", lambda c=None: w.arm_ragged(c)),
+                ("c: CPU oracle x 16 threads", lambda c=None: w.arm_cpu(16, c))]
+        warm = min(w.n, 512)
+        for name, fn in arms:  # warm-up: b on the whole input (its staging is sized by it)
+            sec, _ = timed(lambda: fn(None if name.startswith("b") else warm))
+            print(f"   warm-up {name}: {sec:.3f} s", flush=True)
+        secs = {name: [] for name, _ in arms}
+        for rep in range(args.repeats):
+            for name, fn in arms:
+                w.out[:] = 0
+                sec, _ = timed(fn)
+                secs[name].append(sec)
+                assert np.array_equal(w.out, w.want), f"rebuilt chunks of '{name}' differ"
+                print(f"   repeat {rep + 1} {name}: {sec:.3f} s  "
+                      f"{w.file_bytes / sec / 1e9:7.2f} GB/s  {w.n / sec:9.0f} parts/s", flush=True)
+        print("   every arm rebuilt the erased chunks exactly, in every repeat")
+        names = [name for name, _ in arms]
+        wins = [secs[names[2]][r] < min(secs[names[0]][r], secs[names[1]][r])
+                for r in range(args.repeats)]
+        print(f"   b faster than the better per-part arm in each repeat: {wins}", flush=True)
+        results.append({"d": d, "p": p, "files": len(files), "parts": w.n,
+                        "file_bytes": w.file_bytes, "seconds": secs,
+                        "gbps": {k: [w.file_bytes / s / 1e9 for s in v] for k, v in secs.items()},
+                        "b_faster_each_repeat": wins})
+        del w
+    print(json.dumps({"tool": "small_files_bench", "mode": "host-read", "results": results}))
+
+
+def device_read(args):
+    d, p, n, L = 10, 4, 4096, 65536
+    t = d + p
+    dev = torch.device("cuda", 0)
+    rs = ce.ReedSolomon(d, p)
+    full = torch.zeros((n, t, L), dtype=torch.uint8, device=dev)
+    batch_full = ce.PartBatch.from_tensor(full, L)
+    ce.fill_synthetic(batch_full, d, 1)
+    ce.encode_batch(rs, batch_full)
+    present = np.ones((n, t), np.uint8)
+    for k in range(n):  # two erasures per part: one data chunk, one other chunk
+        present[k, [k % d, (k + 3) % t if (k + 3) % t != k % d else (k + 4) % t]] = 0
+    gone = torch.from_numpy(present == 0).to(dev)
+    pres = present.tobytes()
+    buf = full.clone()
+    batch = ce.PartBatch.from_tensor(buf, L)
+    offs, total = ce.ragged_layout(t, [L] * n)
+    assert total == buf.numel()
+    lens = [L] * n
+
+    def uniform():
+        ce.reconstruct_batch(rs, batch, pres, False)
+
+    def ragged():
+        ce.reconstruct_ragged(rs, buf.data_ptr(), offs, lens, pres, False)
+
+    def run(fn):
+        buf[gone] = 0
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        assert torch.equal(buf, full), "rebuilt chunks differ"
+        return e0.elapsed_time(e1)
+
+    for fn in (uniform, ragged):
+        run(fn)
+    ms = {"reconstruct_batch": [], "reconstruct_ragged": []}
+    for rep in range(args.repeats):
+        ms["reconstruct_batch"].append(run(uniform))
+        ms["reconstruct_ragged"].append(run(ragged))
+    print(f"== device resident read, {n} x RS({d},{p}) x {L} B, two erasures per part")
+    for k, v in ms.items():
+        print(f"   {k}: " + "  ".join(f"{x:.3f} ms" for x in v))
+    ratio = min(ms["reconstruct_ragged"]) / min(ms["reconstruct_batch"])
+    print(f"   ragged / uniform (best of {args.repeats}): {ratio:.3f}   (same rebuilt chunks)")
+    print(json.dumps({"tool": "small_files_bench", "mode": "device-read", "ms": ms,
+                      "ratio": ratio}))
+
+
 def device_mode(args):
     d, p, n, L = 10, 4, 4096, 65536
     t = d + p
@@ -232,12 +446,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--shapes", default="3,2:10,4")
     ap.add_argument("--device", action="store_true")
+    ap.add_argument("--read", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     if args.device:
-        device_mode(args)
+        (device_read if args.read else device_mode)(args)
     else:
-        host_staged(args)
+        (host_read if args.read else host_staged)(args)
 
 
 if __name__ == "__main__":
