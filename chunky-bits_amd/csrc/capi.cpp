@@ -3,72 +3,23 @@
 // Host responsibilities only: argument checks in the crate's order, coding/decode matrices
 // (tiny), erasure-pattern grouping, staging, and kernel launches.  Every shard byte is
 // processed by the gfx950 kernels in kernels.hip; there is no CPU compute path.
-#include "chunky_ec.h"
-
-#include <hip/hip_runtime.h>
+#include "capi_internal.hpp"
 
 #include <algorithm>
-#include <cstdlib>
-#include <array>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
 #include <deque>
-#include <list>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <unordered_map>
-#include <vector>
 
-#include "gf256.hpp"
 #include "hostmem.hpp"
-#include "kernels.hpp"
-#include "knobs.hpp"
 
 using namespace cec;
 
 namespace {
 
 thread_local std::string g_last_error;
-
-int hip_fail(hipError_t e, const char* what) {
-    g_last_error = std::string(what) + ": " + hipGetErrorString(e);
-    return e == hipErrorOutOfMemory ? CEC_ERR_OUT_OF_MEMORY : CEC_ERR_HIP;
-}
-
-#define HIP_TRY(expr)                                        \
-    do {                                                     \
-        hipError_t _e = (expr);                              \
-        if (_e != hipSuccess) return hip_fail(_e, #expr);    \
-    } while (0)
-
-#define CEC_TRY(expr)              \
-    do {                           \
-        int _s = (expr);           \
-        if (_s != CEC_OK) return _s; \
-    } while (0)
-
-int current_device(int* dev) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-        g_last_error = "no HIP device";
-        return CEC_ERR_NO_DEVICE;
-    }
-    HIP_TRY(hipGetDevice(dev));
-    return CEC_OK;
-}
-
-constexpr size_t kChunkAlign = 256;
-size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-bool aligned16(const void* p, size_t a, size_t b) {
-    return (reinterpret_cast<uintptr_t>(p) % 16 == 0) && (a % 16 == 0) && (b % 16 == 0);
-}
 
 // ------------------------------------------------------------------------------------------
 // Small per-launch device buffers (decode pattern records, verify item lists, flag arrays).
@@ -88,15 +39,7 @@ bool aligned16(const void* p, size_t a, size_t b) {
 // ------------------------------------------------------------------------------------------
 class ScratchPool {
    public:
-    struct Buf {
-        int device = 0;
-        uint8_t* dev = nullptr;
-        uint8_t* host = nullptr;  // page-locked mirror of the same size
-        size_t cap = 0;
-        hipEvent_t done = nullptr;
-        bool in_use = false;   // handed out, release not called yet
-        bool pending = false;  // released: `done` marks the end of its last use
-    };
+    using Buf = ScratchBuf;
 
     // A buffer of >= bytes on `device` whose last use has completed.
     hipError_t acquire(int device, size_t bytes, Buf** out) {
@@ -172,32 +115,48 @@ ScratchPool& scratch_pool() {
     return *pool;
 }
 
-// One scratch buffer for the launches of one call: acquire, fill / upload, launch, and the
-// destructor releases it on the stream those launches went to (error paths included).
-class Scratch {
-   public:
-    Scratch() = default;
-    Scratch(const Scratch&) = delete;
-    Scratch& operator=(const Scratch&) = delete;
-    ~Scratch() {
-        if (buf_) scratch_pool().release(buf_, stream_);
-    }
-    int acquire(size_t bytes, hipStream_t s) {
-        int dev = 0;
-        CEC_TRY(current_device(&dev));
-        HIP_TRY(scratch_pool().acquire(dev, bytes, &buf_));
-        stream_ = s;
-        return CEC_OK;
-    }
-    uint8_t* dev() const { return buf_->dev; }
-    uint8_t* host() const { return buf_->host; }
+PatternKey make_key(const uint8_t* present, size_t t, bool data_only) {
+    PatternKey k;
+    for (size_t i = 0; i < t; ++i)
+        if (present[i]) k.bits[i / 64] |= uint64_t(1) << (i % 64);
+    k.data_only = data_only;
+    return k;
+}
 
-   private:
-    ScratchPool::Buf* buf_ = nullptr;
-    hipStream_t stream_ = nullptr;
-};
+}  // namespace
 
-// Upload `words` into `sc` (acquired here) on stream s; *dptr = their device copy.
+namespace cec {  // what capi_internal.hpp declares (described there)
+
+void set_last_error(std::string msg) { g_last_error = std::move(msg); }
+const std::string& last_error() { return g_last_error; }
+
+int hip_fail(hipError_t e, const char* what) {
+    g_last_error = std::string(what) + ": " + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? CEC_ERR_OUT_OF_MEMORY : CEC_ERR_HIP;
+}
+
+int current_device(int* dev) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        g_last_error = "no HIP device";
+        return CEC_ERR_NO_DEVICE;
+    }
+    HIP_TRY(hipGetDevice(dev));
+    return CEC_OK;
+}
+
+Scratch::~Scratch() {
+    if (buf_) scratch_pool().release(buf_, stream_);
+}
+
+int Scratch::acquire(size_t bytes, hipStream_t s) {
+    int dev = 0;
+    CEC_TRY(current_device(&dev));
+    HIP_TRY(scratch_pool().acquire(dev, bytes, &buf_));
+    stream_ = s;
+    return CEC_OK;
+}
+
 int upload_words(const std::vector<uint32_t>& words, hipStream_t s, Scratch& sc, uint32_t** dptr) {
     const size_t bytes = std::max<size_t>(words.size() * sizeof(uint32_t), 4);
     CEC_TRY(sc.acquire(bytes, s));
@@ -208,35 +167,6 @@ int upload_words(const std::vector<uint32_t>& words, hipStream_t s, Scratch& sc,
     return CEC_OK;
 }
 
-// ------------------------------------------------------------------------------------------
-// Staging contexts for the host-buffer API: a stream + a device buffer, leased per call from a
-// bounded per-device pool (not thread_local: the reference calls the crate from tokio's
-// blocking pool, whose threads come and go, file_part.rs:128,161 / any.rs:19-24, so per-thread
-// resources would leak with every retired thread).  At most kMaxIdleCtx contexts per device
-// stay alive between calls, holding at most CEC_IDLE_STAGING_MIB (default 1 GiB) of device
-// buffers together; cec_release_cached() frees the idle ones.
-// ------------------------------------------------------------------------------------------
-struct StageCtx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    uint8_t* dbuf = nullptr;
-    size_t dcap = 0;
-    void release_buffer() {
-        if (dbuf) (void)hipFree(dbuf);
-        dbuf = nullptr;
-        dcap = 0;
-    }
-    void destroy() {  // on `device` (callers set it)
-        if (stream) {
-            (void)hipStreamSynchronize(stream);
-            (void)hipStreamDestroy(stream);
-        }
-        stream = nullptr;
-        release_buffer();
-    }
-};
-
-// Stream + device staging of at least device_bytes (grown, never shrunk while leased).
 int ctx_reserve(StageCtx& c, size_t device_bytes) {
     if (!c.stream) HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
     if (c.dcap < device_bytes) {
@@ -248,6 +178,129 @@ int ctx_reserve(StageCtx& c, size_t device_bytes) {
     return CEC_OK;
 }
 
+int PinnedBuf::reserve(size_t bytes, size_t cap_hint) {
+    if (cap >= bytes) return CEC_OK;
+    if (ptr) HIP_TRY(hipHostFree(ptr));
+    ptr = nullptr;
+    cap = 0;
+    const size_t want =
+        round_up(bytes <= (size_t(64) << 20) ? std::max(bytes, size_t(64) << 20)
+                                             : std::max(bytes, cap_hint),
+                 1 << 20);
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ptr), want, hipHostMallocDefault));
+    cap = want;
+    return CEC_OK;
+}
+
+Arena* ArenaPool::take(int device) {
+    std::lock_guard<std::mutex> lk(mu_);
+    auto& v = free_[device];
+    if (v.empty()) {
+        all_.push_back(std::make_unique<Arena>());
+        all_.back()->dev.device = device;
+        return all_.back().get();
+    }
+    Arena* a = v.back();
+    v.pop_back();
+    return a;
+}
+
+void ArenaPool::give(int device, Arena* a) {
+    std::lock_guard<std::mutex> lk(mu_);
+    free_[device].push_back(a);
+}
+
+int check_present(size_t d, size_t t, const uint8_t* present, size_t n_parts) {
+    for (size_t k = 0; k < n_parts; ++k) {
+        size_t n_present = 0;
+        for (size_t i = 0; i < t; ++i) n_present += present[k * t + i] ? 1 : 0;
+        if (n_present != t && n_present < d) return CEC_TOO_FEW_SHARDS_PRESENT;
+    }
+    return CEC_OK;
+}
+
+void plan_decode(cec_codec* c, const uint8_t* present, size_t n_parts, bool data_only,
+                 DecodePlan* plan) {
+    const size_t t = c->d + c->p;
+    // Group parts by pattern; bucket patterns by output-row count.
+    std::map<PatternKey, std::pair<uint32_t, std::vector<uint32_t>>> groups;  // key -> (n_out, parts)
+    for (size_t k = 0; k < n_parts; ++k) {
+        const uint8_t* pr = present + k * t;
+        size_t n_present = 0;
+        for (size_t i = 0; i < t; ++i) n_present += pr[i] ? 1 : 0;
+        if (n_present == t) continue;
+        PatternKey key = make_key(pr, t, data_only);
+        auto& g = groups[key];
+        g.second.push_back(uint32_t(k));
+    }
+    std::vector<uint32_t>& words = plan->words;
+    std::map<uint32_t, std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> buckets;
+    for (auto& kv : groups) {
+        auto rec = c->decode_record(kv.first);
+        const uint32_t n_out = (*rec)[0];
+        if (n_out == 0) continue;  // data_only: only parity missing, nothing to do
+        if (n_out <= max_var_rows()) plan->var_rows = std::max(plan->var_rows, n_out);
+        const uint32_t off = uint32_t(words.size());
+        words.insert(words.end(), rec->begin(), rec->end());
+        auto& bk = buckets[n_out <= max_var_rows() ? 0u : n_out];  // 0 = the shared launch
+        for (uint32_t part : kv.second.second) {
+            bk.first.push_back(part);
+            bk.second.push_back(off);
+        }
+    }
+    for (auto& kv : buckets) {
+        plan->launches.push_back({kv.first, words.size(), kv.second.first.size()});
+        words.insert(words.end(), kv.second.first.begin(), kv.second.first.end());
+        words.insert(words.end(), kv.second.second.begin(), kv.second.second.end());
+    }
+}
+
+int check_row_class(const DecodePlan& plan, const DecodePlan::Launch& l, uint32_t n_rows,
+                    const char* who) {
+    const uint32_t* pat_off = plan.words.data() + l.ids + l.count;
+    for (size_t q = 0; q < l.count; ++q)
+        if (plan.words[pat_off[q]] == 0 || plan.words[pat_off[q]] > n_rows) {
+            g_last_error = std::string(who) + ": a listed pattern is wider than its launch";
+            return CEC_ERR_INVALID_ARGUMENT;
+        }
+    return CEC_OK;
+}
+
+bool rebuild_mask(size_t d, size_t t, size_t n_parts, const uint8_t* present, uint8_t* verified,
+                  int* part_status, bool only_failed, std::vector<uint8_t>* mask) {
+    const size_t n = n_parts * t;
+    for (size_t i = 0; i < n; ++i)  // verified by an earlier pass: trusted, not hashed again
+        if (present[i] == CEC_PRESENT_VERIFIED) verified[i] = 1;
+    mask->assign(n, uint8_t(1));
+    bool any = false;
+    for (size_t k = 0; k < n_parts; ++k) {
+        size_t good = 0;
+        bool bad = false;
+        for (size_t i = 0; i < t; ++i) {
+            good += verified[k * t + i] ? 1 : 0;
+            bad |= present[k * t + i] && !verified[k * t + i];
+        }
+        part_status[k] = good >= d ? CEC_OK : CEC_TOO_FEW_SHARDS_PRESENT;
+        if (good >= d && (bad || !only_failed)) {
+            std::copy(verified + k * t, verified + (k + 1) * t, mask->begin() + k * t);
+            any = true;
+        }
+    }
+    return any;
+}
+
+}  // namespace cec
+
+namespace {
+
+// ------------------------------------------------------------------------------------------
+// Staging contexts for the host-buffer API: a stream + a device buffer, leased per call from a
+// bounded per-device pool (not thread_local: the reference calls the crate from tokio's
+// blocking pool, whose threads come and go, file_part.rs:128,161 / any.rs:19-24, so per-thread
+// resources would leak with every retired thread).  At most kMaxIdleCtx contexts per device
+// stay alive between calls, holding at most CEC_IDLE_STAGING_MIB (default 1 GiB) of device
+// buffers together; cec_release_cached() frees the idle ones.
+// ------------------------------------------------------------------------------------------
 constexpr size_t kMaxIdleCtx = 8;
 // Device bytes idle contexts may hold per device (knobs().idle_staging_bytes, the
 // CEC_IDLE_STAGING_MIB knob, default 1 GiB).  Bounding the total (not each buffer) keeps a
@@ -363,125 +416,6 @@ class CtxLease {
     std::unique_ptr<StageCtx> c_;
 };
 
-// Erasure-pattern key: present bitset (<= 256 shards) + data_only.
-struct PatternKey {
-    std::array<uint64_t, 4> bits{};
-    bool data_only = false;
-    bool operator<(const PatternKey& o) const {
-        if (bits != o.bits) return bits < o.bits;
-        return data_only < o.data_only;
-    }
-};
-
-}  // namespace
-
-// ------------------------------------------------------------------------------------------
-// Codec
-// ------------------------------------------------------------------------------------------
-struct cec_codec {
-    size_t d = 0, p = 0;
-    ByteMatrix m;                  // (d+p) x d
-    std::vector<uint32_t> enc;     // pattern record: parity rows over the d data chunks
-    bool bs = false;               // parity rows = a compiled bit-sliced shape (bs_encode_matches)
-    std::mutex mu;
-    std::unordered_map<int, uint32_t*> dev_enc;  // encode record per device
-    // Decode records, least recently used first out once kDecCacheCap patterns are cached (every
-    // 1..4-erasure pattern of RS(10,4), both modes, is 2 940).
-    static constexpr size_t kDecCacheCap = 4096;
-    using Record = std::shared_ptr<const std::vector<uint32_t>>;
-    std::list<PatternKey> dec_lru;  // front = most recent
-    std::map<PatternKey, std::pair<Record, std::list<PatternKey>::iterator>> dec_cache;
-
-    ~cec_codec() {
-        int cur = 0;
-        if (hipGetDevice(&cur) != hipSuccess) return;
-        for (auto& kv : dev_enc) {
-            if (hipSetDevice(kv.first) == hipSuccess) (void)hipFree(kv.second);
-        }
-        (void)hipSetDevice(cur);
-    }
-
-    // Device copy of the encode record on the current device.
-    int encode_record(uint32_t** out) {
-        int dev = 0;
-        CEC_TRY(current_device(&dev));
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = dev_enc.find(dev);
-        if (it != dev_enc.end()) {
-            *out = it->second;
-            return CEC_OK;
-        }
-        uint32_t* ptr = nullptr;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ptr), enc.size() * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy(ptr, enc.data(), enc.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        dev_enc[dev] = ptr;
-        *out = ptr;
-        return CEC_OK;
-    }
-
-    // Decode record for a present set: inputs = first d present chunks (the crate's choice,
-    // reconstruct_internal), outputs = missing data (+ missing parity unless data_only).
-    // Missing data rows = rows of inv(M[valid]); missing parity rows = M[r] * inv(M[valid]),
-    // i.e. the crate's "recompute parity from the rebuilt data" folded into one pass
-    // (identical bytes: GF(2^8) arithmetic is exact).
-    std::shared_ptr<const std::vector<uint32_t>> decode_record(const PatternKey& key) {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = dec_cache.find(key);
-        if (it != dec_cache.end()) {
-            dec_lru.splice(dec_lru.begin(), dec_lru, it->second.second);
-            return it->second.first;
-        }
-        const size_t t = d + p;
-        std::vector<uint32_t> in_idx, out_idx;
-        std::vector<size_t> miss_par;
-        for (size_t i = 0; i < t; ++i) {
-            const bool present = (key.bits[i / 64] >> (i % 64)) & 1;
-            if (present) {
-                if (in_idx.size() < d) in_idx.push_back(uint32_t(i));
-            } else if (i < d) {
-                out_idx.push_back(uint32_t(i));
-            } else if (!key.data_only) {
-                miss_par.push_back(i);
-            }
-        }
-        for (size_t i : miss_par) out_idx.push_back(uint32_t(i));
-        ByteMatrix sub(d, d), dec;
-        for (size_t r = 0; r < d; ++r)
-            for (size_t c = 0; c < d; ++c) sub.at(r, c) = m.at(in_idx[r], c);
-        invert(sub, dec);  // any d rows of M are independent (distinct Vandermonde points)
-        ByteMatrix rows(out_idx.size(), d);
-        for (size_t k = 0; k < out_idx.size(); ++k) {
-            const size_t o = out_idx[k];
-            if (o < d) {
-                for (size_t c = 0; c < d; ++c) rows.at(k, c) = dec.at(o, c);
-            } else {
-                const Gf256& g = Gf256::get();
-                for (size_t c = 0; c < d; ++c) {
-                    uint8_t acc = 0;
-                    for (size_t q = 0; q < d; ++q) acc ^= g.mul(m.at(o, q), dec.at(q, c));
-                    rows.at(k, c) = acc;
-                }
-            }
-        }
-        auto rec = std::make_shared<std::vector<uint32_t>>(pattern_words(d, out_idx.size()));
-        write_pattern(rec->data(), d, in_idx, out_idx, rows);
-        if (dec_cache.size() >= kDecCacheCap) {
-            dec_cache.erase(dec_lru.back());
-            dec_lru.pop_back();
-        }
-        dec_lru.push_front(key);
-        dec_cache.emplace(key, std::make_pair(Record(rec), dec_lru.begin()));
-        return rec;
-    }
-
-    size_t cached_patterns() {
-        std::lock_guard<std::mutex> lk(mu);
-        return dec_cache.size();
-    }
-};
-
-namespace {
-
 // Crate checks shared by the per-part reconstruct entry points.  Returns CEC_OK with *len set
 // and *work = true if something must be rebuilt.
 int check_reconstruct(const cec_codec* c, const size_t* lens, const uint8_t* present,
@@ -503,14 +437,6 @@ int check_reconstruct(const cec_codec* c, const size_t* lens, const uint8_t* pre
     if (!*work) return CEC_OK;
     if (n_present < c->d) return CEC_TOO_FEW_SHARDS_PRESENT;
     return CEC_OK;
-}
-
-PatternKey make_key(const uint8_t* present, size_t t, bool data_only) {
-    PatternKey k;
-    for (size_t i = 0; i < t; ++i)
-        if (present[i]) k.bits[i / 64] |= uint64_t(1) << (i % 64);
-    k.data_only = data_only;
-    return k;
 }
 
 int reconstruct_host(const cec_codec* cc, uint8_t* const* shards, const size_t* lens,
@@ -596,38 +522,8 @@ std::atomic<uint64_t> g_calls{0}, g_launches{0};
 
 uint32_t coalesce_window_us() { return knobs().coalesce_us; }
 
-size_t coalesce_max_bytes() { return knobs().coalesce_max_bytes; }
 
 bool coalesce_trace() { return knobs().coalesce_trace; }
-
-// Pinned host staging, never shrunk.  Pinning costs ~0.35 s per GiB, so the first growth
-// past 64 MiB goes straight to the batch cap (one pinning per process, not one per size step).
-struct PinnedBuf {
-    uint8_t* ptr = nullptr;
-    size_t cap = 0;
-    int reserve(size_t bytes, size_t cap_hint) {
-        if (cap >= bytes) return CEC_OK;
-        if (ptr) HIP_TRY(hipHostFree(ptr));
-        ptr = nullptr;
-        cap = 0;
-        const size_t want =
-            round_up(bytes <= (size_t(64) << 20) ? std::max(bytes, size_t(64) << 20)
-                                                 : std::max(bytes, cap_hint),
-                     1 << 20);
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ptr), want, hipHostMallocDefault));
-        cap = want;
-        return CEC_OK;
-    }
-};
-
-struct Arena {
-    StageCtx dev;  // stream + device staging
-    PinnedBuf in, out;
-    // the parity comes back on a side stream as soon as the encode is done, beside the SHA-256
-    // chains (profiles/r2_early_d2h/; made on first use; arenas live as long as the process)
-    hipStream_t side = nullptr;
-    hipEvent_t encoded = nullptr;
-};
 
 struct CoalesceKey {
     const void* codec;
@@ -710,7 +606,7 @@ class Coalescer {
         }
         --callers_;
         lk.unlock();
-        if (r->status != CEC_OK) g_last_error = r->err;
+        if (r->status != CEC_OK) set_last_error(r->err);
         return r->status;
     }
 
@@ -777,7 +673,7 @@ class Coalescer {
             peak_ = callers_;
             batches_since_peak_ = 0;
         }
-        Arena* arena = take_arena(key.device);
+        Arena* arena = arenas_.take(key.device);
         gathering_ = false;
         if (coalesce_trace())
             std::fprintf(stderr, "[cec coalesce] lead arena %p: %zu callers, %u active, %zu queued\n",
@@ -838,21 +734,9 @@ class Coalescer {
                          ms(t3, std::chrono::steady_clock::now()));
         }
         r->phase = Phase::Finished;
-        free_[key.device].push_back(arena);
+        arenas_.give(key.device, arena);
         --active_;
         wake_next();
-    }
-
-    // A free arena of `device` (called with mu_ held; at most coalesce_inflight() are in use).
-    Arena* take_arena(int device) {
-        auto& free_list = free_[device];
-        if (free_list.empty()) {
-            arenas_.push_back(std::make_unique<Arena>());
-            return arenas_.back().get();
-        }
-        Arena* a = free_list.back();
-        free_list.pop_back();
-        return a;
     }
 
     std::mutex mu_;
@@ -866,8 +750,7 @@ class Coalescer {
     size_t peak_ = 0;                // most callers in progress at once, lately
     uint32_t batches_since_peak_ = 0;
     uint64_t last_run_us_ = 0;       // launch-to-results time of the last batch
-    std::vector<std::unique_ptr<Arena>> arenas_;  // owned; free lists per device below
-    std::map<int, std::vector<Arena*>> free_;
+    ArenaPool arenas_;               // at most coalesce_inflight() in use
 };
 
 // ---- cec_sha256(_many): one request = n buffers ----
@@ -1173,248 +1056,242 @@ void coalesce_stats(uint64_t* calls, uint64_t* launches) {
     if (launches) *launches = g_launches.load();
 }
 
-// ------------------------------------------------------------------------------------------
-// Ragged batches (cec_encode_hash_ragged, cec_parts_encode): parts of different chunk lengths,
-// part k's chunk i at base + off[k] + i * stride(L_k), stride = L rounded up to 16.
-// ------------------------------------------------------------------------------------------
-constexpr size_t kRaggedAlign = 16;
-
-// L rounded up to 16; false when that overflows.
-bool ragged_stride(size_t L, size_t* out) {
-    if (L > SIZE_MAX - (kRaggedAlign - 1)) return false;
-    *out = (L + kRaggedAlign - 1) / kRaggedAlign * kRaggedAlign;
-    return true;
-}
-
-// The packed layout: part k+1 directly behind part k.
-int ragged_layout(size_t t, const size_t* lens, size_t n, size_t* offs, size_t* total) {
-    size_t off = 0;
-    for (size_t k = 0; k < n; ++k) {
-        if (lens[k] == 0) return CEC_EMPTY_SHARD;
-        size_t cs = 0, span = 0;
-        if (!ragged_stride(lens[k], &cs) || __builtin_mul_overflow(t, cs, &span) ||
-            span > SIZE_MAX - off)
-            return CEC_ERR_INVALID_ARGUMENT;
-        offs[k] = off;
-        off += span;
-    }
-    *total = off;
+int batch_ok(const cec_part_batch* b) {
+    if (!b || !b->base) return CEC_ERR_INVALID_ARGUMENT;
     return CEC_OK;
 }
 
-// Every argument check of cec_encode_hash_ragged (no device use); *units = the launch's work
-// units.
-int ragged_check(const cec_codec* c, const uint8_t* base, const size_t* offs, const size_t* lens,
-                 size_t n, uint64_t* units) {
-    const size_t t = c->d + c->p;
-    size_t items = 0;  // SHA-256 items are 32-bit (checked before the arrays are walked)
-    if (__builtin_mul_overflow(n, t, &items) || items > 0xFFFFFFFFull)
-        return CEC_ERR_INVALID_ARGUMENT;
-    for (size_t k = 0; k < n; ++k)
-        if (lens[k] == 0) return CEC_EMPTY_SHARD;
-    if (reinterpret_cast<uintptr_t>(base) % kRaggedAlign) return CEC_ERR_INVALID_ARGUMENT;
-    const uint64_t unit = ragged_unit_bytes(), max_units = ragged_max_units();
-    uint64_t total = 0;
-    size_t end = 0;  // first byte behind the parts so far
-    for (size_t k = 0; k < n; ++k) {
-        size_t cs = 0, span = 0;
-        if (offs[k] % kRaggedAlign || offs[k] < end) return CEC_ERR_INVALID_ARGUMENT;
-        if (!ragged_stride(lens[k], &cs) || __builtin_mul_overflow(t, cs, &span) ||
-            span > SIZE_MAX - offs[k])
-            return CEC_ERR_INVALID_ARGUMENT;
-        end = offs[k] + span;
-        total += (uint64_t(lens[k] - 1)) / unit + 1;
-        if (total > max_units) return CEC_ERR_INVALID_ARGUMENT;  // never a silent wrap
+// cec_reconstruct_batch with each decode block reserving lds_reserve bytes of LDS (see
+// ApplyParams::lds_reserve).
+int reconstruct_batch(const cec_codec* cc, const cec_part_batch* b, const uint8_t* present,
+                      int data_only, void* stream, uint32_t lds_reserve) {
+    if (!cc || !present) return CEC_ERR_INVALID_ARGUMENT;
+    CEC_TRY(batch_ok(b));
+    if (b->n_parts == 0) return CEC_OK;
+    if (b->chunk_len == 0) return CEC_EMPTY_SHARD;
+    if (b->n_parts > 0xFFFFFFFFull) return CEC_ERR_INVALID_ARGUMENT;
+    cec_codec* c = const_cast<cec_codec*>(cc);
+    const size_t d = c->d, t = c->d + c->p;
+    // Validate every part before launching anything.
+    CEC_TRY(check_present(d, t, present, b->n_parts));
+    DecodePlan plan;
+    plan_decode(c, present, b->n_parts, data_only != 0, &plan);
+    if (plan.launches.empty()) return CEC_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint32_t* dwords = nullptr;
+    Scratch scratch;  // released on s behind the launches below
+    CEC_TRY(upload_words(plan.words, s, scratch, &dwords));
+    const bool vec = aligned16(b->base, b->part_stride, b->chunk_stride);
+    int status = CEC_OK;
+    for (size_t i = 0; i < plan.launches.size() && status == CEC_OK; ++i) {
+        const DecodePlan::Launch& l = plan.launches[i];
+        ApplyParams a{};
+        a.base = b->base;
+        a.part_stride = b->part_stride;
+        a.chunk_stride = b->chunk_stride;
+        a.len = b->chunk_len;
+        a.pat = dwords;
+        a.part_ids = dwords + l.ids;
+        a.part_pat = dwords + l.ids + l.count;
+        a.n_parts = uint32_t(l.count);
+        a.d = uint32_t(d);
+        a.n_rows = l.n_out ? l.n_out : plan.var_rows;
+        if (!l.n_out) CEC_TRY(check_row_class(plan, l, a.n_rows, "reconstruct_batch"));
+        a.lds_reserve = lds_reserve;
+        hipError_t e = l.n_out ? launch_rs_apply(a, vec, s) : launch_rs_apply_var(a, vec, s);
+        if (e != hipSuccess) status = hip_fail(e, "launch_rs_apply");
     }
-    *units = total;
-    return CEC_OK;
+    return status;
 }
 
-// The launches of a checked ragged batch on `s`: one upload of the per-part words (prefix array
-// of work units, offsets and lengths, the SHA-256 item list), the GF(2^8) kernel, the SHA-256
-// kernel.  The host arrays are copied into the scratch buffer's page-locked mirror before this
-// returns.
-int ragged_launch(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* lens, size_t n,
-                  uint64_t units, uint8_t* digests, hipStream_t s) {
-    const size_t t = c->d + c->p, items = n * t;
-    uint32_t* drec = nullptr;
-    CEC_TRY(c->encode_record(&drec));
-    // [ptrs u64 x items][lens u64 x items][order u32 x items][units u32 x n+1][parts u32 x 4n]
-    const size_t o_len = items * 8, o_ord = o_len + items * 8, o_units = o_ord + items * 4,
-                 o_parts = o_units + (n + 1) * 4, bytes = o_parts + n * 16;
-    Scratch sc;  // released on s behind the launches below
-    CEC_TRY(sc.acquire(bytes, s));
-    uint64_t* h_ptr = reinterpret_cast<uint64_t*>(sc.host());
-    uint64_t* h_len = reinterpret_cast<uint64_t*>(sc.host() + o_len);
-    uint32_t* h_ord = reinterpret_cast<uint32_t*>(sc.host() + o_ord);
-    uint32_t* h_units = reinterpret_cast<uint32_t*>(sc.host() + o_units);
-    uint32_t* h_parts = reinterpret_cast<uint32_t*>(sc.host() + o_parts);
-    const uint64_t unit = ragged_unit_bytes();
-    uint64_t acc = 0;
-    for (size_t k = 0; k < n; ++k) {
-        const uint64_t L = lens[k], cs = (L + kRaggedAlign - 1) / kRaggedAlign * kRaggedAlign;
-        h_units[k] = uint32_t(acc);
-        acc += (L - 1) / unit + 1;
-        h_parts[4 * k + 0] = uint32_t(offs[k]);
-        h_parts[4 * k + 1] = uint32_t(uint64_t(offs[k]) >> 32);
-        h_parts[4 * k + 2] = uint32_t(L);
-        h_parts[4 * k + 3] = uint32_t(L >> 32);
-        for (size_t i = 0; i < t; ++i) {
-            h_ptr[k * t + i] = reinterpret_cast<uint64_t>(base + offs[k] + i * cs);
-            h_len[k * t + i] = L;
+// Side stream of the speculative decode in cec_read_batch / cec_resilver_batch, with the
+// fork/join events that order it against the caller's stream: leased per call from a bounded
+// per-device pool (see CtxPool for why not thread_local).
+struct SideCtx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+    void destroy() {
+        if (stream) {
+            (void)hipStreamSynchronize(stream);
+            (void)hipStreamDestroy(stream);
         }
+        if (fork) (void)hipEventDestroy(fork);
+        if (join) (void)hipEventDestroy(join);
+        stream = nullptr;
+        fork = join = nullptr;
     }
-    h_units[n] = uint32_t(acc);
-    // A SHA-256 wave runs as long as its longest lane: hand the chains out longest first, so the
-    // 64 of a wave have similar lengths.  Digests land at their item's place whatever the order.
-    std::vector<uint32_t> order(n);
-    for (size_t k = 0; k < n; ++k) order[k] = uint32_t(k);
-    std::stable_sort(order.begin(), order.end(),
-                     [&](uint32_t x, uint32_t y) { return lens[x] > lens[y]; });
-    for (size_t q = 0; q < n; ++q)
-        for (size_t i = 0; i < t; ++i) h_ord[q * t + i] = uint32_t(order[q] * t + i);
-    HIP_TRY(hipMemcpyAsync(sc.dev(), sc.host(), bytes, hipMemcpyHostToDevice, s));
-    RaggedParams a{};
-    a.base = base;
-    a.pat = drec;
-    a.units = reinterpret_cast<const uint32_t*>(sc.dev() + o_units);
-    a.parts = reinterpret_cast<const uint32_t*>(sc.dev() + o_parts);
-    a.n_parts = uint32_t(n);
-    a.total_units = uint32_t(units);
-    a.d = uint32_t(c->d);
-    a.n_rows = uint32_t(c->p);
-    HIP_TRY(launch_rs_encode_ragged(a, s));
-    ShaParams h{};
-    h.ptrs = reinterpret_cast<const uint64_t*>(sc.dev());
-    h.lens = reinterpret_cast<const uint64_t*>(sc.dev() + o_len);
-    h.n_parts = uint32_t(items);
-    h.n_chunks = 1;
-    h.digests = digests;
-    h.items = reinterpret_cast<const uint32_t*>(sc.dev() + o_ord);
-    h.n_items = uint32_t(items);
-    HIP_TRY(launch_sha256(h, true, s));
-    return CEC_OK;
-}
+};
 
-// Arenas of cec_parts_encode: one per call in flight (pinned staging + device buffer + stream,
-// as the coalescer's leaders take), kept for the life of the process.
-class ArenaPool {
+class SidePool {
    public:
-    Arena* take(int device) {
+    std::unique_ptr<SideCtx> take(int device) {
         std::lock_guard<std::mutex> lk(mu_);
-        auto& v = free_[device];
+        auto& v = idle_[device];
         if (v.empty()) {
-            all_.push_back(std::make_unique<Arena>());
-            all_.back()->dev.device = device;
-            return all_.back().get();
+            auto c = std::make_unique<SideCtx>();
+            c->device = device;
+            return c;
         }
-        Arena* a = v.back();
+        auto c = std::move(v.back());
         v.pop_back();
-        return a;
+        return c;
     }
-    void give(int device, Arena* a) {
-        std::lock_guard<std::mutex> lk(mu_);
-        free_[device].push_back(a);
+    void give(std::unique_ptr<SideCtx> c) {
+        if (!c) return;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            auto& v = idle_[c->device];
+            if (v.size() < kMaxIdleCtx) {
+                v.push_back(std::move(c));
+                return;
+            }
+        }
+        c->destroy();
     }
 
    private:
     std::mutex mu_;
-    std::vector<std::unique_ptr<Arena>> all_;
-    std::map<int, std::vector<Arena*>> free_;
+    std::map<int, std::vector<std::unique_ptr<SideCtx>>> idle_;
 };
 
-ArenaPool& ragged_arenas() {
-    static ArenaPool* pool = new ArenaPool();
+SidePool& side_pool() {
+    static SidePool* pool = new SidePool();  // leaked: see ctx_pool()
     return *pool;
 }
 
-// fn(k) for k < n on up to 8 threads: one per 16 MiB of `bytes` moved, so a call of a few small
-// parts never starts one.
-template <typename Fn>
-void for_parts(size_t n, size_t bytes, Fn fn) {
-    const size_t nt = std::min<size_t>({size_t(8), bytes / (size_t(16) << 20), n});
-    if (nt <= 1) {
-        for (size_t k = 0; k < n; ++k) fn(k);
-        return;
+class SideLease {
+   public:
+    SideLease() = default;
+    SideLease(const SideLease&) = delete;
+    SideLease& operator=(const SideLease&) = delete;
+    ~SideLease() { side_pool().give(std::move(c_)); }
+    int acquire() {
+        int dev = 0;
+        CEC_TRY(current_device(&dev));
+        c_ = side_pool().take(dev);
+        if (!c_->stream) HIP_TRY(hipStreamCreateWithFlags(&c_->stream, hipStreamNonBlocking));
+        if (!c_->fork) HIP_TRY(hipEventCreateWithFlags(&c_->fork, hipEventDisableTiming));
+        if (!c_->join) HIP_TRY(hipEventCreateWithFlags(&c_->join, hipEventDisableTiming));
+        return CEC_OK;
     }
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-        for (size_t k; (k = next.fetch_add(1, std::memory_order_relaxed)) < n;) fn(k);
-    };
-    std::vector<std::thread> th;
-    for (size_t i = 1; i < nt; ++i) th.emplace_back(work);
-    work();
-    for (auto& x : th) x.join();
-}
+    SideCtx* get() { return c_.get(); }
 
-// One round of cec_parts_encode: parts [0, n) of these arrays, packed, moved, encoded and hashed
-// together, results copied out.
-int parts_round(cec_codec* c, Arena& a, const uint8_t* const* bufs, const size_t* lengths,
-                size_t n, uint8_t* const* parity_outs, uint8_t* digests_out,
-                const size_t* chunk_lens) {
-    const size_t d = c->d, p = c->p, t = d + p;
-    std::vector<size_t> offs(n);
-    size_t total = 0;
-    CEC_TRY(ragged_layout(t, chunk_lens, n, offs.data(), &total));
-    uint64_t units = 0;
-    CEC_TRY(ragged_check(c, nullptr, offs.data(), chunk_lens, n, &units));
-    const size_t cap = coalesce_max_bytes();
-    CEC_TRY(a.in.reserve(total, cap / d * t + t * kRaggedAlign));
-    CEC_TRY(a.out.reserve(n * t * 32, cap / 8));
-    const size_t dig_bytes = round_up(n * t * 32, kChunkAlign);
-    CEC_TRY(ctx_reserve(a.dev, dig_bytes + total));
-    uint8_t* ddig = a.dev.dbuf;
-    uint8_t* dbase = a.dev.dbuf + dig_bytes;
-    uint8_t* stage = a.in.ptr;
-    size_t in_bytes = 0;
-    for (size_t k = 0; k < n; ++k) in_bytes += lengths[k];
-    // data chunk j of part k = bytes [j*L, (j+1)*L) of the caller's `length` bytes, zeros behind
-    for_parts(n, in_bytes, [&](size_t k) {
-        const size_t L = chunk_lens[k], cs = round_up(L, kRaggedAlign), len = lengths[k];
-        for (size_t j = 0; j < d; ++j) {
-            uint8_t* dst = stage + offs[k] + j * cs;
-            const size_t b0 = j * L, have = b0 < len ? std::min(L, len - b0) : 0;
-            if (have) std::memcpy(dst, bufs[k] + b0, have);
-            if (have < L) std::memset(dst + have, 0, L - have);
-        }
-    });
-    hipStream_t s = a.dev.stream;
-    const size_t last_cs = round_up(chunk_lens[n - 1], kRaggedAlign);
-    HIP_TRY(hipMemcpyAsync(dbase, stage, offs[n - 1] + d * last_cs, hipMemcpyHostToDevice, s));
-    CEC_TRY(ragged_launch(c, dbase, offs.data(), chunk_lens, n, units, ddig, s));
-    // The parity spans come back into the staging at their own offsets.  Neighbouring parts share
-    // a copy (the data chunks between their parity travel along) until the data in between is
-    // worth a copy call of its own (256 KiB: a few microseconds of the link either way).
-    constexpr size_t kGap = size_t(256) << 10;
-    for (size_t k = 0; k < n;) {
-        const size_t cs0 = round_up(chunk_lens[k], kRaggedAlign);
-        const size_t from = offs[k] + d * cs0;
-        size_t to = offs[k] + t * cs0;
-        size_t q = k + 1;
-        for (; q < n; ++q) {
-            const size_t cs = round_up(chunk_lens[q], kRaggedAlign);
-            if (d * cs >= kGap) break;
-            to = offs[q] + t * cs;
-        }
-        HIP_TRY(hipMemcpyAsync(stage + from, dbase + from, to - from, hipMemcpyDeviceToHost, s));
-        k = q;
-    }
-    HIP_TRY(hipMemcpyAsync(a.out.ptr, ddig, n * t * 32, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    size_t out_bytes = 0;
-    for (size_t k = 0; k < n; ++k) out_bytes += p * chunk_lens[k];
-    for_parts(n, out_bytes, [&](size_t k) {
-        const size_t L = chunk_lens[k], cs = round_up(L, kRaggedAlign);
-        for (size_t i = 0; i < p; ++i)
-            std::memcpy(parity_outs[k] + i * L, stage + offs[k] + (d + i) * cs, L);
-    });
-    std::memcpy(digests_out, a.out.ptr, n * t * 32);
+   private:
+    std::unique_ptr<SideCtx> c_;
+};
+
+// LDS each speculative-decode block reserves.  100 KiB keeps decode blocks off the CUs holding
+// SHA workgroups (>= 64 KiB each) and runs one per free CU: a low-intensity decode spread under
+// the SHA chains.  Measured on the c3r read (4 096 parts, RS(10,4), d loaded,
+// profiles/r1y_c3r_summary.md): 43.2 ms vs 45.3 (65 KiB: two per free CU) vs 46.5 (none: decode
+// everywhere, done in 17 ms, but the SHA chains slow from 42.6 to 46.4 ms beside it) vs 53.0 ms
+// without speculation.
+constexpr uint32_t kDecodeLds = 100u * 1024u;
+
+// DataVerifier::verify of the loaded chunks (present_host[k*t + i] != 0) of a batch: ok[item] =
+// digest matches (ok of the others is left as is).  The loaded chunks are packed into a
+// compacted item list, so a read with d of d+p chunks loaded runs d/(d+p) of the waves of a
+// strided launch with skipped lanes (a SHA wave costs the same with idle lanes), which leaves
+// SIMDs free for the decode running beside it.
+int verify_loaded(const cec_part_batch* b, size_t t, const uint8_t* present_host,
+                  const uint8_t* expected, uint8_t* ok, hipStream_t s) {
+    const size_t n = b->n_parts * t;
+    std::vector<uint32_t> items;
+    items.reserve(n);
+    for (size_t i = 0; i < n; ++i)
+        if (needs_hash(present_host[i])) items.push_back(uint32_t(i));
+    if (items.empty()) return CEC_OK;
+    const uint32_t n_items = uint32_t(items.size());
+    uint32_t* ditems = nullptr;
+    Scratch sc;  // released on s behind the verification launch
+    CEC_TRY(upload_words(items, s, sc, &ditems));
+    ShaParams h{};
+    h.base = b->base;
+    h.part_stride = b->part_stride;
+    h.chunk_stride = b->chunk_stride;
+    h.len = b->chunk_len;
+    h.n_parts = uint32_t(b->n_parts);
+    h.first_chunk = 0;
+    h.n_chunks = uint32_t(t);
+    h.expected = expected;
+    h.ok = ok;
+    h.items = ditems;
+    h.n_items = n_items;
+    hipError_t e = launch_sha256(h, aligned16(b->base, b->part_stride, b->chunk_stride), s);
+    if (e != hipSuccess) return hip_fail(e, "launch_sha256 (verify)");
     return CEC_OK;
 }
 
-int batch_ok(const cec_part_batch* b) {
-    if (!b || !b->base) return CEC_ERR_INVALID_ARGUMENT;
-    return CEC_OK;
+// Shared body of cec_read_batch / cec_resilver_batch.  The result is the reference's: rebuild
+// from the first d VERIFIED chunks of each part (file_part.rs:98-128 keeps only chunks whose hash
+// matched).  The decode does not wait for the verdict: the pattern is known from the loaded
+// flags, so it runs speculatively from the first d LOADED chunks on a side stream, concurrently
+// with the SHA-256 verification (which leaves 384 of 1 024 SIMDs idle on a 4 096-part RS(10,4)
+// read: 40 960 chains = 640 waves).  Both only read the loaded chunks and the decode writes only
+// chunks that were not loaded, so they do not race.  When every loaded chunk verifies (the
+// common case) the speculative result is the final one; a part with a loaded chunk that failed
+// is decoded again from its verified chunks, which rewrites every chunk the first pass wrote.
+int verify_then_reconstruct(const cec_codec* c, const cec_part_batch* b,
+                            const uint8_t* present_host, const uint8_t* expected,
+                            uint8_t* verified_host, int* part_status, bool data_only,
+                            hipStream_t s) {
+    if (!c || !present_host || !expected || !verified_host || !part_status)
+        return CEC_ERR_INVALID_ARGUMENT;
+    CEC_TRY(batch_ok(b));
+    if (b->n_parts == 0) return CEC_OK;
+    if (b->chunk_len == 0) return CEC_EMPTY_SHARD;
+    const size_t d = c->d, t = c->d + c->p, n = b->n_parts * t;
+    if (n > 0xFFFFFFFFull) return CEC_ERR_INVALID_ARGUMENT;
+    Scratch ok_buf;  // device verification flags, released on s behind the readback
+    CEC_TRY(ok_buf.acquire(n, s));
+    uint8_t* ok = ok_buf.dev();
+    HIP_TRY(hipMemsetAsync(ok, 0, n, s));
+    // Fork point: the caller's work on s so far (the chunks).  The side stream waits for it and
+    // s later waits for the side stream's join, each on an event recorded before the wait is
+    // queued: safe in shared in-order hardware queues (the rule of the coalescer's early parity
+    // download above).
+    SideLease lease;
+    CEC_TRY(lease.acquire());
+    SideCtx* side = lease.get();
+    HIP_TRY(hipEventRecord(side->fork, s));
+    // Verification goes first so its long-lived workgroups claim their CUs (one or two per CU)
+    // before the decode's blocks take the CUs left free.
+    int st = verify_loaded(b, t, present_host, expected, ok, s);
+    if (st == CEC_OK) {
+        // Parts with fewer than d loaded chunks cannot be decoded: left out (mask all ones).
+        std::vector<uint8_t> spec(present_host, present_host + n);
+        for (size_t k = 0; k < b->n_parts; ++k) {
+            const size_t loaded =
+                size_t(std::count_if(spec.begin() + k * t, spec.begin() + (k + 1) * t,
+                                     [](uint8_t f) { return f != 0; }));
+            if (loaded < d) std::fill(spec.begin() + k * t, spec.begin() + (k + 1) * t, uint8_t(1));
+        }
+        hipError_t e = hipStreamWaitEvent(side->stream, side->fork, 0);
+        if (e != hipSuccess) st = hip_fail(e, "speculative decode fork");
+        if (st == CEC_OK)
+            st = reconstruct_batch(c, b, spec.data(), data_only ? 1 : 0, side->stream,
+                                   kDecodeLds);
+        if (st == CEC_OK) {
+            e = hipEventRecord(side->join, side->stream);
+            if (e == hipSuccess) e = hipStreamWaitEvent(s, side->join, 0);
+            if (e != hipSuccess) st = hip_fail(e, "speculative decode join");
+        }
+        // On failure nothing joins the side stream: let what it launched finish before the
+        // caller gets its buffers back.
+        if (st != CEC_OK) (void)hipStreamSynchronize(side->stream);
+    }
+    if (st == CEC_OK) {
+        hipError_t e = hipMemcpyAsync(verified_host, ok, n, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) st = hip_fail(e, "verify readback");
+    }
+    if (st != CEC_OK) return st;
+    // Decode again the parts whose loaded chunks did not all verify.
+    std::vector<uint8_t> pres;
+    if (!rebuild_mask(d, t, b->n_parts, present_host, verified_host, part_status, true, &pres))
+        return CEC_OK;
+    return reconstruct_batch(c, b, pres.data(), data_only ? 1 : 0, s, 0);
 }
 
 }  // namespace
@@ -1591,93 +1468,6 @@ int cec_part_encode(const cec_codec* cc, const uint8_t* data_buf, size_t length,
     return CEC_OK;
 }
 
-int cec_parts_encode(const cec_codec* cc, const uint8_t* const* data_bufs, const size_t* lengths,
-                     size_t n_parts, uint8_t* const* parity_outs, uint8_t* digests_out,
-                     size_t* chunksizes) {
-    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
-    if (n_parts == 0) return CEC_OK;
-    if (!data_bufs || !lengths || !parity_outs || !digests_out || !chunksizes)
-        return CEC_ERR_INVALID_ARGUMENT;
-    for (size_t k = 0; k < n_parts; ++k)
-        if (lengths[k] == 0) return CEC_EMPTY_SHARD;
-    for (size_t k = 0; k < n_parts; ++k)
-        if (!data_bufs[k] || !parity_outs[k]) return CEC_ERR_INVALID_ARGUMENT;
-    cec_codec* c = const_cast<cec_codec*>(cc);
-    const size_t d = c->d, t = c->d + c->p;
-    // Rounds of at most CEC_COALESCE_MAX_MIB of (padded) data chunks, a larger part alone; every
-    // round is checked before the first one runs, so an error leaves the outputs untouched.
-    std::vector<size_t> L(n_parts), round_end;
-    const size_t cap = coalesce_max_bytes();
-    size_t bytes = 0, first = 0;
-    for (size_t k = 0; k < n_parts; ++k) {
-        L[k] = (lengths[k] - 1) / d + 1;
-        size_t cs = 0, b = 0;
-        if (!ragged_stride(L[k], &cs) || __builtin_mul_overflow(d, cs, &b))
-            return CEC_ERR_INVALID_ARGUMENT;
-        if (k > first && (b > cap || bytes > cap - b)) {
-            round_end.push_back(k);
-            first = k;
-            bytes = 0;
-        }
-        bytes += std::min(b, cap);
-    }
-    round_end.push_back(n_parts);
-    {
-        std::vector<size_t> offs(n_parts);
-        size_t k0 = 0;
-        for (size_t k1 : round_end) {
-            size_t total = 0;
-            uint64_t units = 0;
-            CEC_TRY(ragged_layout(t, L.data() + k0, k1 - k0, offs.data(), &total));
-            CEC_TRY(ragged_check(c, nullptr, offs.data(), L.data() + k0, k1 - k0, &units));
-            k0 = k1;
-        }
-    }
-    int dev = 0;
-    CEC_TRY(current_device(&dev));
-    Arena* arena = ragged_arenas().take(dev);
-    int st = CEC_OK;
-    size_t k0 = 0;
-    for (size_t k1 : round_end) {
-        st = parts_round(c, *arena, data_bufs + k0, lengths + k0, k1 - k0, parity_outs + k0,
-                         digests_out + k0 * t * 32, L.data() + k0);
-        if (st != CEC_OK) break;
-        k0 = k1;
-    }
-    if (st != CEC_OK && arena->dev.stream) {  // nothing of a failed round stays in flight
-        (void)hipStreamSynchronize(arena->dev.stream);
-        (void)hipGetLastError();
-    }
-    ragged_arenas().give(dev, arena);
-    if (st != CEC_OK) return st;
-    for (size_t k = 0; k < n_parts; ++k) chunksizes[k] = L[k];
-    return CEC_OK;
-}
-
-size_t cec_ragged_stride(size_t chunk_len) {
-    size_t cs = 0;
-    return ragged_stride(chunk_len, &cs) ? cs : 0;
-}
-
-int cec_ragged_layout(size_t total_shards, const size_t* chunk_lens, size_t n_parts,
-                      size_t* part_offsets, size_t* total_bytes) {
-    if (!total_bytes || total_shards == 0) return CEC_ERR_INVALID_ARGUMENT;
-    if (n_parts && (!chunk_lens || !part_offsets)) return CEC_ERR_INVALID_ARGUMENT;
-    return ragged_layout(total_shards, chunk_lens, n_parts, part_offsets, total_bytes);
-}
-
-int cec_encode_hash_ragged(const cec_codec* cc, uint8_t* base, const size_t* part_offsets,
-                           const size_t* chunk_lens, size_t n_parts, uint8_t* digests,
-                           void* stream) {
-    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
-    if (n_parts == 0) return CEC_OK;
-    if (!base || !part_offsets || !chunk_lens || !digests) return CEC_ERR_INVALID_ARGUMENT;
-    uint64_t units = 0;
-    CEC_TRY(ragged_check(cc, base, part_offsets, chunk_lens, n_parts, &units));
-    return ragged_launch(const_cast<cec_codec*>(cc), base, part_offsets, chunk_lens, n_parts,
-                         units, digests, static_cast<hipStream_t>(stream));
-}
-
 void cec_coalesce_stats(uint64_t* calls, uint64_t* launches) {
     coalesce_stats(calls, launches);
 }
@@ -1760,194 +1550,6 @@ int cec_encode_hash_batch(const cec_codec* cc, const cec_part_batch* b, uint8_t*
     return CEC_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// The host half of a batched reconstruct, shared by the uniform and the ragged layout: the parts
-// that need a rebuild grouped by erasure pattern, one decode record per pattern, the patterns
-// bucketed by output-row count, and per bucket the launch lists.
-// words = [records...][launch lists: part_ids..., part_pat...].  Patterns of up to max_var_rows()
-// rows (every RS(10,4) erasure set) share ONE launch that dispatches on each part's row count;
-// wider patterns get a row-group launch per row count.
-struct DecodePlan {
-    struct Launch {
-        uint32_t n_out;  // 0: per-part row counts (the shared launch)
-        size_t ids;      // word offset of part_ids; part_pat follows at ids + count
-        size_t count;
-    };
-    std::vector<uint32_t> words;
-    std::vector<Launch> launches;  // empty: nothing to rebuild
-    uint32_t var_rows = 0;         // the shared launch's widest pattern: its kernel's row class
-};
-
-// CEC_TOO_FEW_SHARDS_PRESENT when a part has some but fewer than d chunks present.
-int check_present(size_t d, size_t t, const uint8_t* present, size_t n_parts) {
-    for (size_t k = 0; k < n_parts; ++k) {
-        size_t n_present = 0;
-        for (size_t i = 0; i < t; ++i) n_present += present[k * t + i] ? 1 : 0;
-        if (n_present != t && n_present < d) return CEC_TOO_FEW_SHARDS_PRESENT;
-    }
-    return CEC_OK;
-}
-
-void plan_decode(cec_codec* c, const uint8_t* present, size_t n_parts, bool data_only,
-                 DecodePlan* plan) {
-    const size_t t = c->d + c->p;
-    // Group parts by pattern; bucket patterns by output-row count.
-    std::map<PatternKey, std::pair<uint32_t, std::vector<uint32_t>>> groups;  // key -> (n_out, parts)
-    for (size_t k = 0; k < n_parts; ++k) {
-        const uint8_t* pr = present + k * t;
-        size_t n_present = 0;
-        for (size_t i = 0; i < t; ++i) n_present += pr[i] ? 1 : 0;
-        if (n_present == t) continue;
-        PatternKey key = make_key(pr, t, data_only);
-        auto& g = groups[key];
-        g.second.push_back(uint32_t(k));
-    }
-    std::vector<uint32_t>& words = plan->words;
-    std::map<uint32_t, std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> buckets;
-    for (auto& kv : groups) {
-        auto rec = c->decode_record(kv.first);
-        const uint32_t n_out = (*rec)[0];
-        if (n_out == 0) continue;  // data_only: only parity missing, nothing to do
-        if (n_out <= max_var_rows()) plan->var_rows = std::max(plan->var_rows, n_out);
-        const uint32_t off = uint32_t(words.size());
-        words.insert(words.end(), rec->begin(), rec->end());
-        auto& bk = buckets[n_out <= max_var_rows() ? 0u : n_out];  // 0 = the shared launch
-        for (uint32_t part : kv.second.second) {
-            bk.first.push_back(part);
-            bk.second.push_back(off);
-        }
-    }
-    for (auto& kv : buckets) {
-        plan->launches.push_back({kv.first, words.size(), kv.second.first.size()});
-        words.insert(words.end(), kv.second.first.begin(), kv.second.first.end());
-        words.insert(words.end(), kv.second.second.begin(), kv.second.second.end());
-    }
-}
-
-// The shared launch's row class must cover every record it lists (the kernels skip a wider
-// pattern without writing its chunks: kernels.hpp launch_rs_apply_var).
-int check_row_class(const DecodePlan& plan, const DecodePlan::Launch& l, uint32_t n_rows,
-                    const char* who) {
-    const uint32_t* pat_off = plan.words.data() + l.ids + l.count;
-    for (size_t q = 0; q < l.count; ++q)
-        if (plan.words[pat_off[q]] == 0 || plan.words[pat_off[q]] > n_rows) {
-            g_last_error = std::string(who) + ": a listed pattern is wider than its launch";
-            return CEC_ERR_INVALID_ARGUMENT;
-        }
-    return CEC_OK;
-}
-
-// cec_reconstruct_batch with each decode block reserving lds_reserve bytes of LDS (see
-// ApplyParams::lds_reserve).
-int reconstruct_batch(const cec_codec* cc, const cec_part_batch* b, const uint8_t* present,
-                      int data_only, void* stream, uint32_t lds_reserve) {
-    if (!cc || !present) return CEC_ERR_INVALID_ARGUMENT;
-    CEC_TRY(batch_ok(b));
-    if (b->n_parts == 0) return CEC_OK;
-    if (b->chunk_len == 0) return CEC_EMPTY_SHARD;
-    if (b->n_parts > 0xFFFFFFFFull) return CEC_ERR_INVALID_ARGUMENT;
-    cec_codec* c = const_cast<cec_codec*>(cc);
-    const size_t d = c->d, t = c->d + c->p;
-    // Validate every part before launching anything.
-    CEC_TRY(check_present(d, t, present, b->n_parts));
-    DecodePlan plan;
-    plan_decode(c, present, b->n_parts, data_only != 0, &plan);
-    if (plan.launches.empty()) return CEC_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint32_t* dwords = nullptr;
-    Scratch scratch;  // released on s behind the launches below
-    CEC_TRY(upload_words(plan.words, s, scratch, &dwords));
-    const bool vec = aligned16(b->base, b->part_stride, b->chunk_stride);
-    int status = CEC_OK;
-    for (size_t i = 0; i < plan.launches.size() && status == CEC_OK; ++i) {
-        const DecodePlan::Launch& l = plan.launches[i];
-        ApplyParams a{};
-        a.base = b->base;
-        a.part_stride = b->part_stride;
-        a.chunk_stride = b->chunk_stride;
-        a.len = b->chunk_len;
-        a.pat = dwords;
-        a.part_ids = dwords + l.ids;
-        a.part_pat = dwords + l.ids + l.count;
-        a.n_parts = uint32_t(l.count);
-        a.d = uint32_t(d);
-        a.n_rows = l.n_out ? l.n_out : plan.var_rows;
-        if (!l.n_out) CEC_TRY(check_row_class(plan, l, a.n_rows, "reconstruct_batch"));
-        a.lds_reserve = lds_reserve;
-        hipError_t e = l.n_out ? launch_rs_apply(a, vec, s) : launch_rs_apply_var(a, vec, s);
-        if (e != hipSuccess) status = hip_fail(e, "launch_rs_apply");
-    }
-    return status;
-}
-
-// The launches of cec_reconstruct_ragged for a checked layout (ragged_check) and checked flags
-// (check_present), on `s`.  Only the parts the plan lists reach the device: per launch a compact
-// {off, L} array and the prefix array over those parts' work units, behind the plan's words in
-// one scratch buffer whose page-locked mirror holds the copy of the host arrays.
-int reconstruct_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* lens,
-                       size_t n, const uint8_t* present, bool data_only, hipStream_t s) {
-    DecodePlan plan;
-    plan_decode(c, present, n, data_only, &plan);
-    if (plan.launches.empty()) return CEC_OK;
-    size_t listed = 0;
-    for (const auto& l : plan.launches) {
-        if (!l.n_out) CEC_TRY(check_row_class(plan, l, plan.var_rows, "reconstruct_ragged"));
-        listed += l.count;
-    }
-    // [plan words][per launch: units u32 x (count + 1), parts u32 x 4 count]
-    const size_t n_words = plan.words.size() + listed * 5 + plan.launches.size();
-    Scratch sc;  // released on s behind the launches below
-    CEC_TRY(sc.acquire(n_words * sizeof(uint32_t), s));
-    uint32_t* h = reinterpret_cast<uint32_t*>(sc.host());
-    uint32_t* dwords = reinterpret_cast<uint32_t*>(sc.dev());
-    std::memcpy(h, plan.words.data(), plan.words.size() * sizeof(uint32_t));
-    const uint64_t unit = ragged_unit_bytes();
-    std::vector<RaggedParams> params;
-    size_t at = plan.words.size();
-    for (const auto& l : plan.launches) {
-        const uint32_t* ids = plan.words.data() + l.ids;
-        uint32_t* h_units = h + at;
-        uint32_t* h_parts = h + at + l.count + 1;
-        uint64_t acc = 0;  // at most the whole batch's units, which ragged_check bounded
-        for (size_t q = 0; q < l.count; ++q) {
-            const uint64_t off = offs[ids[q]], L = lens[ids[q]];
-            h_units[q] = uint32_t(acc);
-            acc += (L - 1) / unit + 1;
-            h_parts[4 * q + 0] = uint32_t(off);
-            h_parts[4 * q + 1] = uint32_t(off >> 32);
-            h_parts[4 * q + 2] = uint32_t(L);
-            h_parts[4 * q + 3] = uint32_t(L >> 32);
-        }
-        h_units[l.count] = uint32_t(acc);
-        RaggedParams a{};
-        a.base = base;
-        a.pat = dwords;
-        a.units = dwords + at;
-        a.parts = dwords + at + l.count + 1;
-        a.part_pat = dwords + l.ids + l.count;
-        a.n_parts = uint32_t(l.count);
-        a.total_units = uint32_t(acc);
-        a.d = uint32_t(c->d);
-        a.n_rows = l.n_out ? l.n_out : plan.var_rows;
-        params.push_back(a);
-        at += l.count * 5 + 1;
-    }
-    HIP_TRY(hipMemcpyAsync(dwords, h, n_words * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    for (size_t i = 0; i < params.size(); ++i) {
-        const hipError_t e = plan.launches[i].n_out ? launch_rs_encode_ragged(params[i], s)
-                                                    : launch_rs_reconstruct_ragged(params[i], s);
-        if (e != hipSuccess) return hip_fail(e, "launch_rs_reconstruct_ragged");
-    }
-    return CEC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 int cec_reconstruct_batch(const cec_codec* c, const cec_part_batch* b, const uint8_t* present,
                           int data_only, void* stream) {
     return reconstruct_batch(c, b, present, data_only, stream, 0);
@@ -1975,224 +1577,6 @@ int cec_verify_batch(const cec_part_batch* b, size_t first_chunk, size_t n_chunk
     return CEC_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// Side stream of the speculative decode in cec_read_batch / cec_resilver_batch, with the
-// fork/join events that order it against the caller's stream: leased per call from a bounded
-// per-device pool (see CtxPool for why not thread_local).
-struct SideCtx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-    void destroy() {
-        if (stream) {
-            (void)hipStreamSynchronize(stream);
-            (void)hipStreamDestroy(stream);
-        }
-        if (fork) (void)hipEventDestroy(fork);
-        if (join) (void)hipEventDestroy(join);
-        stream = nullptr;
-        fork = join = nullptr;
-    }
-};
-
-class SidePool {
-   public:
-    std::unique_ptr<SideCtx> take(int device) {
-        std::lock_guard<std::mutex> lk(mu_);
-        auto& v = idle_[device];
-        if (v.empty()) {
-            auto c = std::make_unique<SideCtx>();
-            c->device = device;
-            return c;
-        }
-        auto c = std::move(v.back());
-        v.pop_back();
-        return c;
-    }
-    void give(std::unique_ptr<SideCtx> c) {
-        if (!c) return;
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            auto& v = idle_[c->device];
-            if (v.size() < kMaxIdleCtx) {
-                v.push_back(std::move(c));
-                return;
-            }
-        }
-        c->destroy();
-    }
-
-   private:
-    std::mutex mu_;
-    std::map<int, std::vector<std::unique_ptr<SideCtx>>> idle_;
-};
-
-SidePool& side_pool() {
-    static SidePool* pool = new SidePool();  // leaked: see ctx_pool()
-    return *pool;
-}
-
-class SideLease {
-   public:
-    SideLease() = default;
-    SideLease(const SideLease&) = delete;
-    SideLease& operator=(const SideLease&) = delete;
-    ~SideLease() { side_pool().give(std::move(c_)); }
-    int acquire() {
-        int dev = 0;
-        CEC_TRY(current_device(&dev));
-        c_ = side_pool().take(dev);
-        if (!c_->stream) HIP_TRY(hipStreamCreateWithFlags(&c_->stream, hipStreamNonBlocking));
-        if (!c_->fork) HIP_TRY(hipEventCreateWithFlags(&c_->fork, hipEventDisableTiming));
-        if (!c_->join) HIP_TRY(hipEventCreateWithFlags(&c_->join, hipEventDisableTiming));
-        return CEC_OK;
-    }
-    SideCtx* get() { return c_.get(); }
-
-   private:
-    std::unique_ptr<SideCtx> c_;
-};
-
-// LDS each speculative-decode block reserves.  100 KiB keeps decode blocks off the CUs holding
-// SHA workgroups (>= 64 KiB each) and runs one per free CU: a low-intensity decode spread under
-// the SHA chains.  Measured on the c3r read (4 096 parts, RS(10,4), d loaded,
-// profiles/r1y_c3r_summary.md): 43.2 ms vs 45.3 (65 KiB: two per free CU) vs 46.5 (none: decode
-// everywhere, done in 17 ms, but the SHA chains slow from 42.6 to 46.4 ms beside it) vs 53.0 ms
-// without speculation.
-constexpr uint32_t kDecodeLds = 100u * 1024u;
-
-// A loaded chunk is hashed unless the caller marked it CEC_PRESENT_VERIFIED (a read retry's
-// chunks that an earlier pass already verified).
-inline bool needs_hash(uint8_t f) { return f != 0 && f != CEC_PRESENT_VERIFIED; }
-
-// DataVerifier::verify of the loaded chunks (present_host[k*t + i] != 0) of a batch: ok[item] =
-// digest matches (ok of the others is left as is).  The loaded chunks are packed into a
-// compacted item list, so a read with d of d+p chunks loaded runs d/(d+p) of the waves of a
-// strided launch with skipped lanes (a SHA wave costs the same with idle lanes), which leaves
-// SIMDs free for the decode running beside it.
-int verify_loaded(const cec_part_batch* b, size_t t, const uint8_t* present_host,
-                  const uint8_t* expected, uint8_t* ok, hipStream_t s) {
-    const size_t n = b->n_parts * t;
-    std::vector<uint32_t> items;
-    items.reserve(n);
-    for (size_t i = 0; i < n; ++i)
-        if (needs_hash(present_host[i])) items.push_back(uint32_t(i));
-    if (items.empty()) return CEC_OK;
-    const uint32_t n_items = uint32_t(items.size());
-    uint32_t* ditems = nullptr;
-    Scratch sc;  // released on s behind the verification launch
-    CEC_TRY(upload_words(items, s, sc, &ditems));
-    ShaParams h{};
-    h.base = b->base;
-    h.part_stride = b->part_stride;
-    h.chunk_stride = b->chunk_stride;
-    h.len = b->chunk_len;
-    h.n_parts = uint32_t(b->n_parts);
-    h.first_chunk = 0;
-    h.n_chunks = uint32_t(t);
-    h.expected = expected;
-    h.ok = ok;
-    h.items = ditems;
-    h.n_items = n_items;
-    hipError_t e = launch_sha256(h, aligned16(b->base, b->part_stride, b->chunk_stride), s);
-    if (e != hipSuccess) return hip_fail(e, "launch_sha256 (verify)");
-    return CEC_OK;
-}
-
-// Shared body of cec_read_batch / cec_resilver_batch.  The result is the reference's: rebuild
-// from the first d VERIFIED chunks of each part (file_part.rs:98-128 keeps only chunks whose hash
-// matched).  The decode does not wait for the verdict: the pattern is known from the loaded
-// flags, so it runs speculatively from the first d LOADED chunks on a side stream, concurrently
-// with the SHA-256 verification (which leaves 384 of 1 024 SIMDs idle on a 4 096-part RS(10,4)
-// read: 40 960 chains = 640 waves).  Both only read the loaded chunks and the decode writes only
-// chunks that were not loaded, so they do not race.  When every loaded chunk verifies (the
-// common case) the speculative result is the final one; a part with a loaded chunk that failed
-// is decoded again from its verified chunks, which rewrites every chunk the first pass wrote.
-int verify_then_reconstruct(const cec_codec* c, const cec_part_batch* b,
-                            const uint8_t* present_host, const uint8_t* expected,
-                            uint8_t* verified_host, int* part_status, bool data_only,
-                            hipStream_t s) {
-    if (!c || !present_host || !expected || !verified_host || !part_status)
-        return CEC_ERR_INVALID_ARGUMENT;
-    CEC_TRY(batch_ok(b));
-    if (b->n_parts == 0) return CEC_OK;
-    if (b->chunk_len == 0) return CEC_EMPTY_SHARD;
-    const size_t d = c->d, t = c->d + c->p, n = b->n_parts * t;
-    if (n > 0xFFFFFFFFull) return CEC_ERR_INVALID_ARGUMENT;
-    Scratch ok_buf;  // device verification flags, released on s behind the readback
-    CEC_TRY(ok_buf.acquire(n, s));
-    uint8_t* ok = ok_buf.dev();
-    HIP_TRY(hipMemsetAsync(ok, 0, n, s));
-    // Fork point: the caller's work on s so far (the chunks).  The side stream waits for it and
-    // s later waits for the side stream's join, each on an event recorded before the wait is
-    // queued: safe in shared in-order hardware queues (the rule of the coalescer's early parity
-    // download above).
-    SideLease lease;
-    CEC_TRY(lease.acquire());
-    SideCtx* side = lease.get();
-    HIP_TRY(hipEventRecord(side->fork, s));
-    // Verification goes first so its long-lived workgroups claim their CUs (one or two per CU)
-    // before the decode's blocks take the CUs left free.
-    int st = verify_loaded(b, t, present_host, expected, ok, s);
-    if (st == CEC_OK) {
-        // Parts with fewer than d loaded chunks cannot be decoded: left out (mask all ones).
-        std::vector<uint8_t> spec(present_host, present_host + n);
-        for (size_t k = 0; k < b->n_parts; ++k) {
-            const size_t loaded =
-                size_t(std::count_if(spec.begin() + k * t, spec.begin() + (k + 1) * t,
-                                     [](uint8_t f) { return f != 0; }));
-            if (loaded < d) std::fill(spec.begin() + k * t, spec.begin() + (k + 1) * t, uint8_t(1));
-        }
-        hipError_t e = hipStreamWaitEvent(side->stream, side->fork, 0);
-        if (e != hipSuccess) st = hip_fail(e, "speculative decode fork");
-        if (st == CEC_OK)
-            st = reconstruct_batch(c, b, spec.data(), data_only ? 1 : 0, side->stream,
-                                   kDecodeLds);
-        if (st == CEC_OK) {
-            e = hipEventRecord(side->join, side->stream);
-            if (e == hipSuccess) e = hipStreamWaitEvent(s, side->join, 0);
-            if (e != hipSuccess) st = hip_fail(e, "speculative decode join");
-        }
-        // On failure nothing joins the side stream: let what it launched finish before the
-        // caller gets its buffers back.
-        if (st != CEC_OK) (void)hipStreamSynchronize(side->stream);
-    }
-    if (st == CEC_OK) {
-        hipError_t e = hipMemcpyAsync(verified_host, ok, n, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) st = hip_fail(e, "verify readback");
-    }
-    if (st != CEC_OK) return st;
-    for (size_t i = 0; i < n; ++i)  // verified by an earlier pass: trusted, not hashed again
-        if (present_host[i] == CEC_PRESENT_VERIFIED) verified_host[i] = 1;
-    // Parts with fewer than d verified chunks cannot be decoded (the reference's read returns
-    // the part short / resilver reports it).  Decode again the parts whose loaded chunks did
-    // not all verify.
-    std::vector<uint8_t> pres(n, uint8_t(1));
-    bool any = false;
-    for (size_t k = 0; k < b->n_parts; ++k) {
-        size_t good = 0;
-        bool bad = false;
-        for (size_t i = 0; i < t; ++i) {
-            good += verified_host[k * t + i] ? 1 : 0;
-            bad |= present_host[k * t + i] && !verified_host[k * t + i];
-        }
-        part_status[k] = good >= d ? CEC_OK : CEC_TOO_FEW_SHARDS_PRESENT;
-        if (good >= d && bad) {
-            std::copy(verified_host + k * t, verified_host + (k + 1) * t, pres.begin() + k * t);
-            any = true;
-        }
-    }
-    return any ? cec_reconstruct_batch(c, b, pres.data(), data_only ? 1 : 0, s) : CEC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 int cec_read_batch(const cec_codec* c, const cec_part_batch* b, const uint8_t* present,
                    const uint8_t* expected, uint8_t* verified, int* part_status, void* stream) {
     return verify_then_reconstruct(c, b, present, expected, verified, part_status, true,
@@ -2204,285 +1588,6 @@ int cec_resilver_batch(const cec_codec* c, const cec_part_batch* b, const uint8_
                        void* stream) {
     return verify_then_reconstruct(c, b, present, expected, verified, part_status, false,
                                    static_cast<hipStream_t>(stream));
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// Ragged read (cec_reconstruct_ragged, cec_read_ragged, cec_resilver_ragged, cec_parts_read)
-// ------------------------------------------------------------------------------------------
-namespace {
-
-// Shared body of cec_read_ragged / cec_resilver_ragged for a checked layout: on `s` the SHA-256
-// list launch in verify mode over the chunks that need hashing (longest first, so the 64 chains of
-// a wave have similar lengths; ok and expected indexed by k*(d+p)+i), the readback of the flags
-// (the one wait), then the rebuild of every decodable part from its first d verified chunks.
-// No speculative decode beside the verification: the chains of a ragged batch are short and
-// nobody has measured whether it pays (not built).
-int read_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* lens, size_t n,
-                const uint8_t* present, const uint8_t* expected, uint8_t* verified,
-                int* part_status, bool data_only, hipStream_t s) {
-    const size_t d = c->d, t = c->d + c->p, items = n * t;
-    std::vector<uint32_t> order;
-    for (size_t i = 0; i < items; ++i)
-        if (needs_hash(present[i])) order.push_back(uint32_t(i));
-    std::stable_sort(order.begin(), order.end(),
-                     [&](uint32_t x, uint32_t y) { return lens[x / t] > lens[y / t]; });
-    // [ptrs u64 x items][lens u64 x items][order u32 x hashed][ok u8 x items]
-    const size_t o_len = items * 8, o_ord = o_len + items * 8, o_ok = o_ord + order.size() * 4,
-                 bytes = o_ok + items;
-    Scratch sc;  // released on s behind the readback
-    CEC_TRY(sc.acquire(bytes, s));
-    uint8_t* ok = sc.dev() + o_ok;
-    HIP_TRY(hipMemsetAsync(ok, 0, items, s));
-    if (!order.empty()) {
-        uint64_t* h_ptr = reinterpret_cast<uint64_t*>(sc.host());
-        uint64_t* h_len = reinterpret_cast<uint64_t*>(sc.host() + o_len);
-        for (uint32_t it : order) {  // unlisted items are never looked at
-            const size_t k = it / t, i = it % t;
-            const size_t cs = (lens[k] + kRaggedAlign - 1) / kRaggedAlign * kRaggedAlign;
-            h_ptr[it] = reinterpret_cast<uint64_t>(base + offs[k] + i * cs);
-            h_len[it] = lens[k];
-        }
-        std::memcpy(sc.host() + o_ord, order.data(), order.size() * 4);
-        HIP_TRY(hipMemcpyAsync(sc.dev(), sc.host(), o_ok, hipMemcpyHostToDevice, s));
-        ShaParams h{};
-        h.ptrs = reinterpret_cast<const uint64_t*>(sc.dev());
-        h.lens = reinterpret_cast<const uint64_t*>(sc.dev() + o_len);
-        h.n_parts = uint32_t(items);
-        h.n_chunks = 1;
-        h.expected = expected;
-        h.ok = ok;
-        h.items = reinterpret_cast<const uint32_t*>(sc.dev() + o_ord);
-        h.n_items = uint32_t(order.size());
-        const hipError_t e = launch_sha256(h, true, s);
-        if (e != hipSuccess) return hip_fail(e, "launch_sha256 (ragged verify)");
-    }
-    // the flags come back through the mirror, behind the words that went up
-    HIP_TRY(hipMemcpyAsync(sc.host() + o_ok, ok, items, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    std::memcpy(verified, sc.host() + o_ok, items);
-    for (size_t i = 0; i < items; ++i)  // verified by an earlier pass: trusted, not hashed again
-        if (present[i] == CEC_PRESENT_VERIFIED) verified[i] = 1;
-    // Parts with fewer than d verified chunks cannot be decoded: all ones, so the plan skips them.
-    std::vector<uint8_t> pres(items, uint8_t(1));
-    for (size_t k = 0; k < n; ++k) {
-        size_t good = 0;
-        for (size_t i = 0; i < t; ++i) good += verified[k * t + i] ? 1 : 0;
-        part_status[k] = good >= d ? CEC_OK : CEC_TOO_FEW_SHARDS_PRESENT;
-        if (good >= d) std::copy(verified + k * t, verified + (k + 1) * t, pres.begin() + k * t);
-    }
-    return reconstruct_ragged(c, base, offs, lens, n, pres.data(), data_only, s);
-}
-
-// Every check of cec_read_ragged / cec_resilver_ragged, then the work.
-int read_ragged_checked(const cec_codec* cc, uint8_t* base, const size_t* offs, const size_t* lens,
-                        size_t n, const uint8_t* present, const uint8_t* expected,
-                        uint8_t* verified, int* part_status, bool data_only, void* stream) {
-    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
-    if (n == 0) return CEC_OK;
-    if (!base || !offs || !lens || !present || !expected || !verified || !part_status)
-        return CEC_ERR_INVALID_ARGUMENT;
-    uint64_t units = 0;
-    CEC_TRY(ragged_check(cc, base, offs, lens, n, &units));
-    int dev = 0;
-    CEC_TRY(current_device(&dev));
-    return read_ragged(const_cast<cec_codec*>(cc), base, offs, lens, n, present, expected,
-                       verified, part_status, data_only, static_cast<hipStream_t>(stream));
-}
-
-// Copies of the byte ranges [from[q], to[q]) (ascending, disjoint) between the staging and the
-// device arena, which share their offsets.  Neighbouring ranges share one copy, with what lies
-// between them travelling along, until the gap is worth a copy call of its own (parts_round's
-// 256 KiB rule).
-int copy_spans(uint8_t* stage, uint8_t* dbase, const std::vector<std::pair<size_t, size_t>>& spans,
-               bool to_device, hipStream_t s) {
-    constexpr size_t kGap = size_t(256) << 10;
-    for (size_t q = 0; q < spans.size();) {
-        const size_t from = spans[q].first;
-        size_t to = spans[q].second;
-        for (++q; q < spans.size() && spans[q].first - to < kGap; ++q) to = spans[q].second;
-        if (to_device)
-            HIP_TRY(hipMemcpyAsync(dbase + from, stage + from, to - from, hipMemcpyHostToDevice, s));
-        else
-            HIP_TRY(hipMemcpyAsync(stage + from, dbase + from, to - from, hipMemcpyDeviceToHost, s));
-    }
-    return CEC_OK;
-}
-
-// Whether the call fills slot i of a part when it is not among the verified chunks.
-inline bool fills_slot(size_t i, size_t d, bool data_only) { return i < d || !data_only; }
-
-// One round of cec_parts_read: parts [0, n) of these arrays.  The loaded chunks are packed into
-// the arena in the cec_ragged_layout layout and moved up, verified and rebuilt as in
-// cec_read_ragged, and only the rebuilt chunks come back, into the caller's slots.
-int parts_read_round(cec_codec* c, Arena& a, uint8_t* const* shards, const size_t* chunk_lens,
-                     size_t n, const uint8_t* present, const uint8_t* expected, bool data_only,
-                     uint8_t* verified, int* part_status) {
-    const size_t d = c->d, t = c->d + c->p, items = n * t;
-    std::vector<size_t> offs(n);
-    size_t total = 0;
-    CEC_TRY(ragged_layout(t, chunk_lens, n, offs.data(), &total));
-    const size_t cap = coalesce_max_bytes();
-    CEC_TRY(a.in.reserve(total, cap / d * t + t * kRaggedAlign));
-    CEC_TRY(a.out.reserve(items * 32, cap / 8));
-    const size_t dig_bytes = round_up(items * 32, kChunkAlign);
-    CEC_TRY(ctx_reserve(a.dev, dig_bytes + total));
-    uint8_t* dexp = a.dev.dbuf;
-    uint8_t* dbase = a.dev.dbuf + dig_bytes;
-    uint8_t* stage = a.in.ptr;
-    hipStream_t s = a.dev.stream;
-    std::vector<std::pair<size_t, size_t>> spans;
-    size_t in_bytes = 0;
-    for (size_t k = 0; k < n; ++k) {
-        const size_t L = chunk_lens[k], cs = round_up(L, kRaggedAlign);
-        for (size_t i = 0; i < t; ++i)
-            if (present[k * t + i]) {
-                spans.emplace_back(offs[k] + i * cs, offs[k] + i * cs + L);
-                in_bytes += L;
-            }
-    }
-    for_parts(n, in_bytes, [&](size_t k) {
-        const size_t L = chunk_lens[k], cs = round_up(L, kRaggedAlign);
-        for (size_t i = 0; i < t; ++i)
-            if (present[k * t + i]) std::memcpy(stage + offs[k] + i * cs, shards[k * t + i], L);
-    });
-    std::memcpy(a.out.ptr, expected, items * 32);
-    HIP_TRY(hipMemcpyAsync(dexp, a.out.ptr, items * 32, hipMemcpyHostToDevice, s));
-    CEC_TRY(copy_spans(stage, dbase, spans, true, s));
-    CEC_TRY(read_ragged(c, dbase, offs.data(), chunk_lens, n, present, dexp, verified,
-                        part_status, data_only, s));
-    // what the rebuild wrote: in a decodable part, every slot of the mode that did not verify
-    spans.clear();
-    size_t out_bytes = 0;
-    for (size_t k = 0; k < n; ++k) {
-        if (part_status[k] != CEC_OK) continue;
-        const size_t L = chunk_lens[k], cs = round_up(L, kRaggedAlign);
-        for (size_t i = 0; i < t; ++i)
-            if (!verified[k * t + i] && fills_slot(i, d, data_only)) {
-                spans.emplace_back(offs[k] + i * cs, offs[k] + i * cs + L);
-                out_bytes += L;
-            }
-    }
-    CEC_TRY(copy_spans(stage, dbase, spans, false, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for_parts(n, out_bytes, [&](size_t k) {
-        if (part_status[k] != CEC_OK) return;
-        const size_t L = chunk_lens[k], cs = round_up(L, kRaggedAlign);
-        for (size_t i = 0; i < t; ++i)
-            if (!verified[k * t + i] && fills_slot(i, d, data_only))
-                std::memcpy(shards[k * t + i], stage + offs[k] + i * cs, L);
-    });
-    return CEC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int cec_reconstruct_ragged(const cec_codec* cc, uint8_t* base, const size_t* part_offsets,
-                           const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
-                           int data_only, void* stream) {
-    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
-    if (n_parts == 0) return CEC_OK;
-    if (!base || !part_offsets || !chunk_lens || !present) return CEC_ERR_INVALID_ARGUMENT;
-    uint64_t units = 0;
-    CEC_TRY(ragged_check(cc, base, part_offsets, chunk_lens, n_parts, &units));
-    CEC_TRY(check_present(cc->d, cc->d + cc->p, present, n_parts));
-    int dev = 0;
-    CEC_TRY(current_device(&dev));
-    return reconstruct_ragged(const_cast<cec_codec*>(cc), base, part_offsets, chunk_lens, n_parts,
-                              present, data_only != 0, static_cast<hipStream_t>(stream));
-}
-
-int cec_read_ragged(const cec_codec* c, uint8_t* base, const size_t* part_offsets,
-                    const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
-                    const uint8_t* expected, uint8_t* verified, int* part_status, void* stream) {
-    return read_ragged_checked(c, base, part_offsets, chunk_lens, n_parts, present, expected,
-                               verified, part_status, true, stream);
-}
-
-int cec_resilver_ragged(const cec_codec* c, uint8_t* base, const size_t* part_offsets,
-                        const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
-                        const uint8_t* expected, uint8_t* verified, int* part_status,
-                        void* stream) {
-    return read_ragged_checked(c, base, part_offsets, chunk_lens, n_parts, present, expected,
-                               verified, part_status, false, stream);
-}
-
-int cec_parts_read(const cec_codec* cc, uint8_t* const* shards, const size_t* chunk_lens,
-                   size_t n_parts, const uint8_t* present, const uint8_t* expected, int data_only,
-                   uint8_t* verified, int* part_status) {
-    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
-    if (n_parts == 0) return CEC_OK;
-    if (!shards || !chunk_lens || !present || !expected || !verified || !part_status)
-        return CEC_ERR_INVALID_ARGUMENT;
-    for (size_t k = 0; k < n_parts; ++k)
-        if (chunk_lens[k] == 0) return CEC_EMPTY_SHARD;
-    cec_codec* c = const_cast<cec_codec*>(cc);
-    const size_t d = c->d, t = c->d + c->p;
-    size_t items = 0;
-    if (__builtin_mul_overflow(n_parts, t, &items) || items > 0xFFFFFFFFull)
-        return CEC_ERR_INVALID_ARGUMENT;
-    // A loaded chunk needs its bytes; a part that can be decoded (d or more chunks loaded) needs
-    // memory behind every slot the mode fills.
-    for (size_t k = 0; k < n_parts; ++k) {
-        size_t loaded = 0;
-        for (size_t i = 0; i < t; ++i) loaded += present[k * t + i] ? 1 : 0;
-        for (size_t i = 0; i < t; ++i) {
-            const bool need = present[k * t + i] || (loaded >= d && fills_slot(i, d, data_only != 0));
-            if (need && !shards[k * t + i]) {
-                g_last_error = "cec_parts_read: a chunk slot that is read or filled is NULL";
-                return CEC_ERR_INVALID_ARGUMENT;
-            }
-        }
-    }
-    // Rounds as cec_parts_encode cuts them: at most CEC_COALESCE_MAX_MIB of (padded) data-chunk
-    // bytes, a larger part alone; every round is checked before the first one runs.
-    std::vector<size_t> round_end;
-    const size_t cap = coalesce_max_bytes();
-    size_t bytes = 0, first = 0;
-    for (size_t k = 0; k < n_parts; ++k) {
-        size_t cs = 0, b = 0;
-        if (!ragged_stride(chunk_lens[k], &cs) || __builtin_mul_overflow(d, cs, &b))
-            return CEC_ERR_INVALID_ARGUMENT;
-        if (k > first && (b > cap || bytes > cap - b)) {
-            round_end.push_back(k);
-            first = k;
-            bytes = 0;
-        }
-        bytes += std::min(b, cap);
-    }
-    round_end.push_back(n_parts);
-    {
-        std::vector<size_t> offs(n_parts);
-        size_t k0 = 0;
-        for (size_t k1 : round_end) {
-            size_t total = 0;
-            uint64_t units = 0;
-            CEC_TRY(ragged_layout(t, chunk_lens + k0, k1 - k0, offs.data(), &total));
-            CEC_TRY(ragged_check(c, nullptr, offs.data(), chunk_lens + k0, k1 - k0, &units));
-            k0 = k1;
-        }
-    }
-    int dev = 0;
-    CEC_TRY(current_device(&dev));
-    Arena* arena = ragged_arenas().take(dev);
-    int st = CEC_OK;
-    size_t k0 = 0;
-    for (size_t k1 : round_end) {
-        st = parts_read_round(c, *arena, shards + k0 * t, chunk_lens + k0, k1 - k0,
-                              present + k0 * t, expected + k0 * t * 32, data_only != 0,
-                              verified + k0 * t, part_status + k0);
-        if (st != CEC_OK) break;
-        k0 = k1;
-    }
-    if (st != CEC_OK && arena->dev.stream) {  // nothing of a failed round stays in flight
-        (void)hipStreamSynchronize(arena->dev.stream);
-        (void)hipGetLastError();
-    }
-    ragged_arenas().give(dev, arena);
-    return st;
 }
 
 // ------------------------------------------------------------------------------------------

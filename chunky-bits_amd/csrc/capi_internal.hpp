@@ -1,0 +1,301 @@
+// capi_internal.hpp — what the pieces of the C-ABI (capi.cpp, ragged.cpp) share.  Not installed,
+// not exported: everything here is defined once in capi.cpp unless it is inline.
+#pragma once
+
+#include "chunky_ec.h"
+
+#include <hip/hip_runtime.h>
+
+#include <array>
+#include <list>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <unordered_map>
+#include <utility>
+#include <vector>
+
+#include "gf256.hpp"
+#include "kernels.hpp"
+#include "knobs.hpp"
+
+#pragma GCC visibility push(hidden)
+
+namespace cec {
+
+// The calling thread's last error text (cec_last_error).
+void set_last_error(std::string msg);
+const std::string& last_error();
+int hip_fail(hipError_t e, const char* what);  // sets the last error; CEC_ERR_HIP / OUT_OF_MEMORY
+
+#define HIP_TRY(expr)                                        \
+    do {                                                     \
+        hipError_t _e = (expr);                              \
+        if (_e != hipSuccess) return cec::hip_fail(_e, #expr); \
+    } while (0)
+
+#define CEC_TRY(expr)              \
+    do {                           \
+        int _s = (expr);           \
+        if (_s != CEC_OK) return _s; \
+    } while (0)
+
+int current_device(int* dev);
+
+constexpr size_t kChunkAlign = 256;
+inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+inline bool aligned16(const void* p, size_t a, size_t b) {
+    return (reinterpret_cast<uintptr_t>(p) % 16 == 0) && (a % 16 == 0) && (b % 16 == 0);
+}
+
+inline size_t coalesce_max_bytes() { return knobs().coalesce_max_bytes; }
+
+// A buffer of the scratch pool (capi.cpp ScratchPool): device memory with a page-locked host
+// mirror, handed out again only once the event recorded after its last use has completed.
+struct ScratchBuf {
+    int device = 0;
+    uint8_t* dev = nullptr;
+    uint8_t* host = nullptr;  // page-locked mirror of the same size
+    size_t cap = 0;
+    hipEvent_t done = nullptr;
+    bool in_use = false;   // handed out, release not called yet
+    bool pending = false;  // released: `done` marks the end of its last use
+};
+
+// One scratch buffer for the launches of one call: acquire, fill / upload, launch, and the
+// destructor releases it on the stream those launches went to (error paths included).
+class Scratch {
+   public:
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch();
+    int acquire(size_t bytes, hipStream_t s);
+    uint8_t* dev() const { return buf_->dev; }
+    uint8_t* host() const { return buf_->host; }
+
+   private:
+    ScratchBuf* buf_ = nullptr;
+    hipStream_t stream_ = nullptr;
+};
+
+// Upload `words` into `sc` (acquired here) on stream s; *dptr = their device copy.
+int upload_words(const std::vector<uint32_t>& words, hipStream_t s, Scratch& sc, uint32_t** dptr);
+
+// A stream + a device staging buffer (leased from capi.cpp's CtxPool, or part of an Arena).
+struct StageCtx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    uint8_t* dbuf = nullptr;
+    size_t dcap = 0;
+    void release_buffer() {
+        if (dbuf) (void)hipFree(dbuf);
+        dbuf = nullptr;
+        dcap = 0;
+    }
+    void destroy() {  // on `device` (callers set it)
+        if (stream) {
+            (void)hipStreamSynchronize(stream);
+            (void)hipStreamDestroy(stream);
+        }
+        stream = nullptr;
+        release_buffer();
+    }
+};
+
+// Stream + device staging of at least device_bytes (grown, never shrunk while leased).
+int ctx_reserve(StageCtx& c, size_t device_bytes);
+
+// Pinned host staging, never shrunk.  Pinning costs ~0.35 s per GiB, so the first growth
+// past 64 MiB goes straight to the batch cap (one pinning per process, not one per size step).
+struct PinnedBuf {
+    uint8_t* ptr = nullptr;
+    size_t cap = 0;
+    int reserve(size_t bytes, size_t cap_hint);
+};
+
+struct Arena {
+    StageCtx dev;  // stream + device staging
+    PinnedBuf in, out;
+    // the parity comes back on a side stream as soon as the encode is done, beside the SHA-256
+    // chains (profiles/r2_early_d2h/; made on first use; arenas live as long as the process)
+    hipStream_t side = nullptr;
+    hipEvent_t encoded = nullptr;
+};
+
+// A per-device free list of arenas: one per batch or call in flight, kept for the life of the
+// process.
+class ArenaPool {
+   public:
+    Arena* take(int device);
+    void give(int device, Arena* a);
+
+   private:
+    std::mutex mu_;
+    std::vector<std::unique_ptr<Arena>> all_;
+    std::map<int, std::vector<Arena*>> free_;
+};
+
+// Erasure-pattern key: present bitset (<= 256 shards) + data_only.
+struct PatternKey {
+    std::array<uint64_t, 4> bits{};
+    bool data_only = false;
+    bool operator<(const PatternKey& o) const {
+        if (bits != o.bits) return bits < o.bits;
+        return data_only < o.data_only;
+    }
+};
+
+// The host half of a batched reconstruct, shared by the uniform and the ragged layout: the parts
+// that need a rebuild grouped by erasure pattern, one decode record per pattern, the patterns
+// bucketed by output-row count, and per bucket the launch lists.
+// words = [records...][launch lists: part_ids..., part_pat...].  Patterns of up to max_var_rows()
+// rows (every RS(10,4) erasure set) share ONE launch that dispatches on each part's row count;
+// wider patterns get a row-group launch per row count.
+struct DecodePlan {
+    struct Launch {
+        uint32_t n_out;  // 0: per-part row counts (the shared launch)
+        size_t ids;      // word offset of part_ids; part_pat follows at ids + count
+        size_t count;
+    };
+    std::vector<uint32_t> words;
+    std::vector<Launch> launches;  // empty: nothing to rebuild
+    uint32_t var_rows = 0;         // the shared launch's widest pattern: its kernel's row class
+};
+
+void plan_decode(cec_codec* c, const uint8_t* present, size_t n_parts, bool data_only,
+                 DecodePlan* plan);
+
+// CEC_TOO_FEW_SHARDS_PRESENT when a part has some but fewer than d chunks present.
+int check_present(size_t d, size_t t, const uint8_t* present, size_t n_parts);
+
+// The shared launch's row class must cover every record it lists (the kernels skip a wider
+// pattern without writing its chunks: kernels.hpp launch_rs_apply_var).
+int check_row_class(const DecodePlan& plan, const DecodePlan::Launch& l, uint32_t n_rows,
+                    const char* who);
+
+// A loaded chunk is hashed unless the caller marked it CEC_PRESENT_VERIFIED (a read retry's
+// chunks that an earlier pass already verified).
+inline bool needs_hash(uint8_t f) { return f != 0 && f != CEC_PRESENT_VERIFIED; }
+
+// From a verification's flags to the rebuild, for n_parts parts of t chunks.  Chunks an earlier
+// pass verified (present == CEC_PRESENT_VERIFIED) are set in `verified`; part_status[k] = CEC_OK
+// or, with fewer than d verified chunks, CEC_TOO_FEW_SHARDS_PRESENT (the reference's read returns
+// such a part short / resilver reports it); *mask = the rebuild's present flags: a part's
+// verified flags, or all ones (left alone) for a part that cannot be decoded and, with
+// only_failed, for a part whose loaded chunks all verified (the uniform path's speculative pass
+// rebuilt those; the ragged path has none and decodes every decodable part).  Returns whether
+// any part kept its flags.
+bool rebuild_mask(size_t d, size_t t, size_t n_parts, const uint8_t* present, uint8_t* verified,
+                  int* part_status, bool only_failed, std::vector<uint8_t>* mask);
+
+}  // namespace cec
+
+#pragma GCC visibility pop
+
+// The codec behind the C-ABI's handle: the coding matrix, the encode record (one device copy per
+// device) and the decode records by erasure pattern.
+struct cec_codec {
+    size_t d = 0, p = 0;
+    cec::ByteMatrix m;             // (d+p) x d
+    std::vector<uint32_t> enc;     // pattern record: parity rows over the d data chunks
+    bool bs = false;               // parity rows = a compiled bit-sliced shape (bs_encode_matches)
+    std::mutex mu;
+    std::unordered_map<int, uint32_t*> dev_enc;  // encode record per device
+    // Decode records, least recently used first out once kDecCacheCap patterns are cached (every
+    // 1..4-erasure pattern of RS(10,4), both modes, is 2 940).
+    static constexpr size_t kDecCacheCap = 4096;
+    using Record = std::shared_ptr<const std::vector<uint32_t>>;
+    std::list<cec::PatternKey> dec_lru;  // front = most recent
+    std::map<cec::PatternKey, std::pair<Record, std::list<cec::PatternKey>::iterator>> dec_cache;
+
+    ~cec_codec() {
+        int cur = 0;
+        if (hipGetDevice(&cur) != hipSuccess) return;
+        for (auto& kv : dev_enc) {
+            if (hipSetDevice(kv.first) == hipSuccess) (void)hipFree(kv.second);
+        }
+        (void)hipSetDevice(cur);
+    }
+
+    // Device copy of the encode record on the current device.
+    int encode_record(uint32_t** out) {
+        int dev = 0;
+        CEC_TRY(cec::current_device(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = dev_enc.find(dev);
+        if (it != dev_enc.end()) {
+            *out = it->second;
+            return CEC_OK;
+        }
+        uint32_t* ptr = nullptr;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ptr), enc.size() * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpy(ptr, enc.data(), enc.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        dev_enc[dev] = ptr;
+        *out = ptr;
+        return CEC_OK;
+    }
+
+    // Decode record for a present set: inputs = first d present chunks (the crate's choice,
+    // reconstruct_internal), outputs = missing data (+ missing parity unless data_only).
+    // Missing data rows = rows of inv(M[valid]); missing parity rows = M[r] * inv(M[valid]),
+    // i.e. the crate's "recompute parity from the rebuilt data" folded into one pass
+    // (identical bytes: GF(2^8) arithmetic is exact).  Not exported, as before this header (its
+    // key type then had internal linkage).
+    __attribute__((visibility("hidden"))) Record decode_record(const cec::PatternKey& key) {
+        using namespace cec;
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = dec_cache.find(key);
+        if (it != dec_cache.end()) {
+            dec_lru.splice(dec_lru.begin(), dec_lru, it->second.second);
+            return it->second.first;
+        }
+        const size_t t = d + p;
+        std::vector<uint32_t> in_idx, out_idx;
+        std::vector<size_t> miss_par;
+        for (size_t i = 0; i < t; ++i) {
+            const bool present = (key.bits[i / 64] >> (i % 64)) & 1;
+            if (present) {
+                if (in_idx.size() < d) in_idx.push_back(uint32_t(i));
+            } else if (i < d) {
+                out_idx.push_back(uint32_t(i));
+            } else if (!key.data_only) {
+                miss_par.push_back(i);
+            }
+        }
+        for (size_t i : miss_par) out_idx.push_back(uint32_t(i));
+        ByteMatrix sub(d, d), dec;
+        for (size_t r = 0; r < d; ++r)
+            for (size_t c = 0; c < d; ++c) sub.at(r, c) = m.at(in_idx[r], c);
+        invert(sub, dec);  // any d rows of M are independent (distinct Vandermonde points)
+        ByteMatrix rows(out_idx.size(), d);
+        for (size_t k = 0; k < out_idx.size(); ++k) {
+            const size_t o = out_idx[k];
+            if (o < d) {
+                for (size_t c = 0; c < d; ++c) rows.at(k, c) = dec.at(o, c);
+            } else {
+                const Gf256& g = Gf256::get();
+                for (size_t c = 0; c < d; ++c) {
+                    uint8_t acc = 0;
+                    for (size_t q = 0; q < d; ++q) acc ^= g.mul(m.at(o, q), dec.at(q, c));
+                    rows.at(k, c) = acc;
+                }
+            }
+        }
+        auto rec = std::make_shared<std::vector<uint32_t>>(pattern_words(d, out_idx.size()));
+        write_pattern(rec->data(), d, in_idx, out_idx, rows);
+        if (dec_cache.size() >= kDecCacheCap) {
+            dec_cache.erase(dec_lru.back());
+            dec_lru.pop_back();
+        }
+        dec_lru.push_front(key);
+        dec_cache.emplace(key, std::make_pair(Record(rec), dec_lru.begin()));
+        return rec;
+    }
+
+    size_t cached_patterns() {
+        std::lock_guard<std::mutex> lk(mu);
+        return dec_cache.size();
+    }
+};

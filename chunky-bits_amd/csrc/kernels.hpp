@@ -126,7 +126,7 @@ hipError_t launch_rs_encode_ragged(const RaggedParams& a, hipStream_t s);
 // Reconstruct of listed parts whose records carry their own row count (1..max_var_rows()), one
 // launch.  a.part_pat is required; a.n_rows selects the row class (2, 4 or 8) and MUST be at
 // least the widest listed record's row count, or 0 (the 8-row class): a wider record's part is
-// skipped in the kernel.  The caller (capi.cpp reconstruct_ragged) checks the host records first.
+// skipped in the kernel.  The caller (ragged.cpp reconstruct_ragged) checks the host records first.
 hipError_t launch_rs_reconstruct_ragged(const RaggedParams& a, hipStream_t s);
 uint64_t ragged_unit_bytes();
 uint64_t ragged_max_units();  // most units one launch can address (grid and index limits)

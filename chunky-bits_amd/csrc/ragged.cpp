@@ -1,0 +1,591 @@
+// ragged.cpp — the ragged half of include/chunky_ec.h: parts of different chunk lengths in one
+// launch sequence (cec_encode_hash_ragged, cec_reconstruct_ragged, cec_read_ragged,
+// cec_resilver_ragged) and the host-staged calls on top of them (cec_parts_encode,
+// cec_parts_read).  Part k's chunk i lies at base + off[k] + i * stride(L_k), stride = L rounded
+// up to 16.  Host work only; every step of the path has one home here.
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <numeric>
+#include <thread>
+
+#include "capi_internal.hpp"
+
+using namespace cec;
+
+namespace {
+
+constexpr size_t kRaggedAlign = 16;
+
+// L rounded up to 16; 0 when that overflows (and for an empty chunk, which every caller refuses
+// before it asks).
+size_t ragged_stride(size_t L) {
+    return L > SIZE_MAX - (kRaggedAlign - 1) ? 0 : round_up(L, kRaggedAlign);
+}
+
+// The packed layout: part k+1 directly behind part k.
+int ragged_layout(size_t t, const size_t* lens, size_t n, size_t* offs, size_t* total) {
+    size_t off = 0;
+    for (size_t k = 0; k < n; ++k) {
+        if (lens[k] == 0) return CEC_EMPTY_SHARD;
+        const size_t cs = ragged_stride(lens[k]);
+        size_t span = 0;
+        if (!cs || __builtin_mul_overflow(t, cs, &span) || span > SIZE_MAX - off)
+            return CEC_ERR_INVALID_ARGUMENT;
+        offs[k] = off;
+        off += span;
+    }
+    *total = off;
+    return CEC_OK;
+}
+
+// Every argument check of a ragged layout (no device use), the bound on the launch's work units
+// among them.
+int ragged_check(const cec_codec* c, const uint8_t* base, const size_t* offs, const size_t* lens,
+                 size_t n) {
+    const size_t t = c->d + c->p;
+    size_t items = 0;  // SHA-256 items are 32-bit (checked before the arrays are walked)
+    if (__builtin_mul_overflow(n, t, &items) || items > 0xFFFFFFFFull)
+        return CEC_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < n; ++k)
+        if (lens[k] == 0) return CEC_EMPTY_SHARD;
+    if (reinterpret_cast<uintptr_t>(base) % kRaggedAlign) return CEC_ERR_INVALID_ARGUMENT;
+    const uint64_t unit = ragged_unit_bytes(), max_units = ragged_max_units();
+    uint64_t total = 0;
+    size_t end = 0;  // first byte behind the parts so far
+    for (size_t k = 0; k < n; ++k) {
+        const size_t cs = ragged_stride(lens[k]);
+        size_t span = 0;
+        if (offs[k] % kRaggedAlign || offs[k] < end) return CEC_ERR_INVALID_ARGUMENT;
+        if (!cs || __builtin_mul_overflow(t, cs, &span) || span > SIZE_MAX - offs[k])
+            return CEC_ERR_INVALID_ARGUMENT;
+        end = offs[k] + span;
+        total += (uint64_t(lens[k] - 1)) / unit + 1;
+        if (total > max_units) return CEC_ERR_INVALID_ARGUMENT;  // never a silent wrap
+    }
+    return CEC_OK;
+}
+
+// The per-part device records of the parts ids[0 .. count) (null: parts 0 .. count - 1):
+// units[count + 1] = the prefix array of their work units, parts[4 * count] = {off lo, off hi,
+// L lo, L hi}.  Returns the unit total, at most the whole batch's, which ragged_check bounded.
+uint32_t part_records(const size_t* offs, const size_t* lens, const uint32_t* ids, size_t count,
+                      uint32_t* units, uint32_t* parts) {
+    const uint64_t unit = ragged_unit_bytes();
+    uint64_t acc = 0;
+    for (size_t q = 0; q < count; ++q) {
+        const size_t k = ids ? ids[q] : q;
+        const uint64_t off = offs[k], L = lens[k];
+        units[q] = uint32_t(acc);
+        acc += (L - 1) / unit + 1;
+        parts[4 * q + 0] = uint32_t(off);
+        parts[4 * q + 1] = uint32_t(off >> 32);
+        parts[4 * q + 2] = uint32_t(L);
+        parts[4 * q + 3] = uint32_t(L >> 32);
+    }
+    units[count] = uint32_t(acc);
+    return uint32_t(acc);
+}
+
+// The SHA-256 list of a ragged batch: ptrs / h_len of the items k * t + i that pass `pick` (the
+// others are never looked at) and, in `order`, those items stably sorted by their part's length,
+// longest first: a SHA-256 wave runs as long as its longest lane, so the 64 chains of a wave get
+// similar lengths.  Digests and flags land at their item's place whatever the order.  An item's
+// key is its part's, so the parts are sorted and each expanded in place.  Returns the items listed.
+template <typename Pick>
+size_t sha_list(uint8_t* base, const size_t* offs, const size_t* lens, size_t n, size_t t,
+                Pick pick, uint64_t* ptrs, uint64_t* h_len, uint32_t* order) {
+    std::vector<uint32_t> by_len(n);
+    std::iota(by_len.begin(), by_len.end(), 0u);
+    std::stable_sort(by_len.begin(), by_len.end(),
+                     [&](uint32_t x, uint32_t y) { return lens[x] > lens[y]; });
+    size_t count = 0;
+    for (const size_t k : by_len) {
+        const size_t cs = ragged_stride(lens[k]);
+        for (size_t i = 0; i < t; ++i) {
+            const size_t item = k * t + i;
+            if (!pick(item)) continue;
+            ptrs[item] = reinterpret_cast<uint64_t>(base + offs[k] + i * cs);
+            h_len[item] = lens[k];
+            order[count++] = uint32_t(item);
+        }
+    }
+    return count;
+}
+
+// The launches of a checked ragged batch on `s`: one upload of the per-part words (the SHA-256
+// list, the part records), the GF(2^8) kernel, the SHA-256 kernel.  The host arrays are copied
+// into the scratch buffer's page-locked mirror before this returns.
+int ragged_launch(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* lens, size_t n,
+                  uint8_t* digests, hipStream_t s) {
+    const size_t t = c->d + c->p, items = n * t;
+    uint32_t* drec = nullptr;
+    CEC_TRY(c->encode_record(&drec));
+    // [ptrs u64 x items][lens u64 x items][order u32 x items][units u32 x n+1][parts u32 x 4n]
+    const size_t o_len = items * 8, o_ord = o_len + items * 8, o_units = o_ord + items * 4,
+                 o_parts = o_units + (n + 1) * 4, bytes = o_parts + n * 16;
+    Scratch sc;  // released on s behind the launches below
+    CEC_TRY(sc.acquire(bytes, s));
+    sha_list(base, offs, lens, n, t, [](size_t) { return true; },
+             reinterpret_cast<uint64_t*>(sc.host()), reinterpret_cast<uint64_t*>(sc.host() + o_len),
+             reinterpret_cast<uint32_t*>(sc.host() + o_ord));
+    RaggedParams a{};
+    a.total_units = part_records(offs, lens, nullptr, n,
+                                 reinterpret_cast<uint32_t*>(sc.host() + o_units),
+                                 reinterpret_cast<uint32_t*>(sc.host() + o_parts));
+    HIP_TRY(hipMemcpyAsync(sc.dev(), sc.host(), bytes, hipMemcpyHostToDevice, s));
+    a.base = base;
+    a.pat = drec;
+    a.units = reinterpret_cast<const uint32_t*>(sc.dev() + o_units);
+    a.parts = reinterpret_cast<const uint32_t*>(sc.dev() + o_parts);
+    a.n_parts = uint32_t(n);
+    a.d = uint32_t(c->d);
+    a.n_rows = uint32_t(c->p);
+    HIP_TRY(launch_rs_encode_ragged(a, s));
+    ShaParams h{};
+    h.ptrs = reinterpret_cast<const uint64_t*>(sc.dev());
+    h.lens = reinterpret_cast<const uint64_t*>(sc.dev() + o_len);
+    h.n_parts = uint32_t(items);
+    h.n_chunks = 1;
+    h.digests = digests;
+    h.items = reinterpret_cast<const uint32_t*>(sc.dev() + o_ord);
+    h.n_items = uint32_t(items);
+    HIP_TRY(launch_sha256(h, true, s));
+    return CEC_OK;
+}
+
+// The launches of cec_reconstruct_ragged for a checked layout (ragged_check) and checked flags
+// (check_present), on `s`.  Only the parts the plan lists reach the device: per launch the part
+// records of its listed parts, behind the plan's words in one scratch buffer whose page-locked
+// mirror holds the copy of the host arrays.
+int reconstruct_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* lens,
+                       size_t n, const uint8_t* present, bool data_only, hipStream_t s) {
+    DecodePlan plan;
+    plan_decode(c, present, n, data_only, &plan);
+    if (plan.launches.empty()) return CEC_OK;
+    size_t listed = 0;
+    for (const auto& l : plan.launches) {
+        if (!l.n_out) CEC_TRY(check_row_class(plan, l, plan.var_rows, "reconstruct_ragged"));
+        listed += l.count;
+    }
+    // [plan words][per launch: units u32 x (count + 1), parts u32 x 4 count]
+    const size_t n_words = plan.words.size() + listed * 5 + plan.launches.size();
+    Scratch sc;  // released on s behind the launches below
+    CEC_TRY(sc.acquire(n_words * sizeof(uint32_t), s));
+    uint32_t* h = reinterpret_cast<uint32_t*>(sc.host());
+    uint32_t* dwords = reinterpret_cast<uint32_t*>(sc.dev());
+    std::memcpy(h, plan.words.data(), plan.words.size() * sizeof(uint32_t));
+    std::vector<RaggedParams> params;
+    size_t at = plan.words.size();
+    for (const auto& l : plan.launches) {
+        RaggedParams a{};
+        a.total_units = part_records(offs, lens, plan.words.data() + l.ids, l.count, h + at,
+                                     h + at + l.count + 1);
+        a.base = base;
+        a.pat = dwords;
+        a.units = dwords + at;
+        a.parts = dwords + at + l.count + 1;
+        a.part_pat = dwords + l.ids + l.count;
+        a.n_parts = uint32_t(l.count);
+        a.d = uint32_t(c->d);
+        a.n_rows = l.n_out ? l.n_out : plan.var_rows;
+        params.push_back(a);
+        at += l.count * 5 + 1;
+    }
+    HIP_TRY(hipMemcpyAsync(dwords, h, n_words * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    for (size_t i = 0; i < params.size(); ++i) {
+        const hipError_t e = plan.launches[i].n_out ? launch_rs_encode_ragged(params[i], s)
+                                                    : launch_rs_reconstruct_ragged(params[i], s);
+        if (e != hipSuccess) return hip_fail(e, "launch_rs_reconstruct_ragged");
+    }
+    return CEC_OK;
+}
+
+// Shared body of cec_read_ragged / cec_resilver_ragged for a checked layout: on `s` the SHA-256
+// list launch in verify mode over the chunks that need hashing (ok and expected indexed by
+// k*(d+p)+i), the readback of the flags (the one wait), then the rebuild of every decodable part
+// from its first d verified chunks.
+// No speculative decode beside the verification: the chains of a ragged batch are short and
+// nobody has measured whether it pays (not built).
+int read_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* lens, size_t n,
+                const uint8_t* present, const uint8_t* expected, uint8_t* verified,
+                int* part_status, bool data_only, hipStream_t s) {
+    const size_t d = c->d, t = c->d + c->p, items = n * t;
+    // [ptrs u64 x items][lens u64 x items][order u32 x items][ok u8 x items]
+    const size_t o_len = items * 8, o_ord = o_len + items * 8, o_ok = o_ord + items * 4,
+                 bytes = o_ok + items;
+    Scratch sc;  // released on s behind the readback
+    CEC_TRY(sc.acquire(bytes, s));
+    uint8_t* ok = sc.dev() + o_ok;
+    HIP_TRY(hipMemsetAsync(ok, 0, items, s));
+    const size_t hashed = sha_list(
+        base, offs, lens, n, t, [&](size_t item) { return needs_hash(present[item]); },
+        reinterpret_cast<uint64_t*>(sc.host()), reinterpret_cast<uint64_t*>(sc.host() + o_len),
+        reinterpret_cast<uint32_t*>(sc.host() + o_ord));
+    if (hashed) {
+        HIP_TRY(hipMemcpyAsync(sc.dev(), sc.host(), o_ord + hashed * 4, hipMemcpyHostToDevice, s));
+        ShaParams h{};
+        h.ptrs = reinterpret_cast<const uint64_t*>(sc.dev());
+        h.lens = reinterpret_cast<const uint64_t*>(sc.dev() + o_len);
+        h.n_parts = uint32_t(items);
+        h.n_chunks = 1;
+        h.expected = expected;
+        h.ok = ok;
+        h.items = reinterpret_cast<const uint32_t*>(sc.dev() + o_ord);
+        h.n_items = uint32_t(hashed);
+        const hipError_t e = launch_sha256(h, true, s);
+        if (e != hipSuccess) return hip_fail(e, "launch_sha256 (ragged verify)");
+    }
+    // the flags come back through the mirror, behind the words that went up
+    HIP_TRY(hipMemcpyAsync(sc.host() + o_ok, ok, items, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::memcpy(verified, sc.host() + o_ok, items);
+    std::vector<uint8_t> pres;
+    rebuild_mask(d, t, n, present, verified, part_status, false, &pres);
+    return reconstruct_ragged(c, base, offs, lens, n, pres.data(), data_only, s);
+}
+
+// Every check of cec_read_ragged / cec_resilver_ragged, then the work.
+int read_ragged_checked(const cec_codec* cc, uint8_t* base, const size_t* offs, const size_t* lens,
+                        size_t n, const uint8_t* present, const uint8_t* expected,
+                        uint8_t* verified, int* part_status, bool data_only, void* stream) {
+    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
+    if (n == 0) return CEC_OK;
+    if (!base || !offs || !lens || !present || !expected || !verified || !part_status)
+        return CEC_ERR_INVALID_ARGUMENT;
+    CEC_TRY(ragged_check(cc, base, offs, lens, n));
+    int dev = 0;
+    CEC_TRY(current_device(&dev));
+    return read_ragged(const_cast<cec_codec*>(cc), base, offs, lens, n, present, expected,
+                       verified, part_status, data_only, static_cast<hipStream_t>(stream));
+}
+
+// Host staged (cec_parts_encode, cec_parts_read): the parts packed into an arena's pinned staging
+// in the cec_ragged_layout layout, moved up, worked on as above, results copied out.
+
+// Their arenas: one per call in flight.
+ArenaPool& ragged_arenas() {
+    static ArenaPool* pool = new ArenaPool();
+    return *pool;
+}
+
+// fn(k) for k < n on up to 8 threads: one per 16 MiB of `bytes` moved, so a call of a few small
+// parts never starts one.
+template <typename Fn>
+void for_parts(size_t n, size_t bytes, Fn fn) {
+    const size_t nt = std::min<size_t>({size_t(8), bytes / (size_t(16) << 20), n});
+    if (nt <= 1) {
+        for (size_t k = 0; k < n; ++k) fn(k);
+        return;
+    }
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (size_t k; (k = next.fetch_add(1, std::memory_order_relaxed)) < n;) fn(k);
+    };
+    std::vector<std::thread> th;
+    for (size_t i = 1; i < nt; ++i) th.emplace_back(work);
+    work();
+    for (auto& x : th) x.join();
+}
+
+using Spans = std::vector<std::pair<size_t, size_t>>;
+
+// Copies of the byte ranges [first, second) (ascending, disjoint) between the staging and the
+// device arena, which share their offsets.  Neighbouring ranges share one copy, with what lies
+// between them travelling along, until the gap is worth a copy call of its own (256 KiB: a few
+// microseconds of the link either way).
+int copy_spans(uint8_t* stage, uint8_t* dbase, const Spans& spans, bool to_device, hipStream_t s) {
+    constexpr size_t kGap = size_t(256) << 10;
+    for (size_t q = 0; q < spans.size();) {
+        const size_t from = spans[q].first;
+        size_t to = spans[q].second;
+        for (++q; q < spans.size() && spans[q].first - to < kGap; ++q) to = spans[q].second;
+        if (to_device)
+            HIP_TRY(hipMemcpyAsync(dbase + from, stage + from, to - from, hipMemcpyHostToDevice, s));
+        else
+            HIP_TRY(hipMemcpyAsync(stage + from, dbase + from, to - from, hipMemcpyDeviceToHost, s));
+    }
+    return CEC_OK;
+}
+
+// One round's place in an arena: the packed layout of its n parts, `stage` (pinned) and `dbase`
+// (device) sharing those offsets, and `dside`, device room for the round's n * t digests, with
+// the arena's `out` as its pinned side.
+struct Round {
+    std::vector<size_t> offs;
+    uint8_t *stage, *dside, *dbase;
+    hipStream_t s;
+};
+
+int reserve_round(Arena& a, size_t d, size_t t, const size_t* chunk_lens, size_t n, Round* r) {
+    r->offs.resize(n);
+    size_t total = 0;
+    CEC_TRY(ragged_layout(t, chunk_lens, n, r->offs.data(), &total));
+    const size_t cap = coalesce_max_bytes();
+    CEC_TRY(a.in.reserve(total, cap / d * t + t * kRaggedAlign));
+    CEC_TRY(a.out.reserve(n * t * 32, cap / 8));
+    const size_t dig_bytes = round_up(n * t * 32, kChunkAlign);
+    CEC_TRY(ctx_reserve(a.dev, dig_bytes + total));
+    r->stage = a.in.ptr;
+    r->dside = a.dev.dbuf;
+    r->dbase = a.dev.dbuf + dig_bytes;
+    r->s = a.dev.stream;
+    return CEC_OK;
+}
+
+// The rounds of a host-staged call over parts of these chunk lengths: at most
+// CEC_COALESCE_MAX_MIB of (padded) data chunks each, a larger part alone.  Every round is checked
+// before the first one runs, so an error leaves the outputs untouched.  Then round(arena, k0, k1)
+// for each, on one arena; nothing of a failed round stays in flight.
+template <typename Fn>
+int run_rounds(const cec_codec* c, const size_t* chunk_lens, size_t n, Fn round) {
+    const size_t d = c->d, t = c->d + c->p, cap = coalesce_max_bytes();
+    std::vector<size_t> round_end;
+    size_t bytes = 0, first = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const size_t cs = ragged_stride(chunk_lens[k]);
+        size_t b = 0;
+        if (!cs || __builtin_mul_overflow(d, cs, &b)) return CEC_ERR_INVALID_ARGUMENT;
+        if (k > first && (b > cap || bytes > cap - b)) {
+            round_end.push_back(k);
+            first = k;
+            bytes = 0;
+        }
+        bytes += std::min(b, cap);
+    }
+    round_end.push_back(n);
+    std::vector<size_t> offs(n);
+    size_t k0 = 0, total = 0;
+    for (size_t k1 : round_end) {
+        CEC_TRY(ragged_layout(t, chunk_lens + k0, k1 - k0, offs.data(), &total));
+        CEC_TRY(ragged_check(c, nullptr, offs.data(), chunk_lens + k0, k1 - k0));
+        k0 = k1;
+    }
+    int dev = 0;
+    CEC_TRY(current_device(&dev));
+    Arena* arena = ragged_arenas().take(dev);
+    int st = CEC_OK;
+    k0 = 0;
+    for (size_t k1 : round_end) {
+        st = round(*arena, k0, k1);
+        if (st != CEC_OK) break;
+        k0 = k1;
+    }
+    if (st != CEC_OK && arena->dev.stream) {
+        (void)hipStreamSynchronize(arena->dev.stream);
+        (void)hipGetLastError();
+    }
+    ragged_arenas().give(dev, arena);
+    return st;
+}
+
+// One round of cec_parts_encode: parts [0, n) of these arrays, packed, moved, encoded and hashed
+// together, results copied out.
+int parts_round(cec_codec* c, Arena& a, const uint8_t* const* bufs, const size_t* lengths,
+                size_t n, uint8_t* const* parity_outs, uint8_t* digests_out,
+                const size_t* chunk_lens) {
+    const size_t d = c->d, p = c->p, t = d + p;
+    Round r;
+    CEC_TRY(reserve_round(a, d, t, chunk_lens, n, &r));
+    const std::vector<size_t>& offs = r.offs;
+    size_t in_bytes = 0, out_bytes = 0;
+    Spans parity;  // per part, behind its data chunks
+    for (size_t k = 0; k < n; ++k) {
+        const size_t cs = ragged_stride(chunk_lens[k]);
+        in_bytes += lengths[k];
+        out_bytes += p * chunk_lens[k];
+        parity.emplace_back(offs[k] + d * cs, offs[k] + t * cs);
+    }
+    // data chunk j of part k = bytes [j*L, (j+1)*L) of the caller's `length` bytes, zeros behind
+    for_parts(n, in_bytes, [&](size_t k) {
+        const size_t L = chunk_lens[k], cs = ragged_stride(L), len = lengths[k];
+        for (size_t j = 0; j < d; ++j) {
+            uint8_t* dst = r.stage + offs[k] + j * cs;
+            const size_t b0 = j * L, have = b0 < len ? std::min(L, len - b0) : 0;
+            if (have) std::memcpy(dst, bufs[k] + b0, have);
+            if (have < L) std::memset(dst + have, 0, L - have);
+        }
+    });
+    HIP_TRY(hipMemcpyAsync(r.dbase, r.stage, parity.back().first, hipMemcpyHostToDevice, r.s));
+    CEC_TRY(ragged_launch(c, r.dbase, offs.data(), chunk_lens, n, r.dside, r.s));
+    // The parity comes back into the staging at its own offsets; the data chunks between two
+    // parts' parity travel along while they are short (copy_spans).
+    CEC_TRY(copy_spans(r.stage, r.dbase, parity, false, r.s));
+    HIP_TRY(hipMemcpyAsync(a.out.ptr, r.dside, n * t * 32, hipMemcpyDeviceToHost, r.s));
+    HIP_TRY(hipStreamSynchronize(r.s));
+    for_parts(n, out_bytes, [&](size_t k) {
+        const size_t L = chunk_lens[k];
+        for (size_t i = 0; i < p; ++i)
+            std::memcpy(parity_outs[k] + i * L, r.stage + parity[k].first + i * ragged_stride(L), L);
+    });
+    std::memcpy(digests_out, a.out.ptr, n * t * 32);
+    return CEC_OK;
+}
+
+// Whether the call fills slot i of a part when it is not among the verified chunks.
+inline bool fills_slot(size_t i, size_t d, bool data_only) { return i < d || !data_only; }
+
+// One round of cec_parts_read: parts [0, n) of these arrays.  The loaded chunks are packed into
+// the arena and moved up, verified and rebuilt as in cec_read_ragged, and only the rebuilt chunks
+// come back, into the caller's slots.
+int parts_read_round(cec_codec* c, Arena& a, uint8_t* const* shards, const size_t* chunk_lens,
+                     size_t n, const uint8_t* present, const uint8_t* expected, bool data_only,
+                     uint8_t* verified, int* part_status) {
+    const size_t d = c->d, t = c->d + c->p, items = n * t;
+    Round r;
+    CEC_TRY(reserve_round(a, d, t, chunk_lens, n, &r));
+    // fn(item, its offset in the arena, L) for every chunk slot i of part k that passes pick(k, i)
+    auto slots = [&](size_t k, auto pick, auto fn) {
+        const size_t L = chunk_lens[k], cs = ragged_stride(L);
+        for (size_t i = 0; i < t; ++i)
+            if (pick(k, i)) fn(k * t + i, r.offs[k] + i * cs, L);
+    };
+    auto spans_of = [&](auto pick, Spans* spans) {
+        size_t bytes = 0;
+        for (size_t k = 0; k < n; ++k)
+            slots(k, pick, [&](size_t, size_t off, size_t L) {
+                spans->emplace_back(off, off + L);
+                bytes += L;
+            });
+        return bytes;
+    };
+    auto loaded = [&](size_t k, size_t i) { return present[k * t + i] != 0; };
+    Spans spans;
+    const size_t in_bytes = spans_of(loaded, &spans);
+    for_parts(n, in_bytes, [&](size_t k) {
+        slots(k, loaded, [&](size_t item, size_t off, size_t L) {
+            std::memcpy(r.stage + off, shards[item], L);
+        });
+    });
+    std::memcpy(a.out.ptr, expected, items * 32);
+    HIP_TRY(hipMemcpyAsync(r.dside, a.out.ptr, items * 32, hipMemcpyHostToDevice, r.s));
+    CEC_TRY(copy_spans(r.stage, r.dbase, spans, true, r.s));
+    CEC_TRY(read_ragged(c, r.dbase, r.offs.data(), chunk_lens, n, present, r.dside, verified,
+                        part_status, data_only, r.s));
+    // what the rebuild wrote: in a decodable part, every slot of the mode that did not verify
+    auto rebuilt = [&](size_t k, size_t i) {
+        return part_status[k] == CEC_OK && !verified[k * t + i] && fills_slot(i, d, data_only);
+    };
+    spans.clear();
+    const size_t out_bytes = spans_of(rebuilt, &spans);
+    CEC_TRY(copy_spans(r.stage, r.dbase, spans, false, r.s));
+    HIP_TRY(hipStreamSynchronize(r.s));
+    for_parts(n, out_bytes, [&](size_t k) {
+        slots(k, rebuilt, [&](size_t item, size_t off, size_t L) {
+            std::memcpy(shards[item], r.stage + off, L);
+        });
+    });
+    return CEC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t cec_ragged_stride(size_t chunk_len) { return ragged_stride(chunk_len); }
+
+int cec_ragged_layout(size_t total_shards, const size_t* chunk_lens, size_t n_parts,
+                      size_t* part_offsets, size_t* total_bytes) {
+    if (!total_bytes || total_shards == 0) return CEC_ERR_INVALID_ARGUMENT;
+    if (n_parts && (!chunk_lens || !part_offsets)) return CEC_ERR_INVALID_ARGUMENT;
+    return ragged_layout(total_shards, chunk_lens, n_parts, part_offsets, total_bytes);
+}
+
+int cec_encode_hash_ragged(const cec_codec* cc, uint8_t* base, const size_t* part_offsets,
+                           const size_t* chunk_lens, size_t n_parts, uint8_t* digests,
+                           void* stream) {
+    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
+    if (n_parts == 0) return CEC_OK;
+    if (!base || !part_offsets || !chunk_lens || !digests) return CEC_ERR_INVALID_ARGUMENT;
+    CEC_TRY(ragged_check(cc, base, part_offsets, chunk_lens, n_parts));
+    return ragged_launch(const_cast<cec_codec*>(cc), base, part_offsets, chunk_lens, n_parts,
+                         digests, static_cast<hipStream_t>(stream));
+}
+
+int cec_parts_encode(const cec_codec* cc, const uint8_t* const* data_bufs, const size_t* lengths,
+                     size_t n_parts, uint8_t* const* parity_outs, uint8_t* digests_out,
+                     size_t* chunksizes) {
+    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
+    if (n_parts == 0) return CEC_OK;
+    if (!data_bufs || !lengths || !parity_outs || !digests_out || !chunksizes)
+        return CEC_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < n_parts; ++k)
+        if (lengths[k] == 0) return CEC_EMPTY_SHARD;
+    for (size_t k = 0; k < n_parts; ++k)
+        if (!data_bufs[k] || !parity_outs[k]) return CEC_ERR_INVALID_ARGUMENT;
+    cec_codec* c = const_cast<cec_codec*>(cc);
+    const size_t t = c->d + c->p;
+    std::vector<size_t> L(n_parts);
+    for (size_t k = 0; k < n_parts; ++k) L[k] = (lengths[k] - 1) / c->d + 1;
+    CEC_TRY(run_rounds(c, L.data(), n_parts, [&](Arena& a, size_t k0, size_t k1) {
+        return parts_round(c, a, data_bufs + k0, lengths + k0, k1 - k0, parity_outs + k0,
+                           digests_out + k0 * t * 32, L.data() + k0);
+    }));
+    std::copy(L.begin(), L.end(), chunksizes);
+    return CEC_OK;
+}
+
+int cec_reconstruct_ragged(const cec_codec* cc, uint8_t* base, const size_t* part_offsets,
+                           const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                           int data_only, void* stream) {
+    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
+    if (n_parts == 0) return CEC_OK;
+    if (!base || !part_offsets || !chunk_lens || !present) return CEC_ERR_INVALID_ARGUMENT;
+    CEC_TRY(ragged_check(cc, base, part_offsets, chunk_lens, n_parts));
+    CEC_TRY(check_present(cc->d, cc->d + cc->p, present, n_parts));
+    int dev = 0;
+    CEC_TRY(current_device(&dev));
+    return reconstruct_ragged(const_cast<cec_codec*>(cc), base, part_offsets, chunk_lens, n_parts,
+                              present, data_only != 0, static_cast<hipStream_t>(stream));
+}
+
+int cec_read_ragged(const cec_codec* c, uint8_t* base, const size_t* part_offsets,
+                    const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                    const uint8_t* expected, uint8_t* verified, int* part_status, void* stream) {
+    return read_ragged_checked(c, base, part_offsets, chunk_lens, n_parts, present, expected,
+                               verified, part_status, true, stream);
+}
+
+int cec_resilver_ragged(const cec_codec* c, uint8_t* base, const size_t* part_offsets,
+                        const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                        const uint8_t* expected, uint8_t* verified, int* part_status,
+                        void* stream) {
+    return read_ragged_checked(c, base, part_offsets, chunk_lens, n_parts, present, expected,
+                               verified, part_status, false, stream);
+}
+
+int cec_parts_read(const cec_codec* cc, uint8_t* const* shards, const size_t* chunk_lens,
+                   size_t n_parts, const uint8_t* present, const uint8_t* expected, int data_only,
+                   uint8_t* verified, int* part_status) {
+    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
+    if (n_parts == 0) return CEC_OK;
+    if (!shards || !chunk_lens || !present || !expected || !verified || !part_status)
+        return CEC_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < n_parts; ++k)
+        if (chunk_lens[k] == 0) return CEC_EMPTY_SHARD;
+    cec_codec* c = const_cast<cec_codec*>(cc);
+    const size_t d = c->d, t = c->d + c->p;
+    size_t items = 0;
+    if (__builtin_mul_overflow(n_parts, t, &items) || items > 0xFFFFFFFFull)
+        return CEC_ERR_INVALID_ARGUMENT;
+    // A loaded chunk needs its bytes; a part that can be decoded (d or more chunks loaded) needs
+    // memory behind every slot the mode fills.
+    for (size_t k = 0; k < n_parts; ++k) {
+        size_t loaded = 0;
+        for (size_t i = 0; i < t; ++i) loaded += present[k * t + i] ? 1 : 0;
+        for (size_t i = 0; i < t; ++i) {
+            const bool need = present[k * t + i] || (loaded >= d && fills_slot(i, d, data_only != 0));
+            if (need && !shards[k * t + i]) {
+                set_last_error("cec_parts_read: a chunk slot that is read or filled is NULL");
+                return CEC_ERR_INVALID_ARGUMENT;
+            }
+        }
+    }
+    return run_rounds(c, chunk_lens, n_parts, [&](Arena& a, size_t k0, size_t k1) {
+        return parts_read_round(c, a, shards + k0 * t, chunk_lens + k0, k1 - k0, present + k0 * t,
+                                expected + k0 * t * 32, data_only != 0, verified + k0 * t,
+                                part_status + k0);
+    });
+}
+
+}  // extern "C"

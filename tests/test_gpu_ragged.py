@@ -188,6 +188,20 @@ def test_parts_encode_equals_part_encode(d, p):
         assert [h.digest for h in one.hashes] == [h.digest for h in enc.hashes]
 
 
+def test_parts_encode_parity_copy_back_merge_boundary():
+    """The parity comes back from the device in copies that neighbouring parts share until the
+    data chunks between two parts' parity reach 256 KiB.  RS(3,2) chunk lengths that put that gap
+    (d * stride) just under it (262 128), just over it (262 176) and on an unaligned length with
+    the same stride, 16-byte parts between them: every part's parity must still arrive."""
+    d, p = 3, 2
+    chunk_lens = [16, 87376, 16, 87392, 16, 87381, 16]
+    assert [d * _stride(L) for L in chunk_lens[1::2]] == [262128, 262176, 262176]
+    assert 262128 < (256 << 10) < 262176
+    bufs = [gen_bytes(80 + k, d * L).tobytes() for k, L in enumerate(chunk_lens)]
+    encs = ce.parts_encode(ce.ReedSolomon(d, p), bufs)
+    _check_parts(d, p, bufs, encs)
+
+
 def test_parts_encode_rounds(knob_env):
     """A 1 MiB cap cuts about 3 MiB of parts plus one 2 MiB part into several rounds (the large
     part alone); the results are the same."""
