@@ -136,6 +136,8 @@ _sig("cec_resilver_ragged", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp, _
                              ctypes.POINTER(ctypes.c_int), _vp])
 _sig("cec_parts_read", [_vp, ctypes.POINTER(_u8p), _szp, ctypes.c_size_t, _u8p, _u8p, ctypes.c_int,
                         _u8p, ctypes.POINTER(ctypes.c_int)])
+_sig("cec_verify_ragged", [ctypes.c_size_t, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp, _u8p, _vp])
+_sig("cec_parts_verify", [ctypes.POINTER(_u8p), _szp, ctypes.c_size_t, _u8p, _u8p])
 _sig("cec_coalesce_stats", [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
      None)
 _sig("cec_encode_batch", [_vp, ctypes.POINTER(PartBatchStruct), _vp])
@@ -779,6 +781,47 @@ def parts_read(codec: ReedSolomon, parts: Sequence[Sequence], expected: Sequence
                 row.append(None)
         out.append(row)
     return out, bytes(verified), list(status)
+
+
+def verify_ragged(total_shards: int, base_ptr: int, part_offsets: Sequence[int],
+                  chunk_lens: Sequence[int], present, expected_ptr: int, stream=None) -> bytes:
+    """The verification half of :func:`read_ragged` alone (``cec_verify_ragged``):
+    FilePart::verify's compute over device memory at ``base_ptr`` in the layout of
+    :func:`ragged_layout` with ``total_shards`` chunks per part; nothing is rebuilt or written.
+    ``present``: host flags ``n*total_shards`` or ``None`` (every chunk present);
+    ``expected_ptr``: device digests ``[n][total_shards][32]``.  Returns the verified flags."""
+    offs, lens, n = _ragged_args(part_offsets, chunk_lens)
+    items = n * total_shards
+    pres, c_pres = None, None  # NULL: every chunk present
+    if present is not None:
+        pres = bytes(present)
+        assert len(pres) == items
+        c_pres = ctypes.cast(ctypes.c_char_p(pres), _u8p)
+    verified = (ctypes.c_uint8 * max(items, 1))()
+    _check(_lib.cec_verify_ragged(total_shards, base_ptr, offs, lens, n, c_pres, expected_ptr,
+                                  verified, _stream_ptr(stream)))
+    return bytes(verified)[:items]
+
+
+def parts_verify(copies: Sequence, expected: Sequence) -> bytes:
+    """FilePart::verify's compute for a flat list of chunk copies of unrelated lengths in ONE
+    engine call (``cec_parts_verify``): flag i of the result is 1 iff
+    ``SHA-256(copies[i]) == expected[i]`` (32 bytes each).  An entry is a copy, not a chunk: a
+    chunk with three locations is three entries with the same digest."""
+    n = len(copies)
+    if len(expected) != n:
+        raise ValueError("copies and expected differ in length")
+    if n == 0:
+        return b""
+    keep: list = []
+    ptrs = (_u8p * n)(*[_buf_ptr(b, keep) for b in copies])
+    lens = (ctypes.c_size_t * n)(*[_nbytes(b) for b in copies])
+    exp = b"".join(bytes(h) for h in expected)
+    if len(exp) != n * 32:
+        raise ValueError("expected: one digest of 32 bytes per copy")
+    ok = (ctypes.c_uint8 * n)()
+    _check(_lib.cec_parts_verify(ptrs, lens, n, ctypes.cast(ctypes.c_char_p(exp), _u8p), ok))
+    return bytes(ok)
 
 
 def fill_synthetic(batch: PartBatch, n_chunks: int, seed: int, stream=None) -> None:

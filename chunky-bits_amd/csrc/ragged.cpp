@@ -1,8 +1,9 @@
 // ragged.cpp — the ragged half of include/chunky_ec.h: parts of different chunk lengths in one
-// launch sequence (cec_encode_hash_ragged, cec_reconstruct_ragged, cec_read_ragged,
-// cec_resilver_ragged) and the host-staged calls on top of them (cec_parts_encode,
-// cec_parts_read).  Part k's chunk i lies at base + off[k] + i * stride(L_k), stride = L rounded
-// up to 16.  Host work only; every step of the path has one home here.
+// launch sequence (cec_encode_hash_ragged, cec_reconstruct_ragged, cec_verify_ragged,
+// cec_read_ragged, cec_resilver_ragged) and the host-staged calls on top of them
+// (cec_parts_encode, cec_parts_read, cec_parts_verify).  Part k's chunk i lies at
+// base + off[k] + i * stride(L_k), stride = L rounded up to 16.  Host work only; every step of
+// the path has one home here.
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -39,11 +40,9 @@ int ragged_layout(size_t t, const size_t* lens, size_t n, size_t* offs, size_t* 
     return CEC_OK;
 }
 
-// Every argument check of a ragged layout (no device use), the bound on the launch's work units
-// among them.
-int ragged_check(const cec_codec* c, const uint8_t* base, const size_t* offs, const size_t* lens,
-                 size_t n) {
-    const size_t t = c->d + c->p;
+// Every argument check of a ragged layout of t chunks per part (no device use), the bound on the
+// launch's work units among them.
+int ragged_check(size_t t, const uint8_t* base, const size_t* offs, const size_t* lens, size_t n) {
     size_t items = 0;  // SHA-256 items are 32-bit (checked before the arrays are walked)
     if (__builtin_mul_overflow(n, t, &items) || items > 0xFFFFFFFFull)
         return CEC_ERR_INVALID_ARGUMENT;
@@ -93,7 +92,7 @@ uint32_t part_records(const size_t* offs, const size_t* lens, const uint32_t* id
 // similar lengths.  Digests and flags land at their item's place whatever the order.  An item's
 // key is its part's, so the parts are sorted and each expanded in place.  Returns the items listed.
 template <typename Pick>
-size_t sha_list(uint8_t* base, const size_t* offs, const size_t* lens, size_t n, size_t t,
+size_t sha_list(const uint8_t* base, const size_t* offs, const size_t* lens, size_t n, size_t t,
                 Pick pick, uint64_t* ptrs, uint64_t* h_len, uint32_t* order) {
     std::vector<uint32_t> by_len(n);
     std::iota(by_len.begin(), by_len.end(), 0u);
@@ -201,16 +200,15 @@ int reconstruct_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const si
     return CEC_OK;
 }
 
-// Shared body of cec_read_ragged / cec_resilver_ragged for a checked layout: on `s` the SHA-256
-// list launch in verify mode over the chunks that need hashing (ok and expected indexed by
-// k*(d+p)+i), the readback of the flags (the one wait), then the rebuild of every decodable part
-// from its first d verified chunks.
-// No speculative decode beside the verification: the chains of a ragged batch are short and
-// nobody has measured whether it pays (DESIGN.md §4.8, not built).
-int read_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* lens, size_t n,
-                const uint8_t* present, const uint8_t* expected, uint8_t* verified,
-                int* part_status, bool data_only, hipStream_t s) {
-    const size_t d = c->d, t = c->d + c->p, items = n * t;
+// The verification half of the ragged read side for a checked layout of t chunks per part: on `s`
+// the SHA-256 list launch in verify mode over the chunks that need hashing (present null: all of
+// them; ok and expected indexed by k*t+i), then the readback of the flags, the one wait.
+// `verified` is written once they are back: the kernel's flag for a hashed chunk, 1 for a
+// CEC_PRESENT_VERIFIED one, 0 for an absent one.  Nothing of `base` is written.
+int verify_ragged(const uint8_t* base, const size_t* offs, const size_t* lens, size_t n, size_t t,
+                  const uint8_t* present, const uint8_t* expected, uint8_t* verified,
+                  hipStream_t s) {
+    const size_t items = n * t;
     // [ptrs u64 x items][lens u64 x items][order u32 x items][ok u8 x items]
     const size_t o_len = items * 8, o_ord = o_len + items * 8, o_ok = o_ord + items * 4,
                  bytes = o_ok + items;
@@ -219,7 +217,7 @@ int read_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* l
     uint8_t* ok = sc.dev() + o_ok;
     HIP_TRY(hipMemsetAsync(ok, 0, items, s));
     const size_t hashed = sha_list(
-        base, offs, lens, n, t, [&](size_t item) { return needs_hash(present[item]); },
+        base, offs, lens, n, t, [&](size_t item) { return !present || needs_hash(present[item]); },
         reinterpret_cast<uint64_t*>(sc.host()), reinterpret_cast<uint64_t*>(sc.host() + o_len),
         reinterpret_cast<uint32_t*>(sc.host() + o_ord));
     if (hashed) {
@@ -240,6 +238,21 @@ int read_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* l
     HIP_TRY(hipMemcpyAsync(sc.host() + o_ok, ok, items, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     std::memcpy(verified, sc.host() + o_ok, items);
+    for (size_t i = 0; present && i < items; ++i)  // trusted, not hashed
+        if (present[i] == CEC_PRESENT_VERIFIED) verified[i] = 1;
+    return CEC_OK;
+}
+
+// Shared body of cec_read_ragged / cec_resilver_ragged for a checked layout: the verification
+// (verify_ragged), then on `s` the rebuild of every decodable part from its first d verified
+// chunks.
+// No speculative decode beside the verification: the chains of a ragged batch are short and
+// nobody has measured whether it pays (DESIGN.md §4.8, not built).
+int read_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* lens, size_t n,
+                const uint8_t* present, const uint8_t* expected, uint8_t* verified,
+                int* part_status, bool data_only, hipStream_t s) {
+    const size_t d = c->d, t = c->d + c->p;
+    CEC_TRY(verify_ragged(base, offs, lens, n, t, present, expected, verified, s));
     std::vector<uint8_t> pres;
     rebuild_mask(d, t, n, present, verified, part_status, false, &pres);
     return reconstruct_ragged(c, base, offs, lens, n, pres.data(), data_only, s);
@@ -253,15 +266,16 @@ int read_ragged_checked(const cec_codec* cc, uint8_t* base, const size_t* offs, 
     if (n == 0) return CEC_OK;
     if (!base || !offs || !lens || !present || !expected || !verified || !part_status)
         return CEC_ERR_INVALID_ARGUMENT;
-    CEC_TRY(ragged_check(cc, base, offs, lens, n));
+    CEC_TRY(ragged_check(cc->d + cc->p, base, offs, lens, n));
     int dev = 0;
     CEC_TRY(current_device(&dev));
     return read_ragged(const_cast<cec_codec*>(cc), base, offs, lens, n, present, expected,
                        verified, part_status, data_only, static_cast<hipStream_t>(stream));
 }
 
-// Host staged (cec_parts_encode, cec_parts_read): the parts packed into an arena's pinned staging
-// in the cec_ragged_layout layout, moved up, worked on as above, results copied out.
+// Host staged (cec_parts_encode, cec_parts_read, cec_parts_verify): the parts packed into an
+// arena's pinned staging in the cec_ragged_layout layout, moved up, worked on as above, results
+// copied out.
 
 // Their arenas: one per call in flight.
 ArenaPool& ragged_arenas() {
@@ -333,13 +347,13 @@ int reserve_round(Arena& a, size_t d, size_t t, const size_t* chunk_lens, size_t
     return CEC_OK;
 }
 
-// The rounds of a host-staged call over parts of these chunk lengths: at most
-// CEC_COALESCE_MAX_MIB of (padded) data chunks each, a larger part alone.  Every round is checked
-// before the first one runs, so an error leaves the outputs untouched.  Then round(arena, k0, k1)
-// for each, on one arena; nothing of a failed round stays in flight.
+// The rounds of a host-staged call over parts of d data chunks among t, of these chunk lengths:
+// at most CEC_COALESCE_MAX_MIB of (padded) data chunks each, a larger part alone.  Every round is
+// checked before the first one runs, so an error leaves the outputs untouched.  Then
+// round(arena, k0, k1) for each, on one arena; nothing of a failed round stays in flight.
 template <typename Fn>
-int run_rounds(const cec_codec* c, const size_t* chunk_lens, size_t n, Fn round) {
-    const size_t d = c->d, t = c->d + c->p, cap = coalesce_max_bytes();
+int run_rounds(size_t d, size_t t, const size_t* chunk_lens, size_t n, Fn round) {
+    const size_t cap = coalesce_max_bytes();
     std::vector<size_t> round_end;
     size_t bytes = 0, first = 0;
     for (size_t k = 0; k < n; ++k) {
@@ -358,7 +372,7 @@ int run_rounds(const cec_codec* c, const size_t* chunk_lens, size_t n, Fn round)
     size_t k0 = 0, total = 0;
     for (size_t k1 : round_end) {
         CEC_TRY(ragged_layout(t, chunk_lens + k0, k1 - k0, offs.data(), &total));
-        CEC_TRY(ragged_check(c, nullptr, offs.data(), chunk_lens + k0, k1 - k0));
+        CEC_TRY(ragged_check(t, nullptr, offs.data(), chunk_lens + k0, k1 - k0));
         k0 = k1;
     }
     int dev = 0;
@@ -478,6 +492,24 @@ int parts_read_round(cec_codec* c, Arena& a, uint8_t* const* shards, const size_
     return CEC_OK;
 }
 
+// One round of cec_parts_verify: copies [0, n) of these arrays, a ragged layout of one chunk per
+// part.  The copies are packed into the arena and moved up in one copy (the padding between them,
+// under 16 bytes each, travels along), verified as in cec_verify_ragged, and only the flags come
+// back.
+int parts_verify_round(Arena& a, const uint8_t* const* bufs, const size_t* lens, size_t n,
+                       const uint8_t* expected, uint8_t* ok) {
+    Round r;
+    CEC_TRY(reserve_round(a, 1, 1, lens, n, &r));
+    size_t in_bytes = 0;
+    for (size_t k = 0; k < n; ++k) in_bytes += lens[k];
+    for_parts(n, in_bytes, [&](size_t k) { std::memcpy(r.stage + r.offs[k], bufs[k], lens[k]); });
+    std::memcpy(a.out.ptr, expected, n * 32);
+    HIP_TRY(hipMemcpyAsync(r.dside, a.out.ptr, n * 32, hipMemcpyHostToDevice, r.s));
+    HIP_TRY(hipMemcpyAsync(r.dbase, r.stage, r.offs[n - 1] + lens[n - 1], hipMemcpyHostToDevice,
+                           r.s));
+    return verify_ragged(r.dbase, r.offs.data(), lens, n, 1, nullptr, r.dside, ok, r.s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -497,7 +529,7 @@ int cec_encode_hash_ragged(const cec_codec* cc, uint8_t* base, const size_t* par
     if (!cc) return CEC_ERR_INVALID_ARGUMENT;
     if (n_parts == 0) return CEC_OK;
     if (!base || !part_offsets || !chunk_lens || !digests) return CEC_ERR_INVALID_ARGUMENT;
-    CEC_TRY(ragged_check(cc, base, part_offsets, chunk_lens, n_parts));
+    CEC_TRY(ragged_check(cc->d + cc->p, base, part_offsets, chunk_lens, n_parts));
     return ragged_launch(const_cast<cec_codec*>(cc), base, part_offsets, chunk_lens, n_parts,
                          digests, static_cast<hipStream_t>(stream));
 }
@@ -517,7 +549,7 @@ int cec_parts_encode(const cec_codec* cc, const uint8_t* const* data_bufs, const
     const size_t t = c->d + c->p;
     std::vector<size_t> L(n_parts);
     for (size_t k = 0; k < n_parts; ++k) L[k] = (lengths[k] - 1) / c->d + 1;
-    CEC_TRY(run_rounds(c, L.data(), n_parts, [&](Arena& a, size_t k0, size_t k1) {
+    CEC_TRY(run_rounds(c->d, t, L.data(), n_parts, [&](Arena& a, size_t k0, size_t k1) {
         return parts_round(c, a, data_bufs + k0, lengths + k0, k1 - k0, parity_outs + k0,
                            digests_out + k0 * t * 32, L.data() + k0);
     }));
@@ -531,12 +563,26 @@ int cec_reconstruct_ragged(const cec_codec* cc, uint8_t* base, const size_t* par
     if (!cc) return CEC_ERR_INVALID_ARGUMENT;
     if (n_parts == 0) return CEC_OK;
     if (!base || !part_offsets || !chunk_lens || !present) return CEC_ERR_INVALID_ARGUMENT;
-    CEC_TRY(ragged_check(cc, base, part_offsets, chunk_lens, n_parts));
+    CEC_TRY(ragged_check(cc->d + cc->p, base, part_offsets, chunk_lens, n_parts));
     CEC_TRY(check_present(cc->d, cc->d + cc->p, present, n_parts));
     int dev = 0;
     CEC_TRY(current_device(&dev));
     return reconstruct_ragged(const_cast<cec_codec*>(cc), base, part_offsets, chunk_lens, n_parts,
                               present, data_only != 0, static_cast<hipStream_t>(stream));
+}
+
+int cec_verify_ragged(size_t total_shards, const uint8_t* base, const size_t* part_offsets,
+                      const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                      const uint8_t* expected, uint8_t* verified, void* stream) {
+    if (total_shards == 0) return CEC_ERR_INVALID_ARGUMENT;
+    if (n_parts == 0) return CEC_OK;
+    if (!base || !part_offsets || !chunk_lens || !expected || !verified)
+        return CEC_ERR_INVALID_ARGUMENT;
+    CEC_TRY(ragged_check(total_shards, base, part_offsets, chunk_lens, n_parts));
+    int dev = 0;
+    CEC_TRY(current_device(&dev));
+    return verify_ragged(base, part_offsets, chunk_lens, n_parts, total_shards, present, expected,
+                         verified, static_cast<hipStream_t>(stream));
 }
 
 int cec_read_ragged(const cec_codec* c, uint8_t* base, const size_t* part_offsets,
@@ -581,10 +627,27 @@ int cec_parts_read(const cec_codec* cc, uint8_t* const* shards, const size_t* ch
             }
         }
     }
-    return run_rounds(c, chunk_lens, n_parts, [&](Arena& a, size_t k0, size_t k1) {
+    return run_rounds(d, t, chunk_lens, n_parts, [&](Arena& a, size_t k0, size_t k1) {
         return parts_read_round(c, a, shards + k0 * t, chunk_lens + k0, k1 - k0, present + k0 * t,
                                 expected + k0 * t * 32, data_only != 0, verified + k0 * t,
                                 part_status + k0);
+    });
+}
+
+int cec_parts_verify(const uint8_t* const* bufs, const size_t* lens, size_t n,
+                     const uint8_t* expected, uint8_t* ok) {
+    if (n == 0) return CEC_OK;
+    if (!bufs || !lens || !expected || !ok) return CEC_ERR_INVALID_ARGUMENT;
+    if (n > 0xFFFFFFFFull) return CEC_ERR_INVALID_ARGUMENT;  // before the arrays are walked
+    for (size_t i = 0; i < n; ++i)
+        if (lens[i] == 0) return CEC_EMPTY_SHARD;
+    for (size_t i = 0; i < n; ++i)
+        if (!bufs[i]) {
+            set_last_error("cec_parts_verify: a copy is NULL");
+            return CEC_ERR_INVALID_ARGUMENT;
+        }
+    return run_rounds(1, 1, lens, n, [&](Arena& a, size_t k0, size_t k1) {
+        return parts_verify_round(a, bufs + k0, lens + k0, k1 - k0, expected + k0 * 32, ok + k0);
     });
 }
 

@@ -178,6 +178,24 @@ pub mod sys {
             verified: *mut u8,
             part_status: *mut c_int,
         ) -> c_int;
+        pub fn cec_parts_verify(
+            bufs: *const *const u8,
+            lens: *const usize,
+            n: usize,
+            expected: *const u8,
+            ok: *mut u8,
+        ) -> c_int;
+        pub fn cec_verify_ragged(
+            total_shards: usize,
+            base: *const u8,
+            part_offsets: *const usize,
+            chunk_lens: *const usize,
+            n_parts: usize,
+            present: *const u8,
+            expected: *const u8,
+            verified: *mut u8,
+            stream: *mut c_void,
+        ) -> c_int;
         pub fn cec_reconstruct_ragged(
             codec: *const cec_codec,
             base: *mut u8,
@@ -997,6 +1015,77 @@ pub fn parts_read(
         )
     })?;
     Ok((verified, status))
+}
+
+/// `cec_verify_ragged`: the verification half of [`read_ragged`] alone (`FilePart::verify`'s
+/// compute over the ragged layout of `total_shards` chunks per part); nothing is rebuilt or
+/// written.  `present` holds `n * total_shards` flags, `None` = every chunk present.  Returns the
+/// verified flags.
+///
+/// # Safety
+/// `base` must be a device pointer covering the layout the offsets and lengths describe,
+/// `expected` a device pointer to `n * total_shards * 32` bytes; `stream` a HIP stream of the
+/// current device or null.
+pub unsafe fn verify_ragged(
+    total_shards: usize,
+    base: *const u8,
+    part_offsets: &[usize],
+    chunk_lens: &[usize],
+    present: Option<&[u8]>,
+    expected: *const u8,
+    stream: *mut c_void,
+) -> Result<Vec<u8>, CecError> {
+    let n = chunk_lens.len();
+    let items = n * total_shards;
+    if part_offsets.len() != n || present.map_or(false, |f| f.len() != items) {
+        return Err(CecError::Engine(EngineError {
+            code: 101,
+            message: "part_offsets, chunk_lens and present differ in length".to_string(),
+        }));
+    }
+    let mut verified = vec![0u8; items];
+    check(sys::cec_verify_ragged(
+        total_shards,
+        base,
+        part_offsets.as_ptr(),
+        chunk_lens.as_ptr(),
+        n,
+        present.map_or(std::ptr::null(), |f| f.as_ptr()),
+        expected,
+        verified.as_mut_ptr(),
+        stream,
+    ))?;
+    Ok(verified)
+}
+
+/// `cec_parts_verify`: `FilePart::verify`'s compute for a flat list of chunk copies of unrelated
+/// lengths in one engine call.  Flag i of the result is 1 iff `SHA-256(copies[i]) == expected[i]`.
+/// An entry is a copy, not a chunk: a chunk with three locations is three entries with the same
+/// digest.
+pub fn parts_verify(copies: &[&[u8]], expected: &[[u8; 32]]) -> Result<Vec<u8>, CecError> {
+    let n = copies.len();
+    if expected.len() != n {
+        return Err(CecError::Engine(EngineError {
+            code: 101,
+            message: "copies and expected differ in length".to_string(),
+        }));
+    }
+    if n == 0 {
+        return Ok(Vec::new());
+    }
+    let ptrs: Vec<*const u8> = copies.iter().map(|b| b.as_ptr()).collect();
+    let lens: Vec<usize> = copies.iter().map(|b| b.len()).collect();
+    let mut ok = vec![0u8; n];
+    check(unsafe {
+        sys::cec_parts_verify(
+            ptrs.as_ptr(),
+            lens.as_ptr(),
+            n,
+            expected.as_ptr() as *const u8,
+            ok.as_mut_ptr(),
+        )
+    })?;
+    Ok(ok)
 }
 
 /// Batched `FileWriteBuilder::write` compute (writer.rs:166-231): `depth` slots of

@@ -24,6 +24,10 @@
  *                                                          -> cec_reconstruct_batch, cec_sha256_batch
  *     FilePart::resilver compute (file_part.rs:266-308)    -> cec_reconstruct_batch (data_only = 0)
  *     FilePart::verify (file_part.rs:228-251)              -> cec_sha256_batch
+ *   and, for parts whose chunk lengths differ (whole small files, short last parts), the ragged
+ *   forms of the four: cec_parts_encode / cec_encode_hash_ragged (write), cec_parts_read /
+ *   cec_read_ragged (read), cec_parts_read / cec_resilver_ragged (resilver), cec_parts_verify /
+ *   cec_verify_ragged (verify).
  *
  * Conventions
  *   - Plain pointers and sizes only; every buffer is owned by the caller.
@@ -220,6 +224,21 @@ int cec_parts_read(const cec_codec* codec, uint8_t* const* shards, const size_t*
                    size_t n_parts, const uint8_t* present, const uint8_t* expected,
                    int data_only, uint8_t* verified, int* part_status);
 
+/* FilePart::verify's compute (file_part.rs:228-251: every location's copy of every chunk hashed
+ * and compared) for a flat list of n chunk copies of unrelated lengths in one call:
+ * ok[i] = 1 iff SHA-256(bufs[i][0..lens[i])) == expected[i*32 .. +32].  expected is a HOST array
+ * [n][32], ok a HOST array [n].  An entry is a copy, not a chunk slot: a chunk with three
+ * locations is three entries with the same digest.  The copies are packed 16-byte aligned into
+ * one staging area, moved up in one copy and verified as a cec_verify_ragged layout of
+ * total_shards = 1; only the n flags come back.  A call with more than CEC_COALESCE_MAX_MIB of
+ * copies runs in several rounds, a single larger copy alone; every round is checked before the
+ * first one runs.  Errors, before any device use and with ok untouched: null pointer ->
+ * CEC_ERR_INVALID_ARGUMENT; any lens[i] == 0 -> CEC_EMPTY_SHARD; a NULL bufs[i], or n beyond the
+ * 32-bit item index (checked before the arrays are walked) -> CEC_ERR_INVALID_ARGUMENT; then
+ * CEC_ERR_NO_DEVICE.  n == 0 -> CEC_OK.  Concurrent calls are allowed. */
+int cec_parts_verify(const uint8_t* const* bufs, const size_t* lens, size_t n,
+                     const uint8_t* expected, uint8_t* ok);
+
 /* Per-call coalescing.  Concurrent cec_part_encode calls with the same codec and chunk length
  * (and concurrent cec_sha256 / cec_sha256_many calls) on the same device are gathered into one
  * launch: the first caller waits up to CEC_COALESCE_US microseconds (environment, default 200,
@@ -348,10 +367,26 @@ int cec_resilver_batch(const cec_codec* codec, const cec_part_batch* batch,
  * CEC_ERR_INVALID_ARGUMENT (n_parts == 0 with a codec -> CEC_OK, nothing launched); any
  * chunk_lens[k] == 0 -> CEC_EMPTY_SHARD; then the layout errors of cec_encode_hash_ragged ->
  * CEC_ERR_INVALID_ARGUMENT; then cec_reconstruct_ragged's CEC_TOO_FEW_SHARDS_PRESENT; then
- * CEC_ERR_NO_DEVICE. */
+ * CEC_ERR_NO_DEVICE.
+ * cec_verify_ragged: the verification half of cec_read_ragged alone (FilePart::verify's compute
+ * over the ragged layout); nothing is rebuilt and not one byte of base is written.  It takes no
+ * codec: total_shards plays the role it plays in cec_ragged_layout, and with total_shards = 1 the
+ * layout is a flat list of independent buffers.  present: HOST [n_parts][total_shards], NULL =
+ * every chunk present; expected: DEVICE [n_parts][total_shards][32]; verified: HOST output
+ * [n_parts][total_shards]: a chunk flagged nonzero and not CEC_PRESENT_VERIFIED is hashed and
+ * gets 1 iff the digests are equal, a CEC_PRESENT_VERIFIED chunk is trusted, not hashed, and
+ * gets 1, an absent chunk is not read and gets 0.  On `stream`: the hashing (the chunks to hash,
+ * longest first), then the readback of the flags, the one wait.  Errors, all before any device
+ * use and with verified untouched: null pointer (present excepted) or total_shards == 0 ->
+ * CEC_ERR_INVALID_ARGUMENT (n_parts == 0 -> CEC_OK, nothing launched); any chunk_lens[k] == 0
+ * -> CEC_EMPTY_SHARD; then the layout errors of cec_encode_hash_ragged ->
+ * CEC_ERR_INVALID_ARGUMENT; then CEC_ERR_NO_DEVICE. */
 int cec_reconstruct_ragged(const cec_codec* codec, uint8_t* base, const size_t* part_offsets,
                            const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
                            int data_only, void* stream);
+int cec_verify_ragged(size_t total_shards, const uint8_t* base, const size_t* part_offsets,
+                      const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                      const uint8_t* expected, uint8_t* verified, void* stream);
 int cec_read_ragged(const cec_codec* codec, uint8_t* base, const size_t* part_offsets,
                     const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
                     const uint8_t* expected, uint8_t* verified, int* part_status, void* stream);

@@ -951,7 +951,258 @@ struct FileReference {
         return r;
     }
 
+    // verify() for many files in one go (a scrub): result[f] equals files[f]->verify(src,
+    // parts_per_batch, depth, devices).  Runs of two or more parts of one shape still go through
+    // check_run when parts_per_batch is set; every other part of every file (whole small files,
+    // short last parts, every part when parts_per_batch is 0) is gathered, whatever its (d, p) --
+    // verification needs no codec -- into windows of at most kManyWindowBytes of copies: one
+    // cec_parts_verify call per window, one list entry per copy that reads and has the part's
+    // chunk size (the skeleton rule of check_run: a location that does not read is Unavailable,
+    // a copy of another size Invalid without being hashed).  The copies are hashed where they lie
+    // in `src`, which must not be written during the call.
+    static std::vector<std::vector<PartReport>> verify_many(
+        const std::vector<const FileReference*>& files, const ChunkStore& src,
+        size_t parts_per_batch = 0, size_t depth = 4, const std::vector<int>& devices = {}) {
+        struct Window {
+            std::vector<const uint8_t*> bufs;
+            std::vector<size_t> lens;
+            std::vector<uint8_t> expected;
+            std::vector<LocationIntegrity*> where;  // the report entry of each list entry
+            std::vector<PartReport*> reports;
+            size_t bytes = 0;
+        } w;
+        auto flush = [&] {
+            const size_t n = w.bufs.size();
+            std::vector<uint8_t> ok(n, 0);
+            if (n)
+                detail::check(cec_parts_verify(w.bufs.data(), w.lens.data(), n, w.expected.data(),
+                                               ok.data()));
+            for (size_t x = 0; x < n; ++x)
+                *w.where[x] = ok[x] ? LocationIntegrity::Valid : LocationIntegrity::Invalid;
+            for (PartReport* rep : w.reports) rep->summarize();
+            w = Window{};
+        };
+        std::vector<std::vector<PartReport>> out(files.size());
+        for (size_t f = 0; f < files.size(); ++f) {
+            const FileReference& file = *files[f];
+            out[f].resize(file.parts.size());
+            file.for_runs(parts_per_batch, [&](size_t k0, size_t n) {
+                if (n >= 2) {
+                    file.check_run(const_cast<ChunkStore&>(src), k0, n, parts_per_batch, depth,
+                                   devices, nullptr, out[f]);  // verify only reads the store
+                    return;
+                }
+                const FilePart& part = file.parts[k0];
+                PartReport& rep = out[f][k0];
+                if (part.chunksize == 0) {  // no engine call takes an empty chunk
+                    rep = part.verify(src);
+                    return;
+                }
+                const size_t copies = skeleton_report(src, part, rep);
+                if (!w.reports.empty() && w.bytes + copies * part.chunksize > kManyWindowBytes)
+                    flush();
+                w.reports.push_back(&rep);
+                w.bytes += copies * part.chunksize;
+                for (size_t i = 0; i < rep.locations.size(); ++i)
+                    for (size_t j = 0; j < rep.locations[i].size(); ++j) {
+                        if (rep.locations[i][j] != LocationIntegrity::Valid) continue;
+                        const Chunk& c = part.chunk(i);
+                        w.bufs.push_back(src.find(c.locations[j])->data());
+                        w.lens.push_back(part.chunksize);
+                        w.expected.insert(w.expected.end(), c.hash.digest().begin(),
+                                          c.hash.digest().end());
+                        w.where.push_back(&rep.locations[i][j]);
+                    }
+            });
+        }
+        flush();
+        return out;
+    }
+
+    // resilver() for many files in one go: result[f] equals files[f]->resilver(dest,
+    // parts_per_batch, depth, devices) -- the reports, the locations appended to the files'
+    // chunks and the bytes written to `dest` -- whenever no location is shared between two parts.
+    // Runs of two or more parts of one shape still go through check_run when parts_per_batch is
+    // set; every other part of every file is gathered per (d, p) into windows of at most
+    // kManyWindowBytes, each flushed as check_run's resilver branch does it: the copies of chunks
+    // with several locations are hashed first (one cec_parts_verify call) and each such chunk's
+    // first valid copy goes on flagged CEC_PRESENT_VERIFIED, lone copies flagged 1, so every copy
+    // is hashed exactly once; one cec_parts_read(data_only = 0) call then rebuilds every chunk
+    // that has no valid copy.  The engine rebuilds a lone copy that fails verification into its
+    // own slot, so every slot is the window's own memory, the loaded copies copied in: a copy in
+    // the store that was not rewritten keeps its bytes.  A part short of d valid chunks gets
+    // write_error = TooFewShardsPresent and the others go on.  A window's write-backs run in file
+    // order, then part order, then chunk order (dest.write_shard, the new location appended, the
+    // chunk reported Resilvered).
+    // Shared locations: a window's parts are judged against the store as it stood when the
+    // window was loaded, which is when it is flushed.  Parts that share a location across files
+    // or within a window (identical zero-padding chunks, say) and have lost it are therefore each
+    // reported Resilvered, where file-by-file calls would report the later ones Valid; the chunk
+    // is then written once per part, the same bytes to the same location, and each part's chunk
+    // gets the location appended.
+    static std::vector<std::vector<PartReport>> resilver_many(
+        const std::vector<FileReference*>& files, ChunkStore& dest, size_t parts_per_batch = 0,
+        size_t depth = 4, const std::vector<int>& devices = {}) {
+        struct Window {
+            std::vector<ResilverPending> parts;
+            size_t bytes = 0;
+        };
+        std::vector<std::vector<PartReport>> out(files.size());
+        std::map<std::pair<size_t, size_t>, Window> windows;  // per (d, p)
+        auto flush = [&](size_t d, size_t p, Window& w) {
+            resilver_window(dest, d, p, w.parts);
+            w.parts.clear();
+            w.bytes = 0;
+        };
+        for (size_t f = 0; f < files.size(); ++f) {
+            FileReference& file = *files[f];
+            out[f].resize(file.parts.size());
+            file.for_runs(parts_per_batch, [&](size_t k0, size_t n) {
+                if (n >= 2) {
+                    file.check_run(dest, k0, n, parts_per_batch, depth, devices, &file.parts,
+                                   out[f]);
+                    return;
+                }
+                FilePart& part = file.parts[k0];
+                if (part.chunksize == 0) {  // no engine call takes an empty chunk
+                    out[f][k0] = part.resilver(dest);
+                    return;
+                }
+                const size_t d = part.data.size(), p = part.parity.size();
+                const size_t bytes = (d + p) * part.chunksize;
+                Window& w = windows[{d, p}];
+                if (!w.parts.empty() && w.bytes + bytes > kManyWindowBytes) flush(d, p, w);
+                w.parts.push_back({&part, &out[f][k0]});
+                w.bytes += bytes;
+            });
+        }
+        for (auto& kv : windows)
+            if (!kv.second.parts.empty()) flush(kv.first.first, kv.first.second, kv.second);
+        return out;
+    }
+
    private:
+    // The report skeleton of a part (check_run's rule): Unavailable where a location does not
+    // read, Invalid where its copy has another size than the part's chunks, Valid (to be
+    // checked) otherwise.  Returns the number of copies to be checked.
+    static size_t skeleton_report(const ChunkStore& store, const FilePart& part, PartReport& rep) {
+        const size_t t = part.data.size() + part.parity.size();
+        size_t copies = 0;
+        rep = PartReport{};
+        rep.locations.assign(t, {});
+        for (size_t i = 0; i < t; ++i) {
+            const Chunk& c = part.chunk(i);
+            rep.locations[i].assign(c.locations.size(), LocationIntegrity::Unavailable);
+            for (size_t j = 0; j < c.locations.size(); ++j) {
+                const Bytes* b = store.find(c.locations[j]);
+                if (!b) continue;
+                const bool sized = b->size() == part.chunksize;
+                rep.locations[i][j] = sized ? LocationIntegrity::Valid : LocationIntegrity::Invalid;
+                copies += sized ? 1 : 0;
+            }
+        }
+        return copies;
+    }
+
+    struct ResilverPending {
+        FilePart* part;
+        PartReport* rep;
+    };
+
+    // One window of resilver_many: parts of one (d, p) and any chunk lengths (none empty), in
+    // file order then part order.
+    static void resilver_window(ChunkStore& dest, size_t d, size_t p,
+                                const std::vector<ResilverPending>& parts) {
+        const size_t t = d + p, n = parts.size();
+        const ReedSolomon codec(d, p);
+        // the copies of chunks with several locations: every one hashed first, where it lies
+        {
+            std::vector<const uint8_t*> bufs;
+            std::vector<size_t> lens;
+            std::vector<uint8_t> expected;
+            std::vector<LocationIntegrity*> where;
+            for (const ResilverPending& pd : parts) {
+                skeleton_report(dest, *pd.part, *pd.rep);
+                for (size_t i = 0; i < t; ++i) {
+                    auto& locs = pd.rep->locations[i];
+                    if (locs.size() < 2) continue;
+                    const Chunk& c = pd.part->chunk(i);
+                    for (size_t j = 0; j < locs.size(); ++j) {
+                        if (locs[j] != LocationIntegrity::Valid) continue;
+                        bufs.push_back(dest.find(c.locations[j])->data());
+                        lens.push_back(pd.part->chunksize);
+                        expected.insert(expected.end(), c.hash.digest().begin(),
+                                        c.hash.digest().end());
+                        where.push_back(&locs[j]);
+                    }
+                }
+            }
+            std::vector<uint8_t> ok(bufs.size(), 0);
+            if (!bufs.empty())
+                detail::check(cec_parts_verify(bufs.data(), lens.data(), bufs.size(),
+                                               expected.data(), ok.data()));
+            for (size_t x = 0; x < bufs.size(); ++x)
+                *where[x] = ok[x] ? LocationIntegrity::Valid : LocationIntegrity::Invalid;
+        }
+        // every slot is the window's own memory: part q's chunk i at slots + at[q] + i * L_q
+        std::vector<size_t> at(n + 1, 0), lens(n);
+        for (size_t q = 0; q < n; ++q) {
+            lens[q] = parts[q].part->chunksize;
+            at[q + 1] = at[q] + t * lens[q];
+        }
+        Bytes slots(at[n]);
+        std::vector<uint8_t*> shards(n * t);
+        std::vector<uint8_t> present(n * t, 0), expected(n * t * 32), verified(n * t, 0);
+        std::vector<int> status(n, 0);
+        detail::parallel_for(n, [&](size_t q) {
+            const FilePart& part = *parts[q].part;
+            const size_t L = lens[q];
+            for (size_t i = 0; i < t; ++i) {
+                const Chunk& c = part.chunk(i);
+                uint8_t* slot = slots.data() + at[q] + i * L;
+                shards[q * t + i] = slot;
+                std::memcpy(&expected[(q * t + i) * 32], c.hash.digest().data(), 32);
+                const auto& locs = parts[q].rep->locations[i];
+                const auto valid = std::find(locs.begin(), locs.end(), LocationIntegrity::Valid);
+                if (valid == locs.end()) continue;
+                std::memcpy(slot, dest.find(c.locations[size_t(valid - locs.begin())])->data(), L);
+                // a lone copy is hashed by the read call; one from a chunk with several
+                // locations was verified above
+                present[q * t + i] = locs.size() == 1 ? 1 : CEC_PRESENT_VERIFIED;
+            }
+        });
+        detail::check(cec_parts_read(codec.raw(), shards.data(), lens.data(), n, present.data(),
+                                     expected.data(), 0, verified.data(), status.data()));
+        for (size_t q = 0; q < n; ++q) {
+            FilePart& part = *parts[q].part;
+            PartReport& rep = *parts[q].rep;
+            bool missing = false;
+            for (size_t i = 0; i < t; ++i) {
+                const bool ok = verified[q * t + i] != 0;
+                if (present[q * t + i] == 1)  // the lone copy the read call hashed
+                    rep.locations[i][0] =
+                        ok ? LocationIntegrity::Valid : LocationIntegrity::Invalid;
+                missing = missing || !ok;
+            }
+            rep.summarize();
+            if (!missing) continue;
+            if (status[q] != CEC_OK) {  // this part's write_error; the others go on
+                if (status[q] >= CEC_TOO_FEW_SHARDS && status[q] <= CEC_INVALID_INDEX)
+                    rep.write_error = static_cast<Error>(status[q]);
+                else
+                    detail::check(status[q]);
+                continue;
+            }
+            for (size_t i = 0; i < t; ++i) {
+                if (verified[q * t + i]) continue;
+                Chunk& c = part.chunk_mut(i);
+                c.locations.push_back(dest.write_shard(c.hash, shards[q * t + i], lens[q]));
+                rep.new_locations.push_back(c.locations.back());
+                rep.chunks[i] = LocationIntegrity::Resilvered;
+            }
+        }
+    }
+
     // fn(k0, n) over runs of parts of one shape (whole shape: chunk size, d and p) among parts
     // [k_begin, k_end); runs of one part when batching is off.
     template <typename Fn>
@@ -1085,21 +1336,8 @@ struct FileReference {
         // the report skeleton of window part q: Unavailable where a location does not read,
         // Invalid where its copy has the wrong size, Valid (to be checked) otherwise
         auto skeleton = [&](size_t at, size_t cnt) {
-            for (size_t q = 0; q < cnt; ++q) {
-                const FilePart& part = parts[k0 + at + q];
-                PartReport& rep = reports[k0 + at + q];
-                rep = PartReport{};
-                rep.locations.assign(t, {});
-                for (size_t i = 0; i < t; ++i) {
-                    const Chunk& c = part.chunk(i);
-                    rep.locations[i].assign(c.locations.size(), LocationIntegrity::Unavailable);
-                    for (size_t j = 0; j < c.locations.size(); ++j) {
-                        const Bytes* b = store.find(c.locations[j]);
-                        if (b) rep.locations[i][j] = b->size() == L ? LocationIntegrity::Valid
-                                                                    : LocationIntegrity::Invalid;
-                    }
-                }
-            }
+            for (size_t q = 0; q < cnt; ++q)
+                skeleton_report(store, parts[k0 + at + q], reports[k0 + at + q]);
         };
         // a verify job over `items` of window [at, at + cnt): copies into buf (g rows of t),
         // flags into `verified`; returns the job

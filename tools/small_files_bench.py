@@ -30,9 +30,21 @@ All arms' rebuilt chunks must equal the erased ones (asserted).
 --device --read: 4096 x RS(10,4) x 64 KiB, two erasures per part, device resident:
 cec_reconstruct_ragged with uniform lengths against cec_reconstruct_batch on the same bytes.
 
+--verify: the scrub side on the same seeded files and shapes.  Every part is stored as the oracle
+encodes it and every one of its d + p chunks is hashed and compared with its digest:
+
+  a  the per-part way from 10 and from 256 threads: cec_sha256_many over the part's d + p chunks,
+     the digests compared (FilePart::verify)
+  b  one cec_parts_verify call over all chunks of all parts
+  c  the CPU oracle on 16 threads (SHA-256 of every chunk, compared)
+
+Every arm must find every chunk good, and the one chunk that is flipped before the run bad
+(asserted).
+
     python tools/small_files_bench.py [--files 4096] [--repeats 3] [--shapes 3,2:10,4]
     python tools/small_files_bench.py --device
     python tools/small_files_bench.py --read
+    python tools/small_files_bench.py --verify
     python tools/small_files_bench.py --device --read"""
 import argparse
 import ctypes
@@ -193,6 +205,30 @@ def host_staged(args):
     print(json.dumps({"tool": "small_files_bench", "mode": "host", "results": results}))
 
 
+def oracle_store(pool, parts, L, d, p):
+    """The parts as the oracle stores them -> (off, store, expected): part k's d + p chunks of
+    L[k] bytes from store[off[k]], its digests in expected[k]."""
+    n, t = len(parts), d + p
+    off = np.concatenate([[0], np.cumsum([t * x for x in L])])
+    store = np.zeros(int(off[-1]), np.uint8)
+    expected = np.zeros((n, t, 32), np.uint8)
+    lib = oracle.lib()
+    sb, eb = store.ctypes.data, expected.ctypes.data
+
+    def encode(k):
+        o, ln = parts[k]
+        at = int(off[k])
+        store[at:at + ln] = pool[o:o + ln]
+        cs = ctypes.c_size_t(0)
+        st = lib.or_part_encode(d, p, ctypes.cast(sb + at, U8P), ln,
+                                ctypes.cast(sb + at + d * L[k], U8P),
+                                ctypes.cast(eb + k * t * 32, U8P), ctypes.byref(cs))
+        assert st == 0 and cs.value == L[k]
+    with ThreadPoolExecutor(16) as ex:
+        list(ex.map(encode, range(n)))
+    return off, store, expected
+
+
 class ReadWorkload:
     """The parts of `files` as the oracle stores them (d data + p parity chunks of L_k bytes,
     digests), data chunk k % d of part k erased; d - 1 data chunks and parity chunk 0 are loaded."""
@@ -205,23 +241,8 @@ class ReadWorkload:
         self.file_bytes = sum(s for _, s in files)
         self.L = [(ln + d - 1) // d for _, ln in self.parts]
         t = self.t
-        self.off = np.concatenate([[0], np.cumsum([t * L for L in self.L])])
-        self.store = np.zeros(int(self.off[-1]), np.uint8)  # part k: t chunks of L_k from off[k]
-        self.expected = np.zeros((n, t, 32), np.uint8)
-        lib = oracle.lib()
-        sb, eb = self.store.ctypes.data, self.expected.ctypes.data
-
-        def encode(k):
-            o, ln = self.parts[k]
-            at, L = int(self.off[k]), self.L[k]
-            self.store[at:at + ln] = pool[o:o + ln]
-            cs = ctypes.c_size_t(0)
-            st = lib.or_part_encode(d, p, ctypes.cast(sb + at, U8P), ln,
-                                    ctypes.cast(sb + at + d * L, U8P),
-                                    ctypes.cast(eb + k * t * 32, U8P), ctypes.byref(cs))
-            assert st == 0 and cs.value == L
-        with ThreadPoolExecutor(16) as ex:
-            list(ex.map(encode, range(n)))
+        self.off, self.store, self.expected = oracle_store(pool, self.parts, self.L, d, p)
+        sb = self.store.ctypes.data
         self.erased = [k % d for k in range(n)]
         self.loaded = [[i for i in range(d) if i != self.erased[k]] + [d] for k in range(n)]
         # the erased chunks, kept aside and wiped in the store
@@ -339,6 +360,108 @@ def host_read(args):
     print(json.dumps({"tool": "small_files_bench", "mode": "host-read", "results": results}))
 
 
+class VerifyWorkload:
+    """The parts of `files` as the oracle stores them (d data + p parity chunks of L_k bytes,
+    digests); every chunk is one copy to verify.  The first byte of the last chunk of part n // 2
+    is flipped, so every arm has one bad copy to find."""
+
+    def __init__(self, pool, files, d, p):
+        self.d, self.p, self.t = d, p, d + p
+        self.parts = cut_parts(files, d)
+        self.n = n = len(self.parts)
+        self.file_bytes = sum(s for _, s in files)
+        self.L = [(ln + d - 1) // d for _, ln in self.parts]
+        t = self.t
+        self.off, self.store, self.expected = oracle_store(pool, self.parts, self.L, d, p)
+        sb = self.store.ctypes.data
+        self.stored_bytes = int(self.off[-1])
+        self.want = np.ones((n, t), np.uint8)
+        bad = n // 2
+        self.store[int(self.off[bad]) + (t - 1) * self.L[bad]] ^= 0x01
+        self.want[bad, t - 1] = 0
+        # pointer tables, made before any clock starts
+        self.part_ptrs = [(U8P * t)(*[ctypes.cast(sb + int(self.off[k]) + i * self.L[k], U8P)
+                                      for i in range(t)]) for k in range(n)]
+        self.part_lens = [(ctypes.c_size_t * t)(*([L] * t)) for L in self.L]
+        self.all_ptrs = (U8P * (n * t))(*[x for row in self.part_ptrs for x in row])
+        self.all_lens = (ctypes.c_size_t * (n * t))(*[L for L in self.L for _ in range(t)])
+        self.ok = np.zeros((n, t), np.uint8)  # every arm's flags land here
+
+    def arm_percall(self, threads, count=None):
+        t = self.t
+
+        def one(k):
+            dig = np.zeros((t, 32), np.uint8)
+            st = ce._lib.cec_sha256_many(self.part_ptrs[k], self.part_lens[k], t,
+                                         dig.ctypes.data_as(U8P))
+            assert st == 0, (st, k)
+            self.ok[k] = (dig == self.expected[k]).all(axis=1)
+        with ThreadPoolExecutor(threads) as ex:
+            list(ex.map(one, range(count or self.n)))
+
+    def arm_ragged(self, count=None):
+        n = count or self.n
+        ce._check(ce._lib.cec_parts_verify(self.all_ptrs, self.all_lens, n * self.t,
+                                           self.expected.ctypes.data_as(U8P),
+                                           self.ok.ctypes.data_as(U8P)))
+
+    def arm_cpu(self, threads=16, count=None):
+        lib = oracle.lib()
+        t = self.t
+
+        def one(k):
+            dig = np.zeros((t, 32), np.uint8)
+            for i in range(t):
+                lib.or_sha256(self.part_ptrs[k][i], self.L[k],
+                              ctypes.cast(dig.ctypes.data + 32 * i, U8P))
+            self.ok[k] = (dig == self.expected[k]).all(axis=1)
+        with ThreadPoolExecutor(threads) as ex:
+            list(ex.map(one, range(count or self.n)))
+
+
+def host_verify(args):
+    pool, files = make_files(args.files)
+    results = []
+    for shape in args.shapes.split(":"):
+        d, p = (int(x) for x in shape.split(","))
+        w = VerifyWorkload(pool, files, d, p)
+        print(f"== verify RS({d},{p}) chunk 1 MiB: {len(files)} files, "
+              f"{w.file_bytes / 2**30:.2f} GiB in {w.stored_bytes / 2**30:.2f} GiB of chunks, "
+              f"{w.n} parts, {w.n * w.t} copies, one of them flipped", flush=True)
+        arms = [("a: sha256_many per part x 10 threads", lambda c=None: w.arm_percall(10, c)),
+                ("a: sha256_many per part x 256 threads", lambda c=None: w.arm_percall(256, c)),
+                ("b: one parts_verify call", lambda c=None: w.arm_ragged(c)),
+                ("c: CPU oracle x 16 threads", lambda c=None: w.arm_cpu(16, c))]
+        warm = min(w.n, 512)
+        for name, fn in arms:  # warm-up: b on the whole input (its staging is sized by it)
+            sec, _ = timed(lambda: fn(None if name.startswith("b") else warm))
+            print(f"   warm-up {name}: {sec:.3f} s", flush=True)
+        secs = {name: [] for name, _ in arms}
+        for rep in range(args.repeats):
+            for name, fn in arms:
+                w.ok[:] = 7
+                sec, _ = timed(fn)
+                secs[name].append(sec)
+                assert np.array_equal(w.ok, w.want), f"flags of '{name}' differ"
+                print(f"   repeat {rep + 1} {name}: {sec:.3f} s  "
+                      f"{w.stored_bytes / sec / 1e9:7.2f} GB/s of chunks  "
+                      f"{w.file_bytes / sec / 1e9:7.2f} GB/s of files  {w.n / sec:9.0f} parts/s",
+                      flush=True)
+        print("   every arm found every copy good and the flipped one bad, in every repeat")
+        names = [name for name, _ in arms]
+        wins = [secs[names[2]][r] < min(secs[names[0]][r], secs[names[1]][r])
+                for r in range(args.repeats)]
+        print(f"   b faster than the better per-part arm in each repeat: {wins}", flush=True)
+        results.append({"d": d, "p": p, "files": len(files), "parts": w.n,
+                        "file_bytes": w.file_bytes, "stored_bytes": w.stored_bytes,
+                        "seconds": secs,
+                        "gbps_stored": {k: [w.stored_bytes / s / 1e9 for s in v]
+                                        for k, v in secs.items()},
+                        "b_faster_each_repeat": wins})
+        del w
+    print(json.dumps({"tool": "small_files_bench", "mode": "host-verify", "results": results}))
+
+
 def device_read(args):
     d, p, n, L = 10, 4, 4096, 65536
     t = d + p
@@ -447,10 +570,13 @@ def main():
     ap.add_argument("--shapes", default="3,2:10,4")
     ap.add_argument("--device", action="store_true")
     ap.add_argument("--read", action="store_true")
+    ap.add_argument("--verify", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     if args.device:
         (device_read if args.read else device_mode)(args)
+    elif args.verify:
+        host_verify(args)
     else:
         (host_read if args.read else host_staged)(args)
 
