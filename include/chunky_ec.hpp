@@ -609,19 +609,11 @@ struct FilePart {
         size_t chunksize = 0;
         detail::check(cec_part_encode(encoder.raw(), data_buf.data(), length, parity.data(),
                                       digests.data(), &chunksize));
-        FilePart part;
-        part.chunksize = chunksize;
         std::unique_lock<std::mutex> lk;
         if (dest_mu) lk = std::unique_lock<std::mutex>(*dest_mu);
-        for (size_t i = 0; i < d + p; ++i) {
-            std::array<uint8_t, 32> h{};
-            std::memcpy(h.data(), &digests[32 * i], 32);
-            Chunk c{Sha256Hash(h), {}};
-            const uint8_t* src = i < d ? &data_buf[i * L] : &parity[(i - d) * L];
-            c.locations.push_back(dest.write_shard(c.hash, src, L));
-            (i < d ? part.data : part.parity).push_back(std::move(c));
-        }
-        return part;
+        return from_digests(dest, digests.data(), chunksize, d, d + p, [&](size_t i) {
+            return i < d ? &data_buf[i * L] : &parity[(i - d) * L];
+        });
     }
 
     // read_with_context (file_part.rs:73-135): chunks drawn until d verify (data chunks first
@@ -639,17 +631,11 @@ struct FilePart {
         while (have < d) {
             std::vector<size_t> idx;
             std::vector<const Bytes*> copies;
-            for (size_t i : detail::draw_order(good.data(), tried.data(), exhausted.data(), t)) {
-                if (have + idx.size() >= d) break;
-                tried[i] = 1;
-                const Bytes* b = detail::next_copy(src, chunk(i), cursor[i], chunksize, &cursor[i]);
-                if (!b) {
-                    exhausted[i] = 1;
-                    continue;
-                }
-                idx.push_back(i);
-                copies.push_back(b);
-            }
+            draw(src, good.data(), tried.data(), exhausted.data(), cursor.data(), have,
+                 [&](size_t i, const Bytes* b) {
+                     idx.push_back(i);
+                     copies.push_back(b);
+                 });
             if (idx.empty()) throw ErasureError(Error::TooFewShardsPresent);
             const std::vector<Sha256Hash> got = Sha256Hash::from_bufs(copies);  // one launch
             for (size_t k = 0; k < idx.size(); ++k)
@@ -701,13 +687,9 @@ struct FilePart {
         }
         std::unique_lock<std::mutex> lk;
         if (dest_mu) lk = std::unique_lock<std::mutex>(*dest_mu);
-        for (size_t i = 0; i < t; ++i) {
-            if (rep.chunks[i] == LocationIntegrity::Valid) continue;
-            Chunk& c = chunk_mut(i);
-            c.locations.push_back(dest.write_shard(c.hash, *all[i]));
-            rep.new_locations.push_back(c.locations.back());
-            rep.chunks[i] = LocationIntegrity::Resilvered;
-        }
+        for (size_t i = 0; i < t; ++i)
+            if (rep.chunks[i] != LocationIntegrity::Valid)
+                append_rebuilt(rep, i, dest, all[i]->data(), all[i]->size());
         return rep;
     }
 
@@ -715,6 +697,61 @@ struct FilePart {
     Chunk& chunk_mut(size_t i) { return i < data.size() ? data[i] : parity[i - data.size()]; }
 
    private:
+    friend struct FileReference;    // draw, append_rebuilt
+    friend class FileWriteBuilder;  // from_digests
+
+    // The part whose t = d + p chunks hash to digests[t][32]: chunk i, the L bytes at bytes_of(i),
+    // written to `dest` and its location recorded, in chunk order (d data, then parity).  Every
+    // write path ends here; they differ in where a chunk's bytes lie.
+    template <typename BytesOf>
+    static FilePart from_digests(ChunkStore& dest, const uint8_t* digests, size_t L, size_t d,
+                                 size_t t, BytesOf bytes_of) {
+        FilePart part;
+        part.chunksize = L;
+        for (size_t i = 0; i < t; ++i) {
+            std::array<uint8_t, 32> h{};
+            std::memcpy(h.data(), digests + 32 * i, 32);
+            Chunk c{Sha256Hash(h), {}};
+            c.locations.push_back(dest.write_shard(c.hash, bytes_of(i), L));
+            (i < d ? part.data : part.parity).push_back(std::move(c));
+        }
+        return part;
+    }
+
+    // Resilver's write-back of one chunk (file_part.rs:340-347): the rebuilt bytes written to
+    // `dest`, the new location appended to the chunk's list and to the report, the chunk reported
+    // Resilvered.
+    void append_rebuilt(PartReport& rep, size_t i, ChunkStore& dest, const uint8_t* bytes, size_t n) {
+        Chunk& c = chunk_mut(i);
+        c.locations.push_back(dest.write_shard(c.hash, bytes, n));
+        rep.new_locations.push_back(c.locations.back());
+        rep.chunks[i] = LocationIntegrity::Resilvered;
+    }
+
+    // One round's draw for a part short of d verified chunks (file_part.rs:92-107): chunks in
+    // draw_order, each marked tried and moved to its next copy of the part's chunk size (exhausted
+    // when none is left), until `have` plus the copies found reach d; on_copy(i, copy) for each.
+    // good / tried / exhausted / cursor: the part's rows of t entries.  Returns the number of
+    // copies handed on: 0 means the part's copies have run out.
+    template <typename OnCopy>
+    size_t draw(const ChunkStore& src, const uint8_t* good, uint8_t* tried, uint8_t* exhausted,
+                size_t* cursor, size_t have, OnCopy on_copy) const {
+        const size_t d = data.size();
+        size_t added = 0;
+        for (size_t i : detail::draw_order(good, tried, exhausted, d + parity.size())) {
+            if (have + added >= d) break;
+            tried[i] = 1;
+            const Bytes* b = detail::next_copy(src, chunk(i), cursor[i], chunksize, &cursor[i]);
+            if (!b) {
+                exhausted[i] = 1;
+                continue;
+            }
+            on_copy(i, b);
+            ++added;
+        }
+        return added;
+    }
+
     // Every location's copy of every chunk hashed in one launch: rep.locations filled; with
     // `first_valid`, each chunk's first valid copy is copied there.  The copies are taken under
     // `mu` (a resilver elsewhere may be writing the store).
@@ -757,6 +794,48 @@ struct FilePart {
     }
 };
 
+namespace detail {
+// The most one window of the ragged ("many files") calls holds, counted as each call says.
+constexpr size_t kManyWindowBytes = size_t(256) << 20;
+
+// A window of the ragged calls: items gathered until the next one would take a non-empty window
+// past kManyWindowBytes, which hands the window to flush(items) first.  flush() at the end takes
+// what is left.
+template <typename T>
+struct ManyWindow {
+    std::vector<T> items;
+    size_t bytes = 0;
+    template <typename Flush>
+    void add(T item, size_t size, Flush&& fn) {
+        if (!items.empty() && bytes + size > kManyWindowBytes) flush(fn);
+        items.push_back(std::move(item));
+        bytes += size;
+    }
+    template <typename Flush>
+    void flush(Flush&& fn) {
+        if (!items.empty()) fn(items);
+        items.clear();
+        bytes = 0;
+    }
+};
+
+// One ManyWindow per (d, p), for the calls that need a codec: flush(d, p, items); the windows
+// left at the end are flushed in (d, p) order.
+template <typename T>
+struct ShapeWindows {
+    std::map<std::pair<size_t, size_t>, ManyWindow<T>> of;
+    template <typename Flush>
+    void add(size_t d, size_t p, T item, size_t size, Flush&& fn) {
+        of[{d, p}].add(std::move(item), size, [&](std::vector<T>& items) { fn(d, p, items); });
+    }
+    template <typename Flush>
+    void flush(Flush&& fn) {
+        for (auto& kv : of)
+            kv.second.flush([&](std::vector<T>& items) { fn(kv.first.first, kv.first.second, items); });
+    }
+};
+}  // namespace detail
+
 // file::FileReference: total length + parts (the metadata document).
 void release_thread_buffers();
 
@@ -779,8 +858,7 @@ struct FileReference {
     // (TooFewShardsPresent).  Same bytes and the same failure as the per-part path.
     Bytes read(const ChunkStore& src, size_t parts_per_batch = 0, size_t depth = 4,
                const std::vector<int>& devices = {}) const {
-        uint64_t total = 0;
-        for (const FilePart& part : parts) total += part.len_bytes();
+        uint64_t total = parts_bytes();
         if (length && *length < total) total = *length;
         Bytes out(static_cast<size_t>(total));
         size_t at = 0;
@@ -804,7 +882,7 @@ struct FileReference {
     // chunks and go up again, their verified chunks flagged CEC_PRESENT_VERIFIED (no carry pool
     // on this path: those chunks travel again); TooFewShardsPresent when a part's copies run out.
     // Data chunks are loaded into, and rebuilt into, their place in the result.
-    static constexpr size_t kManyWindowBytes = size_t(256) << 20;
+    static constexpr size_t kManyWindowBytes = detail::kManyWindowBytes;
     static std::vector<Bytes> read_many(const std::vector<const FileReference*>& files,
                                         const ChunkStore& src, size_t parts_per_batch = 0,
                                         size_t depth = 4, const std::vector<int>& devices = {}) {
@@ -812,22 +890,14 @@ struct FileReference {
             const FilePart* part;
             uint8_t* out;  // the part's d*L bytes in its file's result
         };
-        struct Window {
-            std::vector<Pending> parts;
-            size_t bytes = 0;
-        };
         std::vector<Bytes> out(files.size());
-        std::map<std::pair<size_t, size_t>, Window> windows;  // per (d, p)
-        auto flush = [&](size_t d, size_t p, Window& w) {
-            read_window(src, d, p, w.parts);
-            w.parts.clear();
-            w.bytes = 0;
+        detail::ShapeWindows<Pending> windows;  // budget: data bytes
+        auto flush = [&](size_t d, size_t p, const std::vector<Pending>& parts) {
+            read_window(src, d, p, parts);
         };
         for (size_t f = 0; f < files.size(); ++f) {
             const FileReference& file = *files[f];
-            uint64_t total = 0;
-            for (const FilePart& part : file.parts) total += part.len_bytes();
-            out[f].resize(static_cast<size_t>(total));
+            out[f].resize(static_cast<size_t>(file.parts_bytes()));
             std::vector<size_t> at(file.parts.size() + 1, 0);
             for (size_t k = 0; k < file.parts.size(); ++k)
                 at[k + 1] = at[k] + file.parts[k].len_bytes();
@@ -842,15 +912,11 @@ struct FileReference {
                     return;
                 }
                 const FilePart& part = file.parts[k0];
-                Window& w = windows[{part.data.size(), part.parity.size()}];
-                if (!w.parts.empty() && w.bytes + part.len_bytes() > kManyWindowBytes)
-                    flush(part.data.size(), part.parity.size(), w);
-                w.parts.push_back({&part, out[f].data() + at[k0]});
-                w.bytes += part.len_bytes();
+                windows.add(part.data.size(), part.parity.size(),
+                            Pending{&part, out[f].data() + at[k0]}, part.len_bytes(), flush);
             });
         }
-        for (auto& kv : windows)
-            if (!kv.second.parts.empty()) flush(kv.first.first, kv.first.second, kv.second);
+        windows.flush(flush);
         for (size_t f = 0; f < files.size(); ++f)
             if (files[f]->length && *files[f]->length < out[f].size())
                 out[f].resize(static_cast<size_t>(*files[f]->length));
@@ -867,12 +933,7 @@ struct FileReference {
         read_span_to(src, 0, parts.size(), 0, len_bytes(), sink, parts_per_batch, depth, devices);
     }
     // FileReference::len_bytes (file_reference.rs:49-56): `length`, else the parts' bytes.
-    uint64_t len_bytes() const {
-        if (length) return *length;
-        uint64_t total = 0;
-        for (const FilePart& part : parts) total += part.len_bytes();
-        return total;
-    }
+    uint64_t len_bytes() const { return length ? *length : parts_bytes(); }
     // Parts [k_begin, k_end) read as read_to reads them; of their bytes (d*L per part, the
     // padding of a short part included) the first `skip` are dropped and at most `limit` go to
     // the sink -- reader.rs:40-67's read_skip and bytes_remaining (FileReadBuilder below).
@@ -963,24 +1024,11 @@ struct FileReference {
     static std::vector<std::vector<PartReport>> verify_many(
         const std::vector<const FileReference*>& files, const ChunkStore& src,
         size_t parts_per_batch = 0, size_t depth = 4, const std::vector<int>& devices = {}) {
-        struct Window {
-            std::vector<const uint8_t*> bufs;
-            std::vector<size_t> lens;
-            std::vector<uint8_t> expected;
-            std::vector<LocationIntegrity*> where;  // the report entry of each list entry
-            std::vector<PartReport*> reports;
-            size_t bytes = 0;
-        } w;
-        auto flush = [&] {
-            const size_t n = w.bufs.size();
-            std::vector<uint8_t> ok(n, 0);
-            if (n)
-                detail::check(cec_parts_verify(w.bufs.data(), w.lens.data(), n, w.expected.data(),
-                                               ok.data()));
-            for (size_t x = 0; x < n; ++x)
-                *w.where[x] = ok[x] ? LocationIntegrity::Valid : LocationIntegrity::Invalid;
-            for (PartReport* rep : w.reports) rep->summarize();
-            w = Window{};
+        CopyList copies;
+        detail::ManyWindow<PartReport*> window;  // one for every (d, p); budget: copies' bytes
+        auto flush = [&](const std::vector<PartReport*>& reports) {
+            copies.run();
+            for (PartReport* rep : reports) rep->summarize();
         };
         std::vector<std::vector<PartReport>> out(files.size());
         for (size_t f = 0; f < files.size(); ++f) {
@@ -998,24 +1046,12 @@ struct FileReference {
                     rep = part.verify(src);
                     return;
                 }
-                const size_t copies = skeleton_report(src, part, rep);
-                if (!w.reports.empty() && w.bytes + copies * part.chunksize > kManyWindowBytes)
-                    flush();
-                w.reports.push_back(&rep);
-                w.bytes += copies * part.chunksize;
-                for (size_t i = 0; i < rep.locations.size(); ++i)
-                    for (size_t j = 0; j < rep.locations[i].size(); ++j) {
-                        if (rep.locations[i][j] != LocationIntegrity::Valid) continue;
-                        const Chunk& c = part.chunk(i);
-                        w.bufs.push_back(src.find(c.locations[j])->data());
-                        w.lens.push_back(part.chunksize);
-                        w.expected.insert(w.expected.end(), c.hash.digest().begin(),
-                                          c.hash.digest().end());
-                        w.where.push_back(&rep.locations[i][j]);
-                    }
+                const size_t n_copies = skeleton_report(src, part, rep);
+                window.add(&rep, n_copies * part.chunksize, flush);
+                copies.add(src, part, rep, false);
             });
         }
-        flush();
+        window.flush(flush);
         return out;
     }
 
@@ -1024,16 +1060,11 @@ struct FileReference {
     // chunks and the bytes written to `dest` -- whenever no location is shared between two parts.
     // Runs of two or more parts of one shape still go through check_run when parts_per_batch is
     // set; every other part of every file is gathered per (d, p) into windows of at most
-    // kManyWindowBytes, each flushed as check_run's resilver branch does it: the copies of chunks
-    // with several locations are hashed first (one cec_parts_verify call) and each such chunk's
-    // first valid copy goes on flagged CEC_PRESENT_VERIFIED, lone copies flagged 1, so every copy
-    // is hashed exactly once; one cec_parts_read(data_only = 0) call then rebuilds every chunk
-    // that has no valid copy.  The engine rebuilds a lone copy that fails verification into its
-    // own slot, so every slot is the window's own memory, the loaded copies copied in: a copy in
-    // the store that was not rewritten keeps its bytes.  A part short of d valid chunks gets
-    // write_error = TooFewShardsPresent and the others go on.  A window's write-backs run in file
-    // order, then part order, then chunk order (dest.write_shard, the new location appended, the
-    // chunk reported Resilvered).
+    // kManyWindowBytes of chunks ((d + p) x chunksize a part), each flushed by resilver_window:
+    // the steps of check_run's resilver branch with cec_parts_verify and cec_parts_read for the
+    // scheduler's jobs.  A part short of d valid chunks gets write_error = TooFewShardsPresent
+    // and the others go on.  A window's write-backs run in file order, then part order, then
+    // chunk order.
     // Shared locations: a window's parts are judged against the store as it stood when the
     // window was loaded, which is when it is flushed.  Parts that share a location across files
     // or within a window (identical zero-padding chunks, say) and have lost it are therefore each
@@ -1043,16 +1074,10 @@ struct FileReference {
     static std::vector<std::vector<PartReport>> resilver_many(
         const std::vector<FileReference*>& files, ChunkStore& dest, size_t parts_per_batch = 0,
         size_t depth = 4, const std::vector<int>& devices = {}) {
-        struct Window {
-            std::vector<ResilverPending> parts;
-            size_t bytes = 0;
-        };
         std::vector<std::vector<PartReport>> out(files.size());
-        std::map<std::pair<size_t, size_t>, Window> windows;  // per (d, p)
-        auto flush = [&](size_t d, size_t p, Window& w) {
-            resilver_window(dest, d, p, w.parts);
-            w.parts.clear();
-            w.bytes = 0;
+        detail::ShapeWindows<ResilverPending> windows;  // budget: (d + p) chunks a part
+        auto flush = [&](size_t d, size_t p, const std::vector<ResilverPending>& parts) {
+            resilver_window(dest, d, p, parts);
         };
         for (size_t f = 0; f < files.size(); ++f) {
             FileReference& file = *files[f];
@@ -1069,19 +1094,21 @@ struct FileReference {
                     return;
                 }
                 const size_t d = part.data.size(), p = part.parity.size();
-                const size_t bytes = (d + p) * part.chunksize;
-                Window& w = windows[{d, p}];
-                if (!w.parts.empty() && w.bytes + bytes > kManyWindowBytes) flush(d, p, w);
-                w.parts.push_back({&part, &out[f][k0]});
-                w.bytes += bytes;
+                windows.add(d, p, ResilverPending{&part, &out[f][k0]}, (d + p) * part.chunksize,
+                            flush);
             });
         }
-        for (auto& kv : windows)
-            if (!kv.second.parts.empty()) flush(kv.first.first, kv.first.second, kv.second);
+        windows.flush(flush);
         return out;
     }
 
    private:
+    uint64_t parts_bytes() const {
+        uint64_t total = 0;
+        for (const FilePart& part : parts) total += part.len_bytes();
+        return total;
+    }
+
     // The report skeleton of a part (check_run's rule): Unavailable where a location does not
     // read, Invalid where its copy has another size than the part's chunks, Valid (to be
     // checked) otherwise.  Returns the number of copies to be checked.
@@ -1104,47 +1131,117 @@ struct FileReference {
         return copies;
     }
 
-    struct ResilverPending {
-        FilePart* part;
-        PartReport* rep;
-    };
+    // fn(i, j) for every copy a skeleton report left to be checked, in chunk then location order;
+    // only_multi: of chunks with at least two locations only (resilver hashes those first, and
+    // leaves a lone copy to the job that rebuilds).
+    template <typename Fn>
+    static void for_each_copy(const PartReport& rep, bool only_multi, Fn fn) {
+        for (size_t i = 0; i < rep.locations.size(); ++i) {
+            const auto& locs = rep.locations[i];
+            if (only_multi && locs.size() < 2) continue;
+            for (size_t j = 0; j < locs.size(); ++j)
+                if (locs[j] == LocationIntegrity::Valid) fn(i, j);
+        }
+    }
 
-    // One window of resilver_many: parts of one (d, p) and any chunk lengths (none empty), in
-    // file order then part order.
-    static void resilver_window(ChunkStore& dest, size_t d, size_t p,
-                                const std::vector<ResilverPending>& parts) {
-        const size_t t = d + p, n = parts.size();
-        const ReedSolomon codec(d, p);
-        // the copies of chunks with several locations: every one hashed first, where it lies
-        {
-            std::vector<const uint8_t*> bufs;
-            std::vector<size_t> lens;
-            std::vector<uint8_t> expected;
-            std::vector<LocationIntegrity*> where;
-            for (const ResilverPending& pd : parts) {
-                skeleton_report(dest, *pd.part, *pd.rep);
-                for (size_t i = 0; i < t; ++i) {
-                    auto& locs = pd.rep->locations[i];
-                    if (locs.size() < 2) continue;
-                    const Chunk& c = pd.part->chunk(i);
-                    for (size_t j = 0; j < locs.size(); ++j) {
-                        if (locs[j] != LocationIntegrity::Valid) continue;
-                        bufs.push_back(dest.find(c.locations[j])->data());
-                        lens.push_back(pd.part->chunksize);
-                        expected.insert(expected.end(), c.hash.digest().begin(),
-                                        c.hash.digest().end());
-                        where.push_back(&locs[j]);
-                    }
-                }
-            }
+    // A list of copies for one cec_parts_verify call: add() enters the copies for_each_copy
+    // names, hashed where they lie in `store`; run() makes the call, writes Valid / Invalid into
+    // the report entry of each copy, and empties the list.
+    struct CopyList {
+        std::vector<const uint8_t*> bufs;
+        std::vector<size_t> lens;
+        std::vector<uint8_t> expected;
+        std::vector<LocationIntegrity*> where;  // the report entry of each list entry
+        void add(const ChunkStore& store, const FilePart& part, PartReport& rep, bool only_multi) {
+            for_each_copy(rep, only_multi, [&](size_t i, size_t j) {
+                const Chunk& c = part.chunk(i);
+                bufs.push_back(store.find(c.locations[j])->data());
+                lens.push_back(part.chunksize);
+                expected.insert(expected.end(), c.hash.digest().begin(), c.hash.digest().end());
+                where.push_back(&rep.locations[i][j]);
+            });
+        }
+        void run() {
             std::vector<uint8_t> ok(bufs.size(), 0);
             if (!bufs.empty())
                 detail::check(cec_parts_verify(bufs.data(), lens.data(), bufs.size(),
                                                expected.data(), ok.data()));
             for (size_t x = 0; x < bufs.size(); ++x)
                 *where[x] = ok[x] ? LocationIntegrity::Valid : LocationIntegrity::Invalid;
+            *this = CopyList{};
         }
-        // every slot is the window's own memory: part q's chunk i at slots + at[q] + i * L_q
+    };
+
+    // Resilver's load of one part whose multi-location copies are checked (file_part.rs:277-295):
+    // each chunk's first Valid copy copied to slot_of(i) and flagged in present[t] -- 1 for a lone
+    // copy, which the job hashes, CEC_PRESENT_VERIFIED for one checked already, so every copy is
+    // hashed exactly once -- and every chunk's digest copied into expected[t][32].
+    template <typename SlotOf>
+    static void resilver_load(const ChunkStore& store, const FilePart& part, const PartReport& rep,
+                              SlotOf slot_of, uint8_t* present, uint8_t* expected) {
+        for (size_t i = 0; i < rep.locations.size(); ++i) {
+            const Chunk& c = part.chunk(i);
+            std::memcpy(expected + i * 32, c.hash.digest().data(), 32);
+            const auto& locs = rep.locations[i];
+            const auto valid = std::find(locs.begin(), locs.end(), LocationIntegrity::Valid);
+            if (valid == locs.end()) continue;
+            std::memcpy(slot_of(i), store.find(c.locations[size_t(valid - locs.begin())])->data(),
+                        part.chunksize);
+            present[i] = locs.size() == 1 ? 1 : CEC_PRESENT_VERIFIED;
+        }
+    }
+
+    // Resilver's collect of one part from its job's verified[t] and status: the lone copies'
+    // results (those resilver_load flagged 1) go into the report, which is summarized; a part
+    // with a chunk missing gets write_error when the job reported a crate error for it (the other
+    // parts go on; an engine failure is thrown), else every unverified chunk, rebuilt at
+    // bytes_of(i), is written back in chunk order.
+    template <typename BytesOf>
+    static void resilver_collect(FilePart& part, PartReport& rep, ChunkStore& dest,
+                                 const uint8_t* present, const uint8_t* verified, int status,
+                                 BytesOf bytes_of) {
+        const size_t t = rep.locations.size();
+        bool missing = false;
+        for (size_t i = 0; i < t; ++i) {
+            if (present[i] == 1)
+                rep.locations[i][0] =
+                    verified[i] ? LocationIntegrity::Valid : LocationIntegrity::Invalid;
+            missing = missing || !verified[i];
+        }
+        rep.summarize();
+        if (!missing) return;
+        if (status != CEC_OK) {
+            if (status >= CEC_TOO_FEW_SHARDS && status <= CEC_INVALID_INDEX)
+                rep.write_error = static_cast<Error>(status);
+            else
+                detail::check(status);
+            return;
+        }
+        for (size_t i = 0; i < t; ++i)
+            if (!verified[i]) part.append_rebuilt(rep, i, dest, bytes_of(i), part.chunksize);
+    }
+
+    struct ResilverPending {
+        FilePart* part;
+        PartReport* rep;
+    };
+
+    // One window of resilver_many: parts of one (d, p) and any chunk lengths (none empty), in
+    // file order then part order.  check_run's resilver steps (CopyList over the multi-location
+    // copies, resilver_load, one job, resilver_collect) over pageable memory: the engine rebuilds
+    // a lone copy that fails verification into its own slot, so every slot is the window's own,
+    // the loaded copies copied in, and a copy in the store that is not rewritten keeps its bytes.
+    static void resilver_window(ChunkStore& dest, size_t d, size_t p,
+                                const std::vector<ResilverPending>& parts) {
+        const size_t t = d + p, n = parts.size();
+        const ReedSolomon codec(d, p);
+        CopyList multi;
+        for (const ResilverPending& pd : parts) {
+            skeleton_report(dest, *pd.part, *pd.rep);
+            multi.add(dest, *pd.part, *pd.rep, true);
+        }
+        multi.run();
+        // part q's chunk i at slots + at[q] + i * L_q
         std::vector<size_t> at(n + 1, 0), lens(n);
         for (size_t q = 0; q < n; ++q) {
             lens[q] = parts[q].part->chunksize;
@@ -1155,52 +1252,17 @@ struct FileReference {
         std::vector<uint8_t> present(n * t, 0), expected(n * t * 32), verified(n * t, 0);
         std::vector<int> status(n, 0);
         detail::parallel_for(n, [&](size_t q) {
-            const FilePart& part = *parts[q].part;
-            const size_t L = lens[q];
-            for (size_t i = 0; i < t; ++i) {
-                const Chunk& c = part.chunk(i);
-                uint8_t* slot = slots.data() + at[q] + i * L;
-                shards[q * t + i] = slot;
-                std::memcpy(&expected[(q * t + i) * 32], c.hash.digest().data(), 32);
-                const auto& locs = parts[q].rep->locations[i];
-                const auto valid = std::find(locs.begin(), locs.end(), LocationIntegrity::Valid);
-                if (valid == locs.end()) continue;
-                std::memcpy(slot, dest.find(c.locations[size_t(valid - locs.begin())])->data(), L);
-                // a lone copy is hashed by the read call; one from a chunk with several
-                // locations was verified above
-                present[q * t + i] = locs.size() == 1 ? 1 : CEC_PRESENT_VERIFIED;
-            }
+            uint8_t** slot = &shards[q * t];
+            for (size_t i = 0; i < t; ++i) slot[i] = slots.data() + at[q] + i * lens[q];
+            resilver_load(dest, *parts[q].part, *parts[q].rep, [&](size_t i) { return slot[i]; },
+                          &present[q * t], &expected[q * t * 32]);
         });
         detail::check(cec_parts_read(codec.raw(), shards.data(), lens.data(), n, present.data(),
                                      expected.data(), 0, verified.data(), status.data()));
-        for (size_t q = 0; q < n; ++q) {
-            FilePart& part = *parts[q].part;
-            PartReport& rep = *parts[q].rep;
-            bool missing = false;
-            for (size_t i = 0; i < t; ++i) {
-                const bool ok = verified[q * t + i] != 0;
-                if (present[q * t + i] == 1)  // the lone copy the read call hashed
-                    rep.locations[i][0] =
-                        ok ? LocationIntegrity::Valid : LocationIntegrity::Invalid;
-                missing = missing || !ok;
-            }
-            rep.summarize();
-            if (!missing) continue;
-            if (status[q] != CEC_OK) {  // this part's write_error; the others go on
-                if (status[q] >= CEC_TOO_FEW_SHARDS && status[q] <= CEC_INVALID_INDEX)
-                    rep.write_error = static_cast<Error>(status[q]);
-                else
-                    detail::check(status[q]);
-                continue;
-            }
-            for (size_t i = 0; i < t; ++i) {
-                if (verified[q * t + i]) continue;
-                Chunk& c = part.chunk_mut(i);
-                c.locations.push_back(dest.write_shard(c.hash, shards[q * t + i], lens[q]));
-                rep.new_locations.push_back(c.locations.back());
-                rep.chunks[i] = LocationIntegrity::Resilvered;
-            }
-        }
+        for (size_t q = 0; q < n; ++q)  // file, part, chunk order
+            resilver_collect(*parts[q].part, *parts[q].rep, dest, &present[q * t],
+                             &verified[q * t], status[q],
+                             [&](size_t i) { return shards[q * t + i]; });
     }
 
     // fn(k0, n) over runs of parts of one shape (whole shape: chunk size, d and p) among parts
@@ -1253,20 +1315,12 @@ struct FileReference {
                 const size_t L = part.chunksize;
                 lens[a] = L;
                 uint8_t* gq = &good[q * t];
-                size_t added = 0;
-                for (size_t i : detail::draw_order(gq, &tried[q * t], &exhausted[q * t], t)) {
-                    if (have[q] + added >= d) break;
-                    tried[q * t + i] = 1;
-                    const Bytes* b =
-                        detail::next_copy(src, part.chunk(i), cursor[q * t + i], L, &cursor[q * t + i]);
-                    if (!b) {
-                        exhausted[q * t + i] = 1;
-                        continue;
-                    }
-                    std::memcpy(slot(q, i), b->data(), L);
-                    present[a * t + i] = 1;
-                    ++added;
-                }
+                const size_t added =
+                    part.draw(src, gq, &tried[q * t], &exhausted[q * t], &cursor[q * t], have[q],
+                              [&](size_t i, const Bytes* b) {
+                                  std::memcpy(slot(q, i), b->data(), L);
+                                  present[a * t + i] = 1;
+                              });
                 if (added == 0) throw ErasureError(Error::TooFewShardsPresent);
                 for (size_t i = 0; i < t; ++i) {
                     if (gq[i]) present[a * t + i] = CEC_PRESENT_VERIFIED;
@@ -1304,8 +1358,7 @@ struct FileReference {
         detail::PinnedBuf prepass;  // resilver: the copies of chunks with several locations
         std::vector<uint8_t> present, expected, verified;
         std::vector<int> status;
-        // verify: one item per copy hashed, (window part, chunk, location); resilver: the chunks
-        // whose lone copy the resilver job hashes
+        // verify: one item per copy hashed, (window part, chunk, location)
         std::vector<std::array<uint32_t, 3>> items;
     };
     static std::array<CheckWindow, 8>& check_windows() {
@@ -1317,10 +1370,10 @@ struct FileReference {
     // pipeline batch per shard (ppb x shards parts), up to `depth` in flight, so loading the next
     // windows overlaps the GPU work; reports (and resilver's write-backs) are made window by
     // window in file order.  verify: every copy of the window is one item of a cec_multi_verify
-    // job, d + p items per scheduler row whatever chunk they belong to.  resilver: a window whose
-    // chunks have one location each is one cec_multi_resilver job; the copies of chunks with
-    // several locations are hashed first (a verify job) and their first valid copy goes to the
-    // resilver job flagged CEC_PRESENT_VERIFIED: every copy is hashed exactly once.
+    // job, d + p items per scheduler row whatever chunk they belong to.  resilver: the copies of
+    // chunks with several locations are hashed first (a verify job, waited for), then the window
+    // is one cec_multi_resilver job between resilver_load and resilver_collect.  Unlike the
+    // ragged windows, every copy is copied into page-locked memory on its way up.
     // rebuilt_into: resilver (its parts get the new locations); nullptr: verify.
     void check_run(ChunkStore& store, size_t k0, size_t n, size_t ppb, size_t depth,
                    const std::vector<int>& devices, std::vector<FilePart>* rebuilt_into,
@@ -1333,16 +1386,27 @@ struct FileReference {
         const size_t W = ppb * devs.size();
         std::array<CheckWindow, 8>& win = check_windows();
         const size_t nwin = std::min<size_t>(std::max<size_t>(depth, 2), win.size());
-        // the report skeleton of window part q: Unavailable where a location does not read,
-        // Invalid where its copy has the wrong size, Valid (to be checked) otherwise
-        auto skeleton = [&](size_t at, size_t cnt) {
-            for (size_t q = 0; q < cnt; ++q)
+        using Items = std::vector<std::array<uint32_t, 3>>;
+        // the skeleton reports of window [at, at + cnt) and the (q, i, j) items of its copies to
+        // be checked (for_each_copy's rule)
+        auto list_copies = [&](Items& items, size_t at, size_t cnt, bool only_multi) {
+            items.clear();
+            for (size_t q = 0; q < cnt; ++q) {
                 skeleton_report(store, parts[k0 + at + q], reports[k0 + at + q]);
+                for_each_copy(reports[k0 + at + q], only_multi, [&](size_t i, size_t j) {
+                    items.push_back({uint32_t(q), uint32_t(i), uint32_t(j)});
+                });
+            }
+        };
+        // a verify job's results into the report entries of its items
+        auto mark = [&](const Items& items, size_t at, const std::vector<uint8_t>& verified) {
+            for (size_t x = 0; x < items.size(); ++x)
+                reports[k0 + at + items[x][0]].locations[items[x][1]][items[x][2]] =
+                    verified[x] ? LocationIntegrity::Valid : LocationIntegrity::Invalid;
         };
         // a verify job over `items` of window [at, at + cnt): copies into buf (g rows of t),
         // flags into `verified`; returns the job
-        auto verify_items = [&](const std::vector<std::array<uint32_t, 3>>& items, size_t at,
-                                uint8_t* buf, std::vector<uint8_t>& present,
+        auto verify_items = [&](const Items& items, size_t at, uint8_t* buf, std::vector<uint8_t>& present,
                                 std::vector<uint8_t>& expected, std::vector<uint8_t>& verified) {
             const size_t g = (items.size() + t - 1) / t;
             present.assign(g * t, 0);
@@ -1361,17 +1425,9 @@ struct FileReference {
             return job;
         };
         auto submit = [&](CheckWindow& w, size_t at, size_t cnt) {
-            skeleton(at, cnt);
             uint8_t* chunks = w.chunks.reserve(W * t * L, devs[0]);
-            w.items.clear();
             if (!resilver) {
-                for (size_t q = 0; q < cnt; ++q)
-                    for (size_t i = 0; i < t; ++i) {
-                        const auto& locs = reports[k0 + at + q].locations[i];
-                        for (size_t j = 0; j < locs.size(); ++j)
-                            if (locs[j] == LocationIntegrity::Valid)
-                                w.items.push_back({uint32_t(q), uint32_t(i), uint32_t(j)});
-                    }
+                list_copies(w.items, at, cnt, false);
                 // page-locked whatever the count: a pageable spill would go through the
                 // scheduler's staging copies, into memory touched for the first time
                 uint8_t* buf = w.items.size() > W * t ? w.chunks.reserve(w.items.size() * L, devs[0])
@@ -1380,51 +1436,24 @@ struct FileReference {
                                                           w.expected, w.verified);
             } else {
                 // chunks with several locations: every copy hashed first (file_part.rs:277-289)
-                std::vector<std::array<uint32_t, 3>> multi;
-                for (size_t q = 0; q < cnt; ++q)
-                    for (size_t i = 0; i < t; ++i) {
-                        const auto& locs = reports[k0 + at + q].locations[i];
-                        if (locs.size() < 2) continue;
-                        for (size_t j = 0; j < locs.size(); ++j)
-                            if (locs[j] == LocationIntegrity::Valid)
-                                multi.push_back({uint32_t(q), uint32_t(i), uint32_t(j)});
-                    }
+                Items multi;
+                list_copies(multi, at, cnt, true);
                 if (!multi.empty()) {
                     uint8_t* buf = w.prepass.reserve(((multi.size() + t - 1) / t) * t * L, devs[0]);
                     std::vector<uint8_t> pr, ex, ver;
                     const uint64_t job = verify_items(multi, at, buf, pr, ex, ver);
                     detail::check_multi(cec_multi_wait(m, job));
-                    for (size_t x = 0; x < multi.size(); ++x)
-                        reports[k0 + at + multi[x][0]].locations[multi[x][1]][multi[x][2]] =
-                            ver[x] ? LocationIntegrity::Valid : LocationIntegrity::Invalid;
+                    mark(multi, at, ver);
                 }
                 uint8_t* rebuilt = w.rebuilt.reserve(W * t * L, devs[0]);
                 w.present.assign(cnt * t, 0);
                 w.expected.resize(cnt * t * 32);
                 w.verified.assign(cnt * t, 0);
                 w.status.assign(cnt, 0);
-                for (size_t q = 0; q < cnt; ++q)
-                    for (size_t i = 0; i < t; ++i) {
-                        const auto& locs = reports[k0 + at + q].locations[i];
-                        if (locs.size() == 1 && locs[0] == LocationIntegrity::Valid)
-                            w.items.push_back({uint32_t(q), uint32_t(i), 0});
-                    }
-                detail::parallel_for(cnt, [&](size_t q) {
-                    const FilePart& part = parts[k0 + at + q];
-                    const auto& rl = reports[k0 + at + q].locations;
-                    for (size_t i = 0; i < t; ++i) {
-                        const Chunk& c = part.chunk(i);
-                        std::memcpy(&w.expected[(q * t + i) * 32], c.hash.digest().data(), 32);
-                        const auto& locs = rl[i];
-                        const auto valid = std::find(locs.begin(), locs.end(),
-                                                     LocationIntegrity::Valid);
-                        if (valid == locs.end()) continue;
-                        const size_t j = size_t(valid - locs.begin());
-                        std::memcpy(chunks + (q * t + i) * L, store.find(c.locations[j])->data(), L);
-                        // a lone copy is hashed by the resilver job; one from a chunk with several
-                        // locations was verified above
-                        w.present[q * t + i] = locs.size() == 1 ? 1 : CEC_PRESENT_VERIFIED;
-                    }
+                detail::parallel_for(cnt, [&](size_t q) {  // into the page-locked window
+                    resilver_load(store, parts[k0 + at + q], reports[k0 + at + q],
+                                  [&](size_t i) { return chunks + (q * t + i) * L; },
+                                  &w.present[q * t], &w.expected[q * t * 32]);
                 });
                 detail::check_multi(cec_multi_resilver(m, chunks, w.present.data(),
                                                        w.expected.data(), cnt, rebuilt,
@@ -1439,42 +1468,16 @@ struct FileReference {
             w.live = false;
             if (!resilver) {
                 if (!w.items.empty()) detail::check_multi(cec_multi_wait(m, w.job));
-                for (size_t x = 0; x < w.items.size(); ++x) {
-                    const auto& it = w.items[x];
-                    reports[k0 + w.first + it[0]].locations[it[1]][it[2]] =
-                        w.verified[x] ? LocationIntegrity::Valid : LocationIntegrity::Invalid;
-                }
+                mark(w.items, w.first, w.verified);
                 for (size_t q = 0; q < w.n; ++q) reports[k0 + w.first + q].summarize();
                 return;
             }
             detail::check_multi(cec_multi_wait(m, w.job));
-            for (const auto& it : w.items)  // the lone copies the resilver job hashed
-                reports[k0 + w.first + it[0]].locations[it[1]][0] =
-                    w.verified[it[0] * t + it[1]] ? LocationIntegrity::Valid
-                                                  : LocationIntegrity::Invalid;
             const uint8_t* rebuilt = w.rebuilt.reserve(W * t * L, devs[0]);
-            for (size_t q = 0; q < w.n; ++q) {
-                PartReport& rep = reports[k0 + w.first + q];
-                rep.summarize();
-                bool missing = false;
-                for (size_t i = 0; i < t; ++i) missing = missing || !w.verified[q * t + i];
-                if (!missing) continue;
-                if (w.status[q] != CEC_OK) {  // this part's write_error; the others go on
-                    if (w.status[q] >= CEC_TOO_FEW_SHARDS && w.status[q] <= CEC_INVALID_INDEX)
-                        rep.write_error = static_cast<Error>(w.status[q]);
-                    else
-                        detail::check(w.status[q]);  // an engine failure is the job's
-                    continue;
-                }
-                FilePart& part = (*rebuilt_into)[k0 + w.first + q];
-                for (size_t i = 0; i < t; ++i) {
-                    if (w.verified[q * t + i]) continue;
-                    Chunk& c = part.chunk_mut(i);
-                    c.locations.push_back(store.write_shard(c.hash, rebuilt + (q * t + i) * L, L));
-                    rep.new_locations.push_back(c.locations.back());
-                    rep.chunks[i] = LocationIntegrity::Resilvered;
-                }
-            }
+            for (size_t q = 0; q < w.n; ++q)  // part, chunk order
+                resilver_collect((*rebuilt_into)[k0 + w.first + q], reports[k0 + w.first + q],
+                                 store, &w.present[q * t], &w.verified[q * t], w.status[q],
+                                 [&](size_t i) { return rebuilt + (q * t + i) * L; });
         };
         try {
             size_t at = 0;
@@ -1772,7 +1775,7 @@ struct FileReference {
         for (size_t q = 0; q < g; ++q) {
             const size_t j = r.open[q];
             const FilePart& part = parts[k0 + w.first + r.failed[j]];
-            size_t have = 0, added = 0;
+            size_t have = 0;
             r.carry_in[q] = r.cid[j];
             for (size_t i = 0; i < t; ++i) {
                 std::memcpy(&r.expected[(q * t + i) * 32], part.chunk(i).hash.digest().data(), 32);
@@ -1782,20 +1785,13 @@ struct FileReference {
                     std::memcpy(&chunks[(q * t + i) * L], r.held[j * t + i]->data(), L);
                 r.present[q * t + i] = CEC_PRESENT_VERIFIED;
             }
-            for (size_t i : detail::draw_order(&r.good[j * t], &r.tried[j * t], &r.exhausted[j * t], t)) {
-                if (!(have + added < d)) break;
-                r.tried[j * t + i] = 1;
-                const Bytes* bytes = detail::next_copy(src, part.chunk(i), r.cursor[j * t + i], L,
-                                                       &r.cursor[j * t + i]);
-                if (!bytes) {
-                    r.exhausted[j * t + i] = 1;
-                    continue;
-                }
-                r.held[j * t + i] = bytes;
-                std::memcpy(&chunks[(q * t + i) * L], bytes->data(), L);
-                r.present[q * t + i] = 1;
-                ++added;
-            }
+            const size_t added =
+                part.draw(src, &r.good[j * t], &r.tried[j * t], &r.exhausted[j * t],
+                          &r.cursor[j * t], have, [&](size_t i, const Bytes* bytes) {
+                              r.held[j * t + i] = bytes;
+                              std::memcpy(&chunks[(q * t + i) * L], bytes->data(), L);
+                              r.present[q * t + i] = 1;
+                          });
             if (added == 0) throw ErasureError(Error::TooFewShardsPresent);
         }
         detail::check_multi(cec_multi_read_carry(
@@ -1813,29 +1809,27 @@ struct FileReference {
     void retry_collect(const ChunkStore& src, cec_multi* m, size_t k0, size_t d, size_t t,
                        size_t L, ReadWindow& w, uint8_t* out) const {
         ReadRetry& r = w.retry;
-        {
-            r.in_flight = false;
-            detail::check_multi(cec_multi_wait(m, r.job));
-            detail::read_times().round_latency +=
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - w.sent).count();
-            const uint8_t* data = r.data.reserve(r.f * d * L, -1);
-            std::vector<size_t> still;
-            for (size_t q = 0; q < r.g; ++q) {
-                const size_t j = r.open[q];
-                for (size_t i = 0; i < t; ++i) r.good[j * t + i] = r.verified[q * t + i] != 0;
-                if (r.status[q] == CEC_OK) {
-                    const size_t part = r.failed[j];
-                    std::memcpy(out + part * d * L, data + q * d * L, d * L);
-                    for (size_t i = 0; i < d; ++i) w.ptrs[part * d + i] = out + (part * d + i) * L;
-                } else {
-                    r.cid[j] = r.carry_out[q];
-                    still.push_back(j);
-                }
+        r.in_flight = false;
+        detail::check_multi(cec_multi_wait(m, r.job));
+        detail::read_times().round_latency +=
+            std::chrono::duration<double>(std::chrono::steady_clock::now() - w.sent).count();
+        const uint8_t* data = r.data.reserve(r.f * d * L, -1);
+        std::vector<size_t> still;
+        for (size_t q = 0; q < r.g; ++q) {
+            const size_t j = r.open[q];
+            for (size_t i = 0; i < t; ++i) r.good[j * t + i] = r.verified[q * t + i] != 0;
+            if (r.status[q] == CEC_OK) {
+                const size_t part = r.failed[j];
+                std::memcpy(out + part * d * L, data + q * d * L, d * L);
+                for (size_t i = 0; i < d; ++i) w.ptrs[part * d + i] = out + (part * d + i) * L;
+            } else {
+                r.cid[j] = r.carry_out[q];
+                still.push_back(j);
             }
-            r.open.swap(still);
-            if (!r.open.empty()) retry_round(src, m, k0, d, t, L, w);
-            else r.active = false;
         }
+        r.open.swap(still);
+        if (!r.open.empty()) retry_round(src, m, k0, d, t, L, w);
+        else r.active = false;
     }
 };
 
@@ -1963,7 +1957,7 @@ class FileWriteBuilder {
         const size_t full = n / part_cap;
         size_t off = 0;
         if (batch_ && full >= 2) {  // full parts: L = chunk_size for every one of them
-            write_full_parts(encoder, bytes, full, dest, file);
+            write_full_parts(bytes, full, dest, file);
             off = full * part_cap;
         }
         std::vector<size_t> offs;
@@ -2011,7 +2005,7 @@ class FileWriteBuilder {
     // every other part of every file (whole small files, short last parts) is gathered, in
     // windows of at most kManyWindowBytes, into ragged batches: one cec_parts_encode call per
     // window, its pointers straight into the callers' bytes (the engine pads in its own staging).
-    static constexpr size_t kManyWindowBytes = size_t(256) << 20;
+    static constexpr size_t kManyWindowBytes = detail::kManyWindowBytes;
     std::vector<FileReference> write_many(
         const std::vector<std::pair<const uint8_t*, size_t>>& files, ChunkStore& dest) const {
         if (concurrency_ <= 1) throw std::invalid_argument("concurrency must be > 1");  // :128
@@ -2023,11 +2017,9 @@ class FileWriteBuilder {
             const uint8_t* bytes;
             size_t length;
         };
-        std::vector<Pending> pend;
-        size_t pend_bytes = 0;
-        auto flush = [&] {
+        detail::ManyWindow<Pending> window;  // budget: data bytes
+        auto flush = [&](const std::vector<Pending>& pend) {
             const size_t n = pend.size();
-            if (n == 0) return;
             std::vector<const uint8_t*> bufs(n);
             std::vector<size_t> lengths(n), chunksizes(n);
             std::vector<Bytes> parity(n);
@@ -2044,29 +2036,16 @@ class FileWriteBuilder {
             Bytes edge;  // a data chunk that reaches past the file's bytes, zero padded
             for (size_t k = 0; k < n; ++k) {
                 const size_t L = chunksizes[k], len = pend[k].length;
-                FilePart part;
-                part.chunksize = L;
-                for (size_t i = 0; i < t; ++i) {
-                    std::array<uint8_t, 32> h{};
-                    std::memcpy(h.data(), &digests[(k * t + i) * 32], 32);
-                    Chunk c{Sha256Hash(h), {}};
-                    const uint8_t* src;
-                    if (i >= d) {
-                        src = &parity[k][(i - d) * L];
-                    } else if ((i + 1) * L <= len) {
-                        src = pend[k].bytes + i * L;
-                    } else {
-                        edge.assign(L, 0);
-                        if (i * L < len) std::memcpy(edge.data(), pend[k].bytes + i * L, len - i * L);
-                        src = edge.data();
-                    }
-                    c.locations.push_back(dest.write_shard(c.hash, src, L));
-                    (i < d ? part.data : part.parity).push_back(std::move(c));
-                }
-                out[pend[k].file].parts.push_back(std::move(part));
+                auto bytes_of = [&](size_t i) -> const uint8_t* {
+                    if (i >= d) return &parity[k][(i - d) * L];
+                    if ((i + 1) * L <= len) return pend[k].bytes + i * L;
+                    edge.assign(L, 0);
+                    if (i * L < len) std::memcpy(edge.data(), pend[k].bytes + i * L, len - i * L);
+                    return edge.data();
+                };
+                out[pend[k].file].parts.push_back(
+                    FilePart::from_digests(dest, &digests[k * t * 32], L, d, t, bytes_of));
             }
-            pend.clear();
-            pend_bytes = 0;
         };
         for (size_t f = 0; f < files.size(); ++f) {
             const uint8_t* bytes = files[f].first;
@@ -2074,19 +2053,17 @@ class FileWriteBuilder {
             const size_t full = n / part_cap;
             size_t off = 0;
             if (batch_ && full >= 2) {
-                flush();  // earlier files' parts reach dest before this file's
-                write_full_parts(encoder, bytes, full, dest, out[f]);
+                window.flush(flush);  // earlier files' parts reach dest before this file's
+                write_full_parts(bytes, full, dest, out[f]);
                 off = full * part_cap;
             }
             for (; off < n; off += part_cap) {
                 const size_t length = std::min(part_cap, n - off);
-                if (!pend.empty() && pend_bytes + length > kManyWindowBytes) flush();
-                pend.push_back({f, bytes + off, length});
-                pend_bytes += length;
+                window.add(Pending{f, bytes + off, length}, length, flush);
             }
             out[f].length = n;
         }
-        flush();
+        window.flush(flush);
         return out;
     }
 
@@ -2117,9 +2094,8 @@ class FileWriteBuilder {
     // write_with_encoder part by part.  The input bytes are already [part][d][L] (a full part is
     // d*chunk_size contiguous bytes), so each window is one job straight from them; parity and
     // digests come back into page-locked buffers.
-    void write_full_parts(const ReedSolomon& encoder, const uint8_t* bytes, size_t full,
-                          ChunkStore& dest, FileReference& file) const {
-        (void)encoder;
+    void write_full_parts(const uint8_t* bytes, size_t full, ChunkStore& dest,
+                          FileReference& file) const {
         const size_t d = data_, p = parity_, t = d + p, L = chunk_size_;
         const std::vector<int> devs = detail::devices_or_current(devices_);
         cec_multi* m = detail::cached_multi(d, p, L, batch_, depth_, devs);
@@ -2130,20 +2106,12 @@ class FileWriteBuilder {
             detail::check_multi(cec_multi_wait(m, w.job));
             const uint8_t* par = w.parity.reserve(W * p * L, devs[0]);
             const uint8_t* dig = w.digests.reserve(W * t * 32, devs[0]);
-            for (size_t k = 0; k < w.n; ++k) {
-                FilePart part;
-                part.chunksize = L;
-                for (size_t i = 0; i < t; ++i) {
-                    std::array<uint8_t, 32> h{};
-                    std::memcpy(h.data(), dig + (k * t + i) * 32, 32);
-                    Chunk c{Sha256Hash(h), {}};
-                    const uint8_t* src = i < d ? bytes + ((w.first + k) * d + i) * L
-                                               : par + (k * p + (i - d)) * L;
-                    c.locations.push_back(dest.write_shard(c.hash, src, L));
-                    (i < d ? part.data : part.parity).push_back(std::move(c));
-                }
-                file.parts.push_back(std::move(part));
-            }
+            for (size_t k = 0; k < w.n; ++k)  // data from the caller's bytes, parity from the job
+                file.parts.push_back(FilePart::from_digests(
+                    dest, dig + k * t * 32, L, d, t, [&](size_t i) {
+                        return i < d ? bytes + ((w.first + k) * d + i) * L
+                                     : par + (k * p + (i - d)) * L;
+                    }));
         };
         try {
             size_t at = 0;

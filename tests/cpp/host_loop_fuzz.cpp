@@ -11,7 +11,10 @@
 // another part's digests).
 //
 // Each seed: (1) writes a file through the batched and the per-part write paths (same parts,
-// digests, locations and stored bytes); (2) builds a store of random location mixes (good;
+// digests, locations and stored bytes), and a handful of files (empty, shorter than a chunk, of a
+// length d does not divide, exactly one part, several full parts and a tail) through write_many
+// (over a stand-in for cec_parts_encode) and through write() file by file: the same
+// FileReferences and stored bytes, the chunks reaching the store in the same order; (2) builds a store of random location mixes (good;
 // [bad, good]; [gone, short, good]; [bad, bad]; bad; gone -- file_part.rs:92-107's location
 // walk) and reads it with a random window size, depth, shard list and carry switch: the bytes out
 // are the file's, in order, up to the first part with fewer than d good chunks, which fails the
@@ -23,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <malloc.h>
 #include <map>
 #include <mutex>
 #include <random>
@@ -298,6 +302,45 @@ int cec_part_encode(const cec_codec* c, const uint8_t* data_buf, size_t length, 
     return CEC_OK;
 }
 
+// cec_part_encode for parts of unrelated lengths (write_many's flush): only lengths[k] bytes of
+// data_bufs[k] are read and zero padded to d * L_k here, as the ABI says the engine does in its
+// own staging.  A parity buffer must be a heap block of exactly p * L_k bytes, which is how the
+// header allocates it (one vector per part): malloc_usable_size gives the requested size under
+// AddressSanitizer, and otherwise at most the allocator's rounding more (glibc: a 16-byte granule,
+// a 32-byte minimum block, and a remainder under 32 bytes that is not split off: under 64 in all).
+int cec_parts_encode(const cec_codec* c, const uint8_t* const* data_bufs, const size_t* lengths,
+                     size_t n_parts, uint8_t* const* parity_outs, uint8_t* digests_out,
+                     size_t* chunksizes) {
+    const size_t d = c->d, p = c->p, t = d + p;
+    if (!data_bufs || !lengths || !parity_outs || !digests_out || !chunksizes) {
+        violation("cec_parts_encode: a NULL array");
+        return CEC_ERR_INVALID_ARGUMENT;
+    }
+    for (size_t k = 0; k < n_parts; ++k) {
+        if (!lengths[k]) {
+            violation("cec_parts_encode: a part of zero length");
+            return CEC_EMPTY_SHARD;
+        }
+        if (!data_bufs[k] || !parity_outs[k]) {
+            violation("cec_parts_encode: a NULL buffer");
+            return CEC_ERR_INVALID_ARGUMENT;
+        }
+    }
+    for (size_t k = 0; k < n_parts; ++k) {
+        const size_t L = (lengths[k] + d - 1) / d;
+        const size_t held = malloc_usable_size(parity_outs[k]);
+        if (held < p * L || held - p * L >= 64) {
+            violation("cec_parts_encode: a parity buffer of the wrong size");
+            return CEC_ERR_INVALID_ARGUMENT;
+        }
+        std::vector<uint8_t> padded(d * L, 0);
+        std::memcpy(padded.data(), data_bufs[k], lengths[k]);
+        encode_part(d, p, L, padded.data(), parity_outs[k], digests_out + k * t * 32);
+        chunksizes[k] = L;
+    }
+    return CEC_OK;
+}
+
 int cec_host_alloc(size_t bytes, int, void** out) {
     *out = std::malloc(bytes ? bytes : 1);
     return *out ? CEC_OK : CEC_ERR_INVALID_ARGUMENT;
@@ -428,6 +471,80 @@ bool run_seed(uint64_t seed) {
                          (unsigned long long)seed);
             return false;
         }
+    }
+
+    // write_many (one cec_parts_encode call for every part that is not a full part of a batched
+    // file) against write() file by file, into two fresh stores: the same FileReferences, the same
+    // stored bytes, and the chunks reach the store in the same order -- file, part, chunk
+    {
+        // draws of its own, so the steps below see the streams they saw before this step existed
+        std::mt19937_64 rng(seed * 104729 + 7);
+        auto uni = [&](size_t lo, size_t hi) { return lo + size_t(rng() % (hi - lo + 1)); };
+        const std::mt19937_64 poll_rng = g_poll_rng;
+        const size_t cap = d * L;
+        size_t not_by_d = cap - 1;  // a length in (L, cap) that d does not divide
+        while (not_by_d % d == 0) --not_by_d;
+        std::vector<size_t> sizes = {0, uni(1, L - 1), not_by_d, cap, uni(2, 4) * cap + uni(1, cap - 1),
+                                     uni(1, 3 * cap), 0, 2 * cap};
+        std::shuffle(sizes.begin(), sizes.end(), rng);
+        std::vector<Bytes> files;
+        std::vector<std::pair<const uint8_t*, size_t>> views;
+        for (size_t size : sizes) {
+            files.emplace_back(size);
+            for (auto& b : files.back()) b = uint8_t(rng());
+        }
+        for (const Bytes& f : files) views.emplace_back(f.data(), f.size());
+        FileWriteBuilder w;
+        w.chunk_size(L).data_chunks(d).parity_chunks(p).concurrency(uni(2, 10));
+        const bool batched = rng() % 2;
+        if (batched) w.batch(uni(1, 3), uni(1, 4)).devices(rng() % 2 ? std::vector<int>{0} : std::vector<int>{0, 0});
+        ChunkStore one_store, many_store;
+        std::vector<Location> one_log, many_log, ref_order;
+        one_store.log_writes(&one_log);
+        many_store.log_writes(&many_log);
+        std::vector<FileReference> one;
+        for (const Bytes& f : files) one.push_back(w.write(f, one_store));
+        const std::vector<FileReference> many = w.write_many(views, many_store);
+        one_store.log_writes(nullptr);
+        many_store.log_writes(nullptr);
+        bool same = many.size() == one.size() && many_store.size() == one_store.size();
+        for (size_t f = 0; same && f < files.size(); ++f) {
+            same = many[f].length == one[f].length && many[f].length == files[f].size() &&
+                   many[f].parts.size() == one[f].parts.size() &&
+                   many[f].parts.size() == (files[f].size() + cap - 1) / cap;
+            for (size_t k = 0; same && k < many[f].parts.size(); ++k) {
+                const FilePart &a = many[f].parts[k], &b = one[f].parts[k];
+                same = a.chunksize == b.chunksize && a.data.size() == d && b.data.size() == d &&
+                       a.parity.size() == p && b.parity.size() == p;
+                for (size_t i = 0; same && i < t; ++i) {
+                    const Chunk &ca = a.chunk(i), &cb = b.chunk(i);
+                    const Bytes *x = ca.locations.size() == 1 ? many_store.find(ca.locations[0]) : nullptr;
+                    const Bytes *y = cb.locations.size() == 1 ? one_store.find(cb.locations[0]) : nullptr;
+                    same = ca.hash == cb.hash && ca.locations == cb.locations && x && y && *x == *y &&
+                           x->size() == a.chunksize;
+                    if (same) ref_order.push_back(cb.locations[0]);
+                }
+            }
+            same = same && many[f].read(many_store) == files[f];
+        }
+        // write() hands a file's parts to `concurrency` tasks, all but the full parts of a batched
+        // file with two or more of them: its FileReferences are in order, its own log only when
+        // no file leaves it more than one part for the tasks
+        bool one_in_order = true;
+        for (const Bytes& f : files) {
+            const size_t full = f.size() / cap, parts = (f.size() + cap - 1) / cap;
+            one_in_order = one_in_order && parts - (batched && full >= 2 ? full : 0) <= 1;
+        }
+        std::vector<Location> one_sorted = one_log, many_sorted = many_log;
+        std::sort(one_sorted.begin(), one_sorted.end());
+        std::sort(many_sorted.begin(), many_sorted.end());
+        if (!same || many_log != ref_order || many_sorted != one_sorted ||
+            (one_in_order && many_log != one_log)) {
+            std::fprintf(stderr, "seed %llu: write_many differs from write() file by file\n",
+                         (unsigned long long)seed);
+            return false;
+        }
+        g_poll_rng = poll_rng;
     }
 
     ChunkStore st;

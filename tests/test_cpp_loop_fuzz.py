@@ -10,7 +10,11 @@ batched verify / resilver loop (check_run) against the per-part FilePart::verify
 copies of the same file and store: same reports, same write-backs, and the resilvered file reads
 back whole (file_part.rs:228-390); and each seed first writes a file through the batched write
 (FileWriteBuilder::batch over cec_multi_encode_hash jobs) and the per-part write: same parts,
-digests, locations and stored bytes (writer.rs:117-255).  The fuzz found a read that failed with a retry round in flight
+digests, locations and stored bytes (writer.rs:117-255), and a handful of files of the awkward
+lengths through write_many (its flush over a stand-in for cec_parts_encode that counts a NULL
+buffer, a zero length or a parity buffer of the wrong size as a contract violation) and through
+write() file by file: same FileReferences, stored bytes and order of the chunks reaching the
+store.  The fuzz found a read that failed with a retry round in flight
 keeping that round's carry ids (fixed)."""
 import os
 import shutil
