@@ -1,5 +1,6 @@
-// capi_internal.hpp — what the pieces of the C-ABI (capi.cpp, ragged.cpp) share.  Not installed,
-// not exported: everything here is defined once in capi.cpp unless it is inline.
+// capi_internal.hpp — what the pieces of the C-ABI (capi.cpp, its per-call tier percall.cpp and
+// its ragged half ragged.cpp) share.  Not installed, not exported: everything here is defined
+// once in capi.cpp unless it is inline.
 #pragma once
 
 #include "chunky_ec.h"
@@ -7,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <array>
+#include <functional>
 #include <list>
 #include <map>
 #include <memory>
@@ -48,6 +50,9 @@ inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline bool aligned16(const void* p, size_t a, size_t b) {
     return (reinterpret_cast<uintptr_t>(p) % 16 == 0) && (a % 16 == 0) && (b % 16 == 0);
 }
+inline bool aligned16(const cec_part_batch& b) {
+    return aligned16(b.base, b.part_stride, b.chunk_stride);
+}
 
 inline size_t coalesce_max_bytes() { return knobs().coalesce_max_bytes; }
 
@@ -83,7 +88,34 @@ class Scratch {
 // Upload `words` into `sc` (acquired here) on stream s; *dptr = their device copy.
 int upload_words(const std::vector<uint32_t>& words, hipStream_t s, Scratch& sc, uint32_t** dptr);
 
-// A stream + a device staging buffer (leased from capi.cpp's CtxPool, or part of an Arena).
+// Contexts a bounded per-device pool keeps alive between calls (percall.cpp CtxPool, capi.cpp
+// SidePool).
+constexpr size_t kMaxIdleCtx = 8;
+
+// RAII lease of a pooled context on the current device.  Pool: Ctx; get(), the process-wide pool;
+// take(device, args...), an idle or new context; prepare(ctx, args...), what a call needs of it
+// (made on first use); give(ctx), back to the pool or destroyed.
+template <typename Pool>
+class Lease {
+   public:
+    Lease() = default;
+    Lease(const Lease&) = delete;
+    Lease& operator=(const Lease&) = delete;
+    ~Lease() { Pool::get().give(std::move(c_)); }
+    template <typename... Args>
+    int acquire(Args... args) {
+        int dev = 0;
+        CEC_TRY(current_device(&dev));
+        c_ = Pool::get().take(dev, args...);
+        return Pool::prepare(*c_, args...);
+    }
+    typename Pool::Ctx* operator->() { return c_.get(); }
+
+   private:
+    std::unique_ptr<typename Pool::Ctx> c_;
+};
+
+// A stream + a device staging buffer (leased from percall.cpp's CtxPool, or part of an Arena).
 struct StageCtx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -189,6 +221,47 @@ inline bool needs_hash(uint8_t f) { return f != 0 && f != CEC_PRESENT_VERIFIED; 
 // any part kept its flags.
 bool rebuild_mask(size_t d, size_t t, size_t n_parts, const uint8_t* present, uint8_t* verified,
                   int* part_status, bool only_failed, std::vector<uint8_t>* mask);
+
+PatternKey make_key(const uint8_t* present, size_t t, bool data_only);
+
+// ---- The launch steps over a uniform layout (cec_part_batch), one copy each. ----
+
+// encode_sep of every part; rec = the codec's encode record on the current device.
+hipError_t launch_encode(const cec_codec& c, const uint32_t* rec, const cec_part_batch& b,
+                         hipStream_t s);
+
+// The verify half of a strided SHA-256 launch (ShaParams: device pointers, all optional).
+struct HashVerify {
+    const uint8_t* present = nullptr;
+    const uint8_t* expected = nullptr;
+    uint8_t* ok = nullptr;
+    const uint32_t* items = nullptr;  // the compacted item list, n_items of them
+    uint32_t n_items = 0;
+};
+// SHA-256 of chunks [first_chunk, first_chunk + n_chunks) of every part: digests and/or verify.
+hipError_t launch_hash(const cec_part_batch& b, size_t first_chunk, size_t n_chunks,
+                       uint8_t* digests, const HashVerify& v, hipStream_t s);
+
+// One decode launch.  l: the listed parts of b, each with its own record in `words` (the shared
+// launch when l->n_out == 0, n_rows its row class); null: every part of b through the n_rows
+// rows of the one record at `words`.
+hipError_t launch_decode(const cec_part_batch& b, size_t d, const uint32_t* words,
+                         const DecodePlan::Launch* l, uint32_t n_rows, uint32_t lds_reserve,
+                         hipStream_t s);
+
+// Fused encode+hash kernel or encode kernel + SHA kernel for a batch of `chunks` chunks (d+p per
+// part).  The fused kernel reads every byte once and wins when the SHA lanes fill the chip; a
+// small batch leaves most SIMDs idle, and the split SHA kernel's lower per-chain latency (31 vs
+// 42 ms per MiB) wins while the encode's extra pass is negligible.  CEC_FUSED (A/B knob): 0 =
+// always separate, 1 = always fused where supported.
+bool prefer_fused(size_t chunks);
+
+// Encode + SHA-256 of all d+p chunks of every part (digests as in ShaParams): the fused kernel
+// where it covers the shape, the layout is 16-byte aligned and prefer_fused says so; else the
+// encode, after_encode() if given, then the SHA-256 launch, and *split (if given) = true.
+int encode_hash_steps(const cec_codec& c, const uint32_t* rec, const cec_part_batch& b,
+                      uint8_t* digests, hipStream_t s,
+                      const std::function<int()>& after_encode = nullptr, bool* split = nullptr);
 
 }  // namespace cec
 

@@ -26,7 +26,7 @@ struct Knobs {
     // sha256_kernels.hip / fused_kernels.hip
     int sha_variant = 0;            // CEC_SHA_VARIANT (raw value; only 1 and 2 are honoured)
     int fused_mode = 0;             // CEC_FUSED_MODE (raw value; only 3 is honoured)
-    // capi.cpp, ragged.cpp
+    // capi.cpp (fused), percall.cpp, ragged.cpp
     int fused = -1;                 // CEC_FUSED 0/1 (-1: by batch size)
     uint32_t coalesce_us = 200;     // CEC_COALESCE_US
     size_t coalesce_max_bytes = size_t(1024) << 20;  // CEC_COALESCE_MAX_MIB

@@ -386,6 +386,60 @@ def test_per_call_coalescing_batches_concurrent_parts_bit_exact():
     assert l1 - l0 < c1 - c0  # some calls shared a launch
 
 
+@pytest.mark.parametrize("fused", [None, "0", "1"])  # by size, encode + early parity + SHA, fused
+@pytest.mark.parametrize("extra", [0, 3])  # L = 4096 = its 256-byte stride; L = 4097, stride 4352
+@pytest.mark.parametrize("d,p", [(3, 2), (10, 4)])
+def test_part_encode_page_locked_callers_vs_oracle(d, p, extra, fused, knob_env):
+    """cec_part_encode called directly with page-locked (HostBuffer) and pageable (numpy) buffers
+    in every combination, concurrently, so one coalesced batch mixes parts the engine copies
+    straight from / into the caller's memory with staged ones: the 1-D copy forms when the chunk
+    length is its own device stride, the 2-D forms otherwise, and under CEC_FUSED=0 the parity
+    download on the side stream.  Chunk size, every parity byte and all d+p digests against the
+    oracle, and not a byte written past p*L of the caller's parity buffer."""
+    import ctypes
+    from concurrent.futures import ThreadPoolExecutor
+
+    if fused is None:
+        knob_env.delenv("CEC_FUSED")
+    else:
+        knob_env.set("CEC_FUSED", fused)
+    length = d * 4096 + extra
+    L = (length + d - 1) // d
+    rs = ce.ReedSolomon(d, p)
+    tail = 64
+
+    def host(nbytes, pinned):
+        if pinned:
+            arr = ce.HostBuffer(nbytes).array
+        else:
+            arr = np.empty(nbytes, np.uint8)
+        assert ce.host_is_pinned(arr) == pinned
+        return arr
+
+    def task(i):
+        in_pinned, out_pinned = [(True, True), (True, False), (False, True), (False, False)][i % 4]
+        src = gen_bytes(12000 + 31 * i + d, length)
+        data = host(d * L, in_pinned)  # the engine reads d*L: zero padded past `length`
+        data[:length] = src
+        data[length:] = 0
+        par = host(p * L + tail, out_pinned)
+        par[:] = 0xA5
+        dig = (ctypes.c_uint8 * (32 * (d + p)))()
+        cs = ctypes.c_size_t(0)
+        code = ce._lib.cec_part_encode(rs.handle, ctypes.cast(ce._addr(data), ce._u8p), length,
+                                       ctypes.cast(ce._addr(par), ce._u8p), dig, ctypes.byref(cs))
+        assert code == 0, i
+        rcs, ref, rdig = oracle.part_encode(d, p, src, length)
+        assert cs.value == rcs == L
+        assert np.array_equal(par[:p * L].reshape(p, L), np.stack(ref)), i
+        assert np.all(par[p * L:] == 0xA5), i
+        assert bytes(dig) == b"".join(x.tobytes() for x in rdig), i
+        return i
+
+    with ThreadPoolExecutor(max_workers=12) as ex:
+        assert sorted(ex.map(task, range(24))) == list(range(24))
+
+
 # ----------------------------------------------------------------------------------------------
 # Device-resident batches
 # ----------------------------------------------------------------------------------------------
