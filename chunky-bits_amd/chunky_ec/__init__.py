@@ -129,6 +129,21 @@ _sig("cec_parts_encode", [_vp, ctypes.POINTER(_u8p), _szp, ctypes.c_size_t, ctyp
 _sig("cec_ragged_stride", [ctypes.c_size_t], ctypes.c_size_t)
 _sig("cec_ragged_layout", [ctypes.c_size_t, _szp, ctypes.c_size_t, _szp, _szp])
 _sig("cec_encode_hash_ragged", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _vp, _vp])
+_sig("cec_split_layout", [ctypes.c_size_t, ctypes.c_size_t, _szp, ctypes.c_size_t, _szp, _szp,
+                          _szp, _szp])
+_sig("cec_encode_hash_split", [_vp, _vp, _szp, _vp, _szp, _szp, ctypes.c_size_t, _vp, _vp])
+_sig("cec_parts_pipeline_new", [_vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                ctypes.POINTER(_vp)])
+_sig("cec_parts_pipeline_free", [_vp], None)
+_sig("cec_parts_pipeline_depth", [_vp], ctypes.c_size_t)
+_sig("cec_parts_pipeline_acquire", [_vp, _szp, ctypes.POINTER(_u8p)])
+_sig("cec_parts_pipeline_submit", [_vp, ctypes.c_size_t, _szp, ctypes.c_size_t])
+_sig("cec_parts_pipeline_submit_from", [_vp, ctypes.c_size_t, ctypes.POINTER(_u8p), _szp,
+                                        ctypes.c_size_t, _szp])
+_sig("cec_parts_pipeline_wait", [_vp, ctypes.c_size_t, ctypes.POINTER(_u8p), ctypes.POINTER(_u8p),
+                                 _szp])
+_sig("cec_parts_pipeline_query", [_vp, ctypes.c_size_t])
+_sig("cec_parts_pipeline_drain", [_vp])
 _sig("cec_reconstruct_ragged", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, ctypes.c_int, _vp])
 _sig("cec_read_ragged", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp, _u8p,
                          ctypes.POINTER(ctypes.c_int), _vp])
@@ -622,6 +637,37 @@ def encode_hash_ragged(codec: ReedSolomon, base_ptr: int, part_offsets: Sequence
                                        _stream_ptr(stream)))
 
 
+def split_layout(data_shards: int, parity_shards: int, chunk_lens: Sequence[int]):
+    """The packed split ragged layout (``cec_split_layout``): ``(data_offsets, parity_offsets,
+    data_bytes, parity_bytes)``.  Part k's data chunk j is at ``data_offsets[k] + j * stride`` of
+    the data region, its parity chunk i at ``parity_offsets[k] + i * stride`` of the parity
+    region, ``stride = ragged_stride(chunk_lens[k])``."""
+    n = len(chunk_lens)
+    lens = (ctypes.c_size_t * max(n, 1))(*chunk_lens)
+    doffs = (ctypes.c_size_t * max(n, 1))()
+    poffs = (ctypes.c_size_t * max(n, 1))()
+    db, pb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(_lib.cec_split_layout(data_shards, parity_shards, lens, n, doffs, poffs,
+                                 ctypes.byref(db), ctypes.byref(pb)))
+    return list(doffs[:n]), list(poffs[:n]), db.value, pb.value
+
+
+def encode_hash_split(codec: ReedSolomon, data_ptr: int, data_offsets: Sequence[int],
+                      parity_ptr: int, parity_offsets: Sequence[int], chunk_lens: Sequence[int],
+                      digests_ptr: int, stream=None) -> None:
+    """:func:`encode_hash_ragged` over the split layout (``cec_encode_hash_split``): the data
+    chunks are read from the device region at ``data_ptr``, the parity chunks written to the one
+    at ``parity_ptr``, digests ``[n][d+p][32]`` at ``digests_ptr``."""
+    n = len(chunk_lens)
+    if len(data_offsets) != n or len(parity_offsets) != n:
+        raise ValueError("offsets and chunk_lens differ in length")
+    doffs = (ctypes.c_size_t * max(n, 1))(*data_offsets)
+    poffs = (ctypes.c_size_t * max(n, 1))(*parity_offsets)
+    lens = (ctypes.c_size_t * max(n, 1))(*chunk_lens)
+    _check(_lib.cec_encode_hash_split(codec.handle, data_ptr, doffs, parity_ptr, poffs, lens, n,
+                                      digests_ptr, _stream_ptr(stream)))
+
+
 def sha256_batch(batch: PartBatch, first_chunk: int, n_chunks: int, digests_ptr: int,
                  stream=None) -> None:
     s = batch.struct()
@@ -915,6 +961,88 @@ class Pipeline:
 
     def drain(self) -> None:
         _check(_lib.cec_pipeline_drain(self._h))
+
+
+class PartsPipeline:
+    """cec_parts_pipeline: :func:`parts_encode` with `depth` slots in flight, for parts whose
+    chunk lengths differ, in the split ragged layout (:func:`split_layout`).
+
+    Per batch: ``slot, data = pl.acquire()`` (a writable numpy view of the slot's pinned data
+    region), then either fill it in the packed split layout and ``pl.submit(slot, chunk_lens)``,
+    or ``pl.submit_from(slot, bufs)`` (the engine packs; returns the chunk sizes); later
+    ``parity, digests = pl.wait(slot)``: a numpy view of the slot's pinned parity region (part k's
+    parity chunk i at ``parity_offsets[k] + i * ragged_stride(L_k)``) and ``[n][d+p][32]``
+    digests, valid until the slot is acquired again.
+    """
+
+    def __init__(self, codec: ReedSolomon, slot_data_bytes: int, max_parts: int, depth: int = 3):
+        h = _vp()
+        _check(_lib.cec_parts_pipeline_new(codec.handle, slot_data_bytes, max_parts, depth,
+                                           ctypes.byref(h)))
+        self._h = h
+        self.codec = codec  # keep the codec alive
+        self.d, self.p = codec.data_shard_count(), codec.parity_shard_count()
+        self.slot_data_bytes = slot_data_bytes
+        self.max_parts = max_parts
+        self.depth = depth
+        self._parity_bytes = [0] * depth
+
+    def __del__(self, _free=_lib.cec_parts_pipeline_free):
+        h = getattr(self, "_h", None)
+        if h:
+            _free(h)
+            self._h = None
+
+    def acquire(self):
+        import numpy as np
+        slot = ctypes.c_size_t(0)
+        ptr = _u8p()
+        _check(_lib.cec_parts_pipeline_acquire(self._h, ctypes.byref(slot), ctypes.byref(ptr)))
+        return slot.value, np.ctypeslib.as_array(ptr, shape=(self.slot_data_bytes,))
+
+    def _submitted(self, slot: int, chunk_lens) -> None:
+        self._parity_bytes[slot] = sum(self.p * ragged_stride(L) for L in chunk_lens)
+
+    def submit(self, slot: int, chunk_lens: Sequence[int]) -> None:
+        n = len(chunk_lens)
+        lens = (ctypes.c_size_t * max(n, 1))(*chunk_lens)
+        _check(_lib.cec_parts_pipeline_submit(self._h, slot, lens, n))
+        self._submitted(slot, chunk_lens)
+
+    def submit_from(self, slot: int, bufs: Sequence) -> List[int]:
+        """Part k is the whole of ``bufs[k]``; returns the parts' chunk sizes."""
+        n = len(bufs)
+        keep: list = []
+        ptrs = (_u8p * max(n, 1))(*[_buf_ptr(b, keep) for b in bufs])
+        lens = (ctypes.c_size_t * max(n, 1))(*[_nbytes(b) for b in bufs])
+        cs = (ctypes.c_size_t * max(n, 1))()
+        _check(_lib.cec_parts_pipeline_submit_from(self._h, slot, ptrs, lens, n, cs))
+        out = list(cs[:n])
+        self._submitted(slot, out)
+        return out
+
+    def wait(self, slot: int):
+        import numpy as np
+        par, dig = _u8p(), _u8p()
+        n = ctypes.c_size_t(0)
+        _check(_lib.cec_parts_pipeline_wait(self._h, slot, ctypes.byref(par), ctypes.byref(dig),
+                                            ctypes.byref(n)))
+        k, t = n.value, self.d + self.p
+        nb = self._parity_bytes[slot] if k else 0
+        parity = np.ctypeslib.as_array(par, shape=(max(nb, 1),))[:nb]
+        digests = np.ctypeslib.as_array(dig, shape=(max(k * t * 32, 1),))[: k * t * 32].reshape(
+            k, t, 32)
+        return parity, digests
+
+    def query(self, slot: int) -> bool:
+        """True when the slot's batch is complete (never blocks)."""
+        r = _lib.cec_parts_pipeline_query(self._h, slot)
+        if r < 0 or r > 1:
+            raise Error(r)
+        return bool(r)
+
+    def drain(self) -> None:
+        _check(_lib.cec_parts_pipeline_drain(self._h))
 
 
 class ReadPipeline:

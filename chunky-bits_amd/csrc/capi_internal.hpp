@@ -263,6 +263,28 @@ int encode_hash_steps(const cec_codec& c, const uint32_t* rec, const cec_part_ba
                       uint8_t* digests, hipStream_t s,
                       const std::function<int()>& after_encode = nullptr, bool* split = nullptr);
 
+// ---- The ragged encode (ragged.cpp), as the parts pipeline (ragged_pipeline.cpp) shares it. ----
+
+size_t ragged_stride(size_t chunk_len);  // cec_ragged_stride
+// cec_split_layout behind its pointer checks.
+int split_layout(size_t d, size_t p, const size_t* lens, size_t n, size_t* doffs, size_t* poffs,
+                 size_t* data_bytes, size_t* parity_bytes);
+// Every argument check of cec_encode_hash_split behind its pointer checks; no device use.
+int split_check(size_t d, size_t p, const uint8_t* data, const size_t* doffs,
+                const uint8_t* parity, const size_t* poffs, const size_t* lens, size_t n);
+// Host-staged packing of n parts' data chunks into dst at offs (zero-padded), on up to 8 threads.
+void pack_parts(uint8_t* dst, const size_t* offs, size_t d, const uint8_t* const* bufs,
+                const size_t* lengths, const size_t* chunk_lens, size_t n);
+// Bytes of per-part words the launches of a ragged encode of n parts of t chunks upload.
+size_t ragged_words_bytes(size_t t, size_t n);
+// The launches of a ragged encode + SHA-256 of checked arguments on s.  poffs null: parity behind
+// each part's data (cec_encode_hash_ragged, `parity` unused); else the split layout.  hwords /
+// dwords: page-locked and device room of ragged_words_bytes for the words, which a caller that
+// owns them must not reuse before the launches are done (null: a buffer of the scratch pool).
+int ragged_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, uint8_t* parity,
+                  const size_t* poffs, const size_t* lens, size_t n, uint8_t* digests,
+                  hipStream_t s, uint8_t* hwords = nullptr, uint8_t* dwords = nullptr);
+
 }  // namespace cec
 
 #pragma GCC visibility pop

@@ -105,6 +105,10 @@ uint32_t max_var_rows();
 // array over the parts' unit counts (units[0] = 0, units[n_parts] = total_units) and `parts`
 // holds {off lo, off hi, L lo, L hi} per part (device memory, read as wave-uniform words).
 // Exactly L_k bytes of each parity chunk are written.
+// Split layout (split != 0, encode only): `parts` holds six words per part, {off, L, disp}: the
+// d data chunks at base + off[k] + j * stride(L_k) as above, and output row r's chunk (index d + r
+// of the record) at that address plus disp[k], a 64-bit displacement that wraps (the parity
+// region may lie below the data region).  Not one byte of the data chunks is written.
 // Reconstruct: the listed parts are a compact selection of the batch (those that need a rebuild),
 // `parts` / `units` describe the listed parts only, and listed part lp uses the pattern record at
 // pat + part_pat[lp] (word offsets into one uploaded block of records).
@@ -112,12 +116,13 @@ struct RaggedParams {
     uint8_t* base;
     const uint32_t* pat;    // the codec's encode record, or the block of decode records
     const uint32_t* units;  // [n_parts + 1]
-    const uint32_t* parts;  // [n_parts][4]
+    const uint32_t* parts;  // [n_parts][4], split: [n_parts][6]
     const uint32_t* part_pat;  // [n_parts] or null: every part uses the record at pat
     uint32_t n_parts;
     uint32_t total_units;
     uint32_t d;
     uint32_t n_rows;
+    uint32_t split;  // nonzero: the split layout's records (launch_rs_encode_ragged only)
 };
 // Every listed part through all a.n_rows rows of its record (part_pat: records that share that
 // row count), in row groups of up to max_var_rows(): the encode, and reconstruct patterns wider

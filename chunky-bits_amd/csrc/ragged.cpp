@@ -1,9 +1,11 @@
 // ragged.cpp — the ragged half of include/chunky_ec.h: parts of different chunk lengths in one
-// launch sequence (cec_encode_hash_ragged, cec_reconstruct_ragged, cec_verify_ragged,
-// cec_read_ragged, cec_resilver_ragged) and the host-staged calls on top of them
-// (cec_parts_encode, cec_parts_read, cec_parts_verify).  Part k's chunk i lies at
-// base + off[k] + i * stride(L_k), stride = L rounded up to 16.  Host work only; every step of
-// the path has one home here.
+// launch sequence (cec_encode_hash_ragged, cec_encode_hash_split, cec_reconstruct_ragged,
+// cec_verify_ragged, cec_read_ragged, cec_resilver_ragged) and the host-staged calls on top of
+// them (cec_parts_encode, cec_parts_read, cec_parts_verify).  Part k's chunk i lies at
+// base + off[k] + i * stride(L_k), stride = L rounded up to 16; the split layout keeps the parity
+// chunks in a region of their own.  Host work only; every step of the path has one home here
+// (the ragged write pipeline, ragged_pipeline.cpp, takes its steps from here through
+// capi_internal.hpp).
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -18,11 +20,15 @@ namespace {
 
 constexpr size_t kRaggedAlign = 16;
 
+}  // namespace
+
 // L rounded up to 16; 0 when that overflows (and for an empty chunk, which every caller refuses
 // before it asks).
-size_t ragged_stride(size_t L) {
+size_t cec::ragged_stride(size_t L) {
     return L > SIZE_MAX - (kRaggedAlign - 1) ? 0 : round_up(L, kRaggedAlign);
 }
+
+namespace {
 
 // The packed layout: part k+1 directly behind part k.
 int ragged_layout(size_t t, const size_t* lens, size_t n, size_t* offs, size_t* total) {
@@ -65,22 +71,59 @@ int ragged_check(size_t t, const uint8_t* base, const size_t* offs, const size_t
     return CEC_OK;
 }
 
+}  // namespace
+
+// Every argument check of a split layout (no device use): each region by ragged_check's rules,
+// d chunks per part in the data region and p in the parity region, the SHA-256 items of both
+// together, and the two regions' byte ranges apart.
+int cec::split_check(size_t d, size_t p, const uint8_t* data, const size_t* doffs,
+                     const uint8_t* parity, const size_t* poffs, const size_t* lens, size_t n) {
+    size_t items = 0;
+    if (__builtin_mul_overflow(n, d + p, &items) || items > 0xFFFFFFFFull)
+        return CEC_ERR_INVALID_ARGUMENT;
+    CEC_TRY(ragged_check(d, data, doffs, lens, n));
+    CEC_TRY(ragged_check(p, parity, poffs, lens, n));
+    if (n == 0) return CEC_OK;
+    const size_t cs = ragged_stride(lens[n - 1]);
+    const uintptr_t d0 = reinterpret_cast<uintptr_t>(data), p0 = reinterpret_cast<uintptr_t>(parity);
+    uintptr_t d_lo = 0, d_hi = 0, p_lo = 0, p_hi = 0;
+    if (__builtin_add_overflow(d0, doffs[0], &d_lo) ||
+        __builtin_add_overflow(d0, doffs[n - 1] + d * cs, &d_hi) ||
+        __builtin_add_overflow(p0, poffs[0], &p_lo) ||
+        __builtin_add_overflow(p0, poffs[n - 1] + p * cs, &p_hi))
+        return CEC_ERR_INVALID_ARGUMENT;
+    if (d_lo < p_hi && p_lo < d_hi) {
+        set_last_error("split layout: the data and the parity region overlap");
+        return CEC_ERR_INVALID_ARGUMENT;
+    }
+    return CEC_OK;
+}
+
+namespace {
+
 // The per-part device records of the parts ids[0 .. count) (null: parts 0 .. count - 1):
 // units[count + 1] = the prefix array of their work units, parts[4 * count] = {off lo, off hi,
 // L lo, L hi}.  Returns the unit total, at most the whole batch's, which ragged_check bounded.
+// With `disp` (the split layout, kernels.hpp RaggedParams::split) a record has two more words,
+// {disp lo, disp hi}: parts[6 * count].
 uint32_t part_records(const size_t* offs, const size_t* lens, const uint32_t* ids, size_t count,
-                      uint32_t* units, uint32_t* parts) {
+                      uint32_t* units, uint32_t* parts, const uint64_t* disp = nullptr) {
     const uint64_t unit = ragged_unit_bytes();
+    const size_t w = disp ? 6 : 4;
     uint64_t acc = 0;
     for (size_t q = 0; q < count; ++q) {
         const size_t k = ids ? ids[q] : q;
         const uint64_t off = offs[k], L = lens[k];
         units[q] = uint32_t(acc);
         acc += (L - 1) / unit + 1;
-        parts[4 * q + 0] = uint32_t(off);
-        parts[4 * q + 1] = uint32_t(off >> 32);
-        parts[4 * q + 2] = uint32_t(L);
-        parts[4 * q + 3] = uint32_t(L >> 32);
+        parts[w * q + 0] = uint32_t(off);
+        parts[w * q + 1] = uint32_t(off >> 32);
+        parts[w * q + 2] = uint32_t(L);
+        parts[w * q + 3] = uint32_t(L >> 32);
+        if (disp) {
+            parts[w * q + 4] = uint32_t(disp[k]);
+            parts[w * q + 5] = uint32_t(disp[k] >> 32);
+        }
     }
     units[count] = uint32_t(acc);
     return uint32_t(acc);
@@ -91,9 +134,10 @@ uint32_t part_records(const size_t* offs, const size_t* lens, const uint32_t* id
 // longest first: a SHA-256 wave runs as long as its longest lane, so the 64 chains of a wave get
 // similar lengths.  Digests and flags land at their item's place whatever the order.  An item's
 // key is its part's, so the parts are sorted and each expanded in place.  Returns the items listed.
-template <typename Pick>
-size_t sha_list(const uint8_t* base, const size_t* offs, const size_t* lens, size_t n, size_t t,
-                Pick pick, uint64_t* ptrs, uint64_t* h_len, uint32_t* order) {
+// at(k, i, stride) is where part k's chunk i lies.
+template <typename Pick, typename At>
+size_t sha_list(const size_t* lens, size_t n, size_t t, Pick pick, At at, uint64_t* ptrs,
+                uint64_t* h_len, uint32_t* order) {
     std::vector<uint32_t> by_len(n);
     std::iota(by_len.begin(), by_len.end(), 0u);
     std::stable_sort(by_len.begin(), by_len.end(),
@@ -104,7 +148,7 @@ size_t sha_list(const uint8_t* base, const size_t* offs, const size_t* lens, siz
         for (size_t i = 0; i < t; ++i) {
             const size_t item = k * t + i;
             if (!pick(item)) continue;
-            ptrs[item] = reinterpret_cast<uint64_t>(base + offs[k] + i * cs);
+            ptrs[item] = reinterpret_cast<uint64_t>(at(k, i, cs));
             h_len[item] = lens[k];
             order[count++] = uint32_t(item);
         }
@@ -112,46 +156,70 @@ size_t sha_list(const uint8_t* base, const size_t* offs, const size_t* lens, siz
     return count;
 }
 
-// The launches of a checked ragged batch on `s`: one upload of the per-part words (the SHA-256
+}  // namespace
+
+// [ptrs u64 x items][lens u64 x items][order u32 x items][units u32 x n+1][parts u32 x 4n or 6n]
+size_t cec::ragged_words_bytes(size_t t, size_t n) { return n * t * 20 + (n + 1) * 4 + n * 24; }
+
+// The launches of a checked ragged encode on `s`: one upload of the per-part words (the SHA-256
 // list, the part records), the GF(2^8) kernel, the SHA-256 kernel.  The host arrays are copied
-// into the scratch buffer's page-locked mirror before this returns.
-int ragged_launch(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* lens, size_t n,
-                  uint8_t* digests, hipStream_t s) {
-    const size_t t = c->d + c->p, items = n * t;
+// into the words' page-locked side before this returns.  Part k's data chunks lie at
+// data + doffs[k]; its parity chunks behind them (poffs null: the layout of cec_ragged_layout,
+// records without a displacement) or at parity + poffs[k] (the split layout).
+int cec::ragged_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, uint8_t* parity,
+                       const size_t* poffs, const size_t* lens, size_t n, uint8_t* digests,
+                       hipStream_t s, uint8_t* hwords, uint8_t* dwords) {
+    const size_t d = c->d, t = c->d + c->p, items = n * t;
     uint32_t* drec = nullptr;
     CEC_TRY(c->encode_record(&drec));
-    // [ptrs u64 x items][lens u64 x items][order u32 x items][units u32 x n+1][parts u32 x 4n]
     const size_t o_len = items * 8, o_ord = o_len + items * 8, o_units = o_ord + items * 4,
-                 o_parts = o_units + (n + 1) * 4, bytes = o_parts + n * 16;
-    Scratch sc;  // released on s behind the launches below
-    CEC_TRY(sc.acquire(bytes, s));
-    sha_list(base, offs, lens, n, t, [](size_t) { return true; },
-             reinterpret_cast<uint64_t*>(sc.host()), reinterpret_cast<uint64_t*>(sc.host() + o_len),
-             reinterpret_cast<uint32_t*>(sc.host() + o_ord));
+                 o_parts = o_units + (n + 1) * 4, bytes = o_parts + n * (poffs ? 24 : 16);
+    Scratch sc;  // the words of a caller that has none: released on s behind the launches below
+    if (!hwords) {
+        CEC_TRY(sc.acquire(bytes, s));
+        hwords = sc.host();
+        dwords = sc.dev();
+    }
+    // where part k's parity chunk 0 lies, less where today's layout has it
+    std::vector<uint64_t> disp(poffs ? n : 0);
+    for (size_t k = 0; k < disp.size(); ++k)
+        disp[k] = (reinterpret_cast<uint64_t>(parity) + poffs[k]) -
+                  (reinterpret_cast<uint64_t>(data) + doffs[k] + d * ragged_stride(lens[k]));
+    sha_list(
+        lens, n, t, [](size_t) { return true; },
+        [&](size_t k, size_t i, size_t cs) {
+            return i < d || !poffs ? data + doffs[k] + i * cs : parity + poffs[k] + (i - d) * cs;
+        },
+        reinterpret_cast<uint64_t*>(hwords), reinterpret_cast<uint64_t*>(hwords + o_len),
+        reinterpret_cast<uint32_t*>(hwords + o_ord));
     RaggedParams a{};
-    a.total_units = part_records(offs, lens, nullptr, n,
-                                 reinterpret_cast<uint32_t*>(sc.host() + o_units),
-                                 reinterpret_cast<uint32_t*>(sc.host() + o_parts));
-    HIP_TRY(hipMemcpyAsync(sc.dev(), sc.host(), bytes, hipMemcpyHostToDevice, s));
-    a.base = base;
+    a.total_units = part_records(doffs, lens, nullptr, n,
+                                 reinterpret_cast<uint32_t*>(hwords + o_units),
+                                 reinterpret_cast<uint32_t*>(hwords + o_parts),
+                                 poffs ? disp.data() : nullptr);
+    HIP_TRY(hipMemcpyAsync(dwords, hwords, bytes, hipMemcpyHostToDevice, s));
+    a.base = const_cast<uint8_t*>(data);  // split: only read
     a.pat = drec;
-    a.units = reinterpret_cast<const uint32_t*>(sc.dev() + o_units);
-    a.parts = reinterpret_cast<const uint32_t*>(sc.dev() + o_parts);
+    a.units = reinterpret_cast<const uint32_t*>(dwords + o_units);
+    a.parts = reinterpret_cast<const uint32_t*>(dwords + o_parts);
     a.n_parts = uint32_t(n);
-    a.d = uint32_t(c->d);
+    a.d = uint32_t(d);
     a.n_rows = uint32_t(c->p);
+    a.split = poffs ? 1u : 0u;
     HIP_TRY(launch_rs_encode_ragged(a, s));
     ShaParams h{};
-    h.ptrs = reinterpret_cast<const uint64_t*>(sc.dev());
-    h.lens = reinterpret_cast<const uint64_t*>(sc.dev() + o_len);
+    h.ptrs = reinterpret_cast<const uint64_t*>(dwords);
+    h.lens = reinterpret_cast<const uint64_t*>(dwords + o_len);
     h.n_parts = uint32_t(items);
     h.n_chunks = 1;
     h.digests = digests;
-    h.items = reinterpret_cast<const uint32_t*>(sc.dev() + o_ord);
+    h.items = reinterpret_cast<const uint32_t*>(dwords + o_ord);
     h.n_items = uint32_t(items);
     HIP_TRY(launch_sha256(h, true, s));
     return CEC_OK;
 }
+
+namespace {
 
 // The launches of cec_reconstruct_ragged for a checked layout (ragged_check) and checked flags
 // (check_present), on `s`.  Only the parts the plan lists reach the device: per launch the part
@@ -217,7 +285,8 @@ int verify_ragged(const uint8_t* base, const size_t* offs, const size_t* lens, s
     uint8_t* ok = sc.dev() + o_ok;
     HIP_TRY(hipMemsetAsync(ok, 0, items, s));
     const size_t hashed = sha_list(
-        base, offs, lens, n, t, [&](size_t item) { return !present || needs_hash(present[item]); },
+        lens, n, t, [&](size_t item) { return !present || needs_hash(present[item]); },
+        [&](size_t k, size_t i, size_t cs) { return base + offs[k] + i * cs; },
         reinterpret_cast<uint64_t*>(sc.host()), reinterpret_cast<uint64_t*>(sc.host() + o_len),
         reinterpret_cast<uint32_t*>(sc.host() + o_ord));
     if (hashed) {
@@ -301,6 +370,35 @@ void for_parts(size_t n, size_t bytes, Fn fn) {
     work();
     for (auto& x : th) x.join();
 }
+
+}  // namespace
+
+// The packing of a host-staged encode: data chunk j of part k (L_k bytes at
+// dst + offs[k] + j * stride(L_k)) = bytes [j*L, (j+1)*L) of the caller's lengths[k] bytes, zeros
+// behind.  Only those bytes are read.
+void cec::pack_parts(uint8_t* dst, const size_t* offs, size_t d, const uint8_t* const* bufs,
+                     const size_t* lengths, const size_t* chunk_lens, size_t n) {
+    size_t in_bytes = 0;
+    for (size_t k = 0; k < n; ++k) in_bytes += lengths[k];
+    for_parts(n, in_bytes, [&](size_t k) {
+        const size_t L = chunk_lens[k], cs = ragged_stride(L), len = lengths[k];
+        for (size_t j = 0; j < d; ++j) {
+            uint8_t* to = dst + offs[k] + j * cs;
+            const size_t b0 = j * L, have = b0 < len ? std::min(L, len - b0) : 0;
+            if (have) std::memcpy(to, bufs[k] + b0, have);
+            if (have < L) std::memset(to + have, 0, L - have);
+        }
+    });
+}
+
+// The packed split layout: part k+1 directly behind part k in each region.
+int cec::split_layout(size_t d, size_t p, const size_t* lens, size_t n, size_t* doffs,
+                      size_t* poffs, size_t* data_bytes, size_t* parity_bytes) {
+    CEC_TRY(ragged_layout(d, lens, n, doffs, data_bytes));
+    return ragged_layout(p, lens, n, poffs, parity_bytes);
+}
+
+namespace {
 
 using Spans = std::vector<std::pair<size_t, size_t>>;
 
@@ -402,26 +500,16 @@ int parts_round(cec_codec* c, Arena& a, const uint8_t* const* bufs, const size_t
     Round r;
     CEC_TRY(reserve_round(a, d, t, chunk_lens, n, &r));
     const std::vector<size_t>& offs = r.offs;
-    size_t in_bytes = 0, out_bytes = 0;
+    size_t out_bytes = 0;
     Spans parity;  // per part, behind its data chunks
     for (size_t k = 0; k < n; ++k) {
         const size_t cs = ragged_stride(chunk_lens[k]);
-        in_bytes += lengths[k];
         out_bytes += p * chunk_lens[k];
         parity.emplace_back(offs[k] + d * cs, offs[k] + t * cs);
     }
-    // data chunk j of part k = bytes [j*L, (j+1)*L) of the caller's `length` bytes, zeros behind
-    for_parts(n, in_bytes, [&](size_t k) {
-        const size_t L = chunk_lens[k], cs = ragged_stride(L), len = lengths[k];
-        for (size_t j = 0; j < d; ++j) {
-            uint8_t* dst = r.stage + offs[k] + j * cs;
-            const size_t b0 = j * L, have = b0 < len ? std::min(L, len - b0) : 0;
-            if (have) std::memcpy(dst, bufs[k] + b0, have);
-            if (have < L) std::memset(dst + have, 0, L - have);
-        }
-    });
+    pack_parts(r.stage, offs.data(), d, bufs, lengths, chunk_lens, n);
     HIP_TRY(hipMemcpyAsync(r.dbase, r.stage, parity.back().first, hipMemcpyHostToDevice, r.s));
-    CEC_TRY(ragged_launch(c, r.dbase, offs.data(), chunk_lens, n, r.dside, r.s));
+    CEC_TRY(ragged_launch(c, r.dbase, offs.data(), r.dbase, nullptr, chunk_lens, n, r.dside, r.s));
     // The parity comes back into the staging at its own offsets; the data chunks between two
     // parts' parity travel along while they are short (copy_spans).
     CEC_TRY(copy_spans(r.stage, r.dbase, parity, false, r.s));
@@ -530,8 +618,34 @@ int cec_encode_hash_ragged(const cec_codec* cc, uint8_t* base, const size_t* par
     if (n_parts == 0) return CEC_OK;
     if (!base || !part_offsets || !chunk_lens || !digests) return CEC_ERR_INVALID_ARGUMENT;
     CEC_TRY(ragged_check(cc->d + cc->p, base, part_offsets, chunk_lens, n_parts));
-    return ragged_launch(const_cast<cec_codec*>(cc), base, part_offsets, chunk_lens, n_parts,
-                         digests, static_cast<hipStream_t>(stream));
+    return ragged_launch(const_cast<cec_codec*>(cc), base, part_offsets, base, nullptr, chunk_lens,
+                         n_parts, digests, static_cast<hipStream_t>(stream));
+}
+
+int cec_split_layout(size_t data_shards, size_t parity_shards, const size_t* chunk_lens,
+                     size_t n_parts, size_t* data_offsets, size_t* parity_offsets,
+                     size_t* data_bytes, size_t* parity_bytes) {
+    if (!data_bytes || !parity_bytes || data_shards == 0 || parity_shards == 0)
+        return CEC_ERR_INVALID_ARGUMENT;
+    if (n_parts && (!chunk_lens || !data_offsets || !parity_offsets))
+        return CEC_ERR_INVALID_ARGUMENT;
+    return split_layout(data_shards, parity_shards, chunk_lens, n_parts, data_offsets,
+                        parity_offsets, data_bytes, parity_bytes);
+}
+
+int cec_encode_hash_split(const cec_codec* cc, const uint8_t* data_base,
+                          const size_t* data_offsets, uint8_t* parity_base,
+                          const size_t* parity_offsets, const size_t* chunk_lens, size_t n_parts,
+                          uint8_t* digests, void* stream) {
+    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
+    if (n_parts == 0) return CEC_OK;
+    if (!data_base || !data_offsets || !parity_base || !parity_offsets || !chunk_lens || !digests)
+        return CEC_ERR_INVALID_ARGUMENT;
+    CEC_TRY(split_check(cc->d, cc->p, data_base, data_offsets, parity_base, parity_offsets,
+                        chunk_lens, n_parts));
+    return ragged_launch(const_cast<cec_codec*>(cc), data_base, data_offsets, parity_base,
+                         parity_offsets, chunk_lens, n_parts, digests,
+                         static_cast<hipStream_t>(stream));
 }
 
 int cec_parts_encode(const cec_codec* cc, const uint8_t* const* data_bufs, const size_t* lengths,

@@ -8,7 +8,9 @@
 //  rs_apply_var_kernel  the same for a reconstruct batch whose parts miss different numbers of
 //                       chunks: one launch, each block dispatched on its pattern's row count.
 //  rs_apply_ragged_kernel  encode_sep for parts of different chunk lengths, one launch: one
-//                       wave per 4 KiB of a part's columns, found through a prefix array.
+//                       wave per 4 KiB of a part's columns, found through a prefix array.  Its
+//                       SPLIT build stores the rows into a parity region of its own (the split
+//                       ragged layout) through a per-part output displacement.
 //  rs_reconstruct_ragged_kernel  reconstruct for such parts: a pattern record per listed part,
 //                       mixed erasure counts in one launch.
 //  fill_kernel          counter-based synthetic bytes for benchmarks/tests.
@@ -73,11 +75,14 @@ __device__ __forceinline__ void st16(uint8_t* p, uint4 v) {
 // (otherwise V == 1 with a byte-granular load/store of a rem < 16 tail).
 // tab points at row0's table of input 0; input j's RG tables start at tab + j*tab_stride.
 // GROUP inputs (x V columns) are loaded before any is multiplied; NT selects non-temporal
-// loads/stores (streamed once, never re-read).
+// loads/stores (streamed once, never re-read).  out_disp (wave-uniform) is added to every output
+// address: 0 where a part's outputs lie among its inputs' chunks, the distance to the part's
+// place in a parity region of its own in the split ragged layout.
 template <int RG, bool FULL, int GROUP, int V, bool NT>
 __device__ __forceinline__ void apply_column(uint8_t* pbase, uint64_t cs, uint64_t x,
                                              uint64_t rem, uint32_t d, uint32_t tab_stride,
-                                             cu32* in_idx, cu32* out_idx, cu32* tab) {
+                                             cu32* in_idx, cu32* out_idx, cu32* tab,
+                                             uint64_t out_disp = 0) {
     static_assert(FULL || V == 1, "ragged columns are single");
     uint32_t acc[RG][V][4];
 #pragma unroll
@@ -125,7 +130,7 @@ __device__ __forceinline__ void apply_column(uint8_t* pbase, uint64_t cs, uint64
     }
 #pragma unroll
     for (int r = 0; r < RG; ++r) {
-        uint8_t* dst = pbase + uint64_t(out_idx[r]) * cs + x;
+        uint8_t* dst = pbase + (uint64_t(out_idx[r]) * cs + out_disp) + x;
 #pragma unroll
         for (int c = 0; c < V; ++c) {
             if (FULL)
@@ -383,12 +388,15 @@ __device__ __forceinline__ uint32_t ragged_find(cu32* pre, uint32_t n_parts, uin
 }
 
 // One 4 KiB unit (columns from x0) of the part described by pm = {off lo, off hi, L lo, L hi}:
-// rows [row0, row0 + RG) of the record `pat`, n_out rows in all.
-template <int RG>
+// rows [row0, row0 + RG) of the record `pat`, n_out rows in all.  SPLIT: pm carries two more
+// words {disp lo, disp hi}, the part's output displacement (apply_column; scalar like the rest of
+// the record), so the rows land in the parity region and nothing is stored among the inputs.
+template <int RG, bool SPLIT = false>
 __device__ __forceinline__ void ragged_unit(uint8_t* base, cu32* pm, uint64_t x0, uint32_t d,
                                             cu32* pat, uint32_t n_out, uint32_t row0) {
     const uint64_t off = uint64_t(pm[0]) | (uint64_t(pm[1]) << 32);
     const uint64_t len = uint64_t(pm[2]) | (uint64_t(pm[3]) << 32);
+    const uint64_t disp = SPLIT ? uint64_t(pm[4]) | (uint64_t(pm[5]) << 32) : 0;
     const uint64_t cs = (len + 15) & ~uint64_t(15);
     uint8_t* pbase = base + off;
     cu32* in_idx = pat + 1;
@@ -402,18 +410,18 @@ __device__ __forceinline__ void ragged_unit(uint8_t* base, cu32* pm, uint64_t x0
         const uint64_t x = xb + lane_x;
         if (x + 16 <= len) {  // every lane of a step that is not the part's last
             apply_column<RG, true, 4, 1, false>(pbase, cs, x, len - x, d, tab_stride, in_idx,
-                                                out_idx, tab);
+                                                out_idx, tab, disp);
         } else if (x < len) {
             apply_column<RG, false, 4, 1, false>(pbase, cs, x, len - x, d, tab_stride, in_idx,
-                                                 out_idx, tab);
+                                                 out_idx, tab, disp);
         }
     }
 }
 
 // grid.x = ceil(total_units / kRaggedWaves), grid.y = row groups of exactly RG rows from row_base.
 // Every listed part uses the record at pat + part_pat[lp] (null: the one record at pat, the
-// encode), all of a.n_rows rows.
-template <int RG>
+// encode), all of a.n_rows rows.  SPLIT: the split layout's six-word part records (a.split).
+template <int RG, bool SPLIT = false>
 __global__ __launch_bounds__(kApplyThreads) void rs_apply_ragged_kernel(RaggedParams a,
                                                                         uint32_t row_base) {
     const uint32_t u = __builtin_amdgcn_readfirstlane(blockIdx.x * kRaggedWaves +
@@ -422,9 +430,9 @@ __global__ __launch_bounds__(kApplyThreads) void rs_apply_ragged_kernel(RaggedPa
     cu32* pre = as_const(a.units);
     const uint32_t lo = ragged_find(pre, a.n_parts, u);
     cu32* pat = as_const(a.pat) + (a.part_pat ? as_const(a.part_pat)[lo] : 0u);
-    ragged_unit<RG>(a.base, as_const(a.parts) + size_t(lo) * 4,
-                    uint64_t(u - pre[lo]) * kRaggedUnit, a.d, pat, a.n_rows,
-                    row_base + blockIdx.y * RG);
+    ragged_unit<RG, SPLIT>(a.base, as_const(a.parts) + size_t(lo) * (SPLIT ? 6 : 4),
+                           uint64_t(u - pre[lo]) * kRaggedUnit, a.d, pat, a.n_rows,
+                           row_base + blockIdx.y * RG);
 }
 
 // Ragged reconstruct: the listed parts are the ones that need a rebuild, each
@@ -930,7 +938,11 @@ hipError_t launch_ragged_rg(const RaggedParams& a, uint32_t row_base, uint32_t g
                             hipStream_t s) {
     const dim3 grid((a.total_units + kRaggedWaves - 1) / kRaggedWaves, groups);
     clear_stale_error();
-    hipLaunchKernelGGL(rs_apply_ragged_kernel<RG>, grid, dim3(kApplyThreads), 0, s, a, row_base);
+    if (a.split)
+        hipLaunchKernelGGL((rs_apply_ragged_kernel<RG, true>), grid, dim3(kApplyThreads), 0, s, a,
+                           row_base);
+    else
+        hipLaunchKernelGGL(rs_apply_ragged_kernel<RG>, grid, dim3(kApplyThreads), 0, s, a, row_base);
     return hipGetLastError();
 }
 
@@ -967,7 +979,7 @@ hipError_t launch_rs_encode_ragged(const RaggedParams& a, hipStream_t s) {
 // a.n_rows (the widest listed record; 0 = unknown, the 8-row class).
 hipError_t launch_rs_reconstruct_ragged(const RaggedParams& a, hipStream_t s) {
     if (a.n_parts == 0 || a.total_units == 0) return hipSuccess;
-    if (!a.part_pat || a.n_rows > kMaxApplyRows) return hipErrorInvalidValue;
+    if (!a.part_pat || a.split || a.n_rows > kMaxApplyRows) return hipErrorInvalidValue;
     if (a.total_units > ragged_max_units()) return hipErrorInvalidValue;
     const uint32_t rows = a.n_rows ? a.n_rows : kMaxApplyRows;
     const dim3 grid((a.total_units + kRaggedWaves - 1) / kRaggedWaves);

@@ -29,6 +29,11 @@ pub mod sys {
     }
 
     #[repr(C)]
+    pub struct cec_parts_pipeline {
+        _private: [u8; 0],
+    }
+
+    #[repr(C)]
     pub struct cec_multi {
         _private: [u8; 0],
     }
@@ -162,6 +167,27 @@ pub mod sys {
             codec: *const cec_codec,
             base: *mut u8,
             part_offsets: *const usize,
+            chunk_lens: *const usize,
+            n_parts: usize,
+            digests: *mut u8,
+            stream: *mut c_void,
+        ) -> c_int;
+        pub fn cec_split_layout(
+            data_shards: usize,
+            parity_shards: usize,
+            chunk_lens: *const usize,
+            n_parts: usize,
+            data_offsets: *mut usize,
+            parity_offsets: *mut usize,
+            data_bytes: *mut usize,
+            parity_bytes: *mut usize,
+        ) -> c_int;
+        pub fn cec_encode_hash_split(
+            codec: *const cec_codec,
+            data_base: *const u8,
+            data_offsets: *const usize,
+            parity_base: *mut u8,
+            parity_offsets: *const usize,
             chunk_lens: *const usize,
             n_parts: usize,
             digests: *mut u8,
@@ -524,6 +550,52 @@ pub mod sys {
         pub fn cec_synth_byte(seed: u64, part: u64, chunk: u64, offset: u64) -> u8;
         pub fn cec_reload_knobs();
         pub fn cec_release_cached(device: c_int) -> usize;
+    }
+
+    /// include/chunky_ec_parts.h: the ragged write pipeline, the part of the C-ABI that header
+    /// declares (the block above is include/chunky_ec.h, function for function).
+    pub mod parts {
+        use super::*;
+
+        extern "C" {
+            pub fn cec_parts_pipeline_new(
+                codec: *const cec_codec,
+                slot_data_bytes: usize,
+                max_parts: usize,
+                depth: usize,
+                out: *mut *mut cec_parts_pipeline,
+            ) -> c_int;
+            pub fn cec_parts_pipeline_free(pipeline: *mut cec_parts_pipeline);
+            pub fn cec_parts_pipeline_depth(pipeline: *const cec_parts_pipeline) -> usize;
+            pub fn cec_parts_pipeline_acquire(
+                pipeline: *mut cec_parts_pipeline,
+                slot: *mut usize,
+                data: *mut *mut u8,
+            ) -> c_int;
+            pub fn cec_parts_pipeline_submit(
+                pipeline: *mut cec_parts_pipeline,
+                slot: usize,
+                chunk_lens: *const usize,
+                n_parts: usize,
+            ) -> c_int;
+            pub fn cec_parts_pipeline_submit_from(
+                pipeline: *mut cec_parts_pipeline,
+                slot: usize,
+                data_bufs: *const *const u8,
+                lengths: *const usize,
+                n_parts: usize,
+                chunksizes: *mut usize,
+            ) -> c_int;
+            pub fn cec_parts_pipeline_wait(
+                pipeline: *mut cec_parts_pipeline,
+                slot: usize,
+                parity: *mut *const u8,
+                digests: *mut *const u8,
+                n_parts: *mut usize,
+            ) -> c_int;
+            pub fn cec_parts_pipeline_query(pipeline: *mut cec_parts_pipeline, slot: usize) -> c_int;
+            pub fn cec_parts_pipeline_drain(pipeline: *mut cec_parts_pipeline) -> c_int;
+        }
     }
 }
 
@@ -896,6 +968,73 @@ pub unsafe fn encode_hash_ragged(
     ))
 }
 
+/// The packed split ragged layout (`cec_split_layout`): the data chunks of all parts in one
+/// region, their parity chunks in another.
+pub struct SplitLayout {
+    pub data_offsets: Vec<usize>,
+    pub parity_offsets: Vec<usize>,
+    pub data_bytes: usize,
+    pub parity_bytes: usize,
+}
+
+pub fn split_layout(data_shards: usize, parity_shards: usize, chunk_lens: &[usize]) -> Result<SplitLayout, CecError> {
+    let mut l = SplitLayout {
+        data_offsets: vec![0usize; chunk_lens.len()],
+        parity_offsets: vec![0usize; chunk_lens.len()],
+        data_bytes: 0,
+        parity_bytes: 0,
+    };
+    check(unsafe {
+        sys::cec_split_layout(
+            data_shards,
+            parity_shards,
+            chunk_lens.as_ptr(),
+            chunk_lens.len(),
+            l.data_offsets.as_mut_ptr(),
+            l.parity_offsets.as_mut_ptr(),
+            &mut l.data_bytes,
+            &mut l.parity_bytes,
+        )
+    })?;
+    Ok(l)
+}
+
+/// `cec_encode_hash_split`: [`encode_hash_ragged`] over the split layout; the data region is only
+/// read, exactly `chunk_lens[k]` bytes of each parity chunk are written.
+///
+/// # Safety
+/// `data_base`, `parity_base` and `digests` must be device pointers covering the two regions the
+/// offsets and lengths describe and `[n][d+p][32]` bytes; `stream` a HIP stream of the current
+/// device or null.
+pub unsafe fn encode_hash_split(
+    codec: &ReedSolomon,
+    data_base: *const u8,
+    data_offsets: &[usize],
+    parity_base: *mut u8,
+    parity_offsets: &[usize],
+    chunk_lens: &[usize],
+    digests: *mut u8,
+    stream: *mut c_void,
+) -> Result<(), CecError> {
+    if data_offsets.len() != chunk_lens.len() || parity_offsets.len() != chunk_lens.len() {
+        return Err(CecError::Engine(EngineError {
+            code: 101,
+            message: "offsets and chunk_lens differ in length".to_string(),
+        }));
+    }
+    check(sys::cec_encode_hash_split(
+        codec.raw,
+        data_base,
+        data_offsets.as_ptr(),
+        parity_base,
+        parity_offsets.as_ptr(),
+        chunk_lens.as_ptr(),
+        chunk_lens.len(),
+        digests,
+        stream,
+    ))
+}
+
 /// `cec_reconstruct_ragged`: `reconstruct` (`data_only` false) / `reconstruct_data` (true) of parts
 /// of different chunk lengths in device memory, asynchronous on `stream`.  `present` holds
 /// `n * (d+p)` flags.
@@ -1170,6 +1309,112 @@ impl WritePipeline {
     /// Wait for every submitted batch.
     pub fn drain(&mut self) -> Result<(), CecError> {
         check_pipe(unsafe { sys::cec_pipeline_drain(self.raw) })
+    }
+}
+
+/// [`parts_encode`] with `depth` slots in flight (`cec_parts_pipeline_*`): batches of parts whose
+/// chunk lengths differ, in the split ragged layout ([`split_layout`]).  One thread drives a
+/// pipeline (it is `Send`, not `Sync`).  Per slot: [`acquire`](Self::acquire) hands out the
+/// pinned data region, [`submit`](Self::submit) queues a batch the caller packed there,
+/// [`submit_from`](Self::submit_from) lets the engine pack the caller's buffers, and
+/// [`wait`](Self::wait) borrows the slot's pinned parity region and the digests.
+pub struct PartsPipeline {
+    raw: *mut sys::cec_parts_pipeline,
+    d: usize,
+    p: usize,
+    slot_data_bytes: usize,
+}
+
+unsafe impl Send for PartsPipeline {}
+
+impl Drop for PartsPipeline {
+    fn drop(&mut self) {
+        unsafe { sys::parts::cec_parts_pipeline_free(self.raw) }
+    }
+}
+
+/// One completed ragged batch: the slot's parity region (part k's parity chunk i at
+/// `parity_offsets[k] + i * ragged_stride(L_k)` of [`split_layout`]) and digests
+/// `[parts][d+p][32]`, pinned host memory owned by the slot until it is acquired again.
+pub struct PartsResult<'a> {
+    pub parity: &'a [u8],
+    pub digests: &'a [u8],
+    pub n_parts: usize,
+}
+
+impl PartsPipeline {
+    pub fn new(
+        codec: &ReedSolomon,
+        slot_data_bytes: usize,
+        max_parts: usize,
+        depth: usize,
+    ) -> Result<PartsPipeline, CecError> {
+        let mut raw = std::ptr::null_mut();
+        check(unsafe { sys::parts::cec_parts_pipeline_new(codec.raw, slot_data_bytes, max_parts, depth, &mut raw) })?;
+        Ok(PartsPipeline {
+            raw,
+            d: codec.data_shard_count(),
+            p: codec.parity_shard_count(),
+            slot_data_bytes,
+        })
+    }
+
+    pub fn depth(&self) -> usize {
+        unsafe { sys::parts::cec_parts_pipeline_depth(self.raw) }
+    }
+
+    /// Next slot (waits for its previous batch) and its pinned data region.
+    pub fn acquire(&mut self) -> Result<(usize, &mut [u8]), CecError> {
+        let mut slot = 0usize;
+        let mut data = std::ptr::null_mut();
+        check(unsafe { sys::parts::cec_parts_pipeline_acquire(self.raw, &mut slot, &mut data) })?;
+        Ok((slot, unsafe { std::slice::from_raw_parts_mut(data, self.slot_data_bytes) }))
+    }
+
+    /// Queue the batch the caller wrote into `slot` in the packed split layout (asynchronous).
+    pub fn submit(&mut self, slot: usize, chunk_lens: &[usize]) -> Result<(), CecError> {
+        check(unsafe { sys::parts::cec_parts_pipeline_submit(self.raw, slot, chunk_lens.as_ptr(), chunk_lens.len()) })
+    }
+
+    /// Pack `bufs` (part k is the whole of `bufs[k]`) into `slot` and queue them; returns the
+    /// parts' chunk sizes.
+    pub fn submit_from(&mut self, slot: usize, bufs: &[&[u8]]) -> Result<Vec<usize>, CecError> {
+        let ptrs: Vec<*const u8> = bufs.iter().map(|b| b.as_ptr()).collect();
+        let lens: Vec<usize> = bufs.iter().map(|b| b.len()).collect();
+        let mut cs = vec![0usize; bufs.len()];
+        check(unsafe {
+            sys::parts::cec_parts_pipeline_submit_from(self.raw, slot, ptrs.as_ptr(), lens.as_ptr(), bufs.len(), cs.as_mut_ptr())
+        })?;
+        Ok(cs)
+    }
+
+    /// Wait for `slot`'s batch of these chunk lengths and borrow its parity and digests.
+    pub fn wait(&mut self, slot: usize, chunk_lens: &[usize]) -> Result<PartsResult<'_>, CecError> {
+        let mut parity = std::ptr::null();
+        let mut digests = std::ptr::null();
+        let mut n_parts = 0usize;
+        check(unsafe { sys::parts::cec_parts_pipeline_wait(self.raw, slot, &mut parity, &mut digests, &mut n_parts) })?;
+        let plen: usize = chunk_lens.iter().take(n_parts).map(|&l| self.p * ragged_stride(l)).sum();
+        let dlen = n_parts * (self.d + self.p) * 32;
+        Ok(PartsResult {
+            parity: unsafe { std::slice::from_raw_parts(parity, plen) },
+            digests: unsafe { std::slice::from_raw_parts(digests, dlen) },
+            n_parts,
+        })
+    }
+
+    /// Whether `slot`'s batch is complete (never blocks).
+    pub fn query(&mut self, slot: usize) -> Result<bool, CecError> {
+        match unsafe { sys::parts::cec_parts_pipeline_query(self.raw, slot) } {
+            0 => Ok(false),
+            1 => Ok(true),
+            code => check(code).map(|_| true),
+        }
+    }
+
+    /// Wait for every submitted batch.
+    pub fn drain(&mut self) -> Result<(), CecError> {
+        check(unsafe { sys::parts::cec_parts_pipeline_drain(self.raw) })
     }
 }
 

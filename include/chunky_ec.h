@@ -25,9 +25,11 @@
  *     FilePart::resilver compute (file_part.rs:266-308)    -> cec_reconstruct_batch (data_only = 0)
  *     FilePart::verify (file_part.rs:228-251)              -> cec_sha256_batch
  *   and, for parts whose chunk lengths differ (whole small files, short last parts), the ragged
- *   forms of the four: cec_parts_encode / cec_encode_hash_ragged (write), cec_parts_read /
- *   cec_read_ragged (read), cec_parts_read / cec_resilver_ragged (resilver), cec_parts_verify /
- *   cec_verify_ragged (verify).
+ *   forms of the four: cec_parts_encode / cec_encode_hash_ragged (write; with the data and the
+ *   parity in regions of their own cec_encode_hash_split, and with slots in flight the ragged
+ *   write pipeline cec_parts_pipeline_*, chunky_ec_parts.h), cec_parts_read / cec_read_ragged (read),
+ *   cec_parts_read / cec_resilver_ragged (resilver), cec_parts_verify / cec_verify_ragged
+ *   (verify).
  *
  * Conventions
  *   - Plain pointers and sizes only; every buffer is owned by the caller.
@@ -101,7 +103,7 @@ int cec_device_numa_node(int device);
 const char* cec_build_info(void);
 /* Provenance: 16 hex digits, the hash of the sources the library was built from
  * (chunky-bits_amd/csrc/source_hash.py: every .cpp, .hip and .hpp file of csrc, its Makefile
- * and this header).  The Python binding refuses a library whose id differs from its shipped sources. */
+ * and this header with chunky_ec_parts.h).  The Python binding refuses a library whose id differs from its shipped sources. */
 const char* cec_build_id(void);
 /* Environment knobs (CEC_APPLY_*, CEC_FUSED*, CEC_SHA_VARIANT, CEC_COALESCE_*, ...;
  * DESIGN.md §6.3) are read ONCE, on the first call that needs one, into an immutable snapshot;
@@ -296,6 +298,31 @@ int cec_ragged_layout(size_t total_shards, const size_t* chunk_lens, size_t n_pa
 int cec_encode_hash_ragged(const cec_codec* codec, uint8_t* base, const size_t* part_offsets,
                            const size_t* chunk_lens, size_t n_parts, uint8_t* digests,
                            void* stream);
+
+/* Split ragged layout: the same parts with their data chunks in one region and their parity
+ * chunks in another, so a host-staged writer moves the data up and the parity back in one copy
+ * each.  With cs = cec_ragged_stride(chunk_lens[k]), part k's data chunk j is chunk_lens[k] bytes
+ * at data_base + data_offsets[k] + j*cs and its parity chunk i is chunk_lens[k] bytes at
+ * parity_base + parity_offsets[k] + i*cs; both bases and all offsets are multiples of 16.
+ * cec_split_layout: the packed form (data_offsets[k+1] = data_offsets[k] + d*cs,
+ * parity_offsets[k+1] = parity_offsets[k] + p*cs) and the two regions' sizes; errors as
+ * cec_ragged_layout (a zero shard count, null pointers, a zero chunk length, overflow).
+ * cec_encode_hash_split: cec_encode_hash_ragged over that layout.  Exactly chunk_lens[k] bytes of
+ * each parity chunk are written; not one byte of the data region, nor the padding up to the
+ * stride, nor anything between parts.  Digests as cec_encode_hash_ragged ([n_parts][d+p][32]).
+ * The bases and digests are DEVICE pointers; the offset and length arrays are HOST arrays, copied
+ * before the call returns.  Asynchronous on `stream`.  Errors, all before any device use and in
+ * this order: null pointer -> CEC_ERR_INVALID_ARGUMENT; any chunk_lens[k] == 0 ->
+ * CEC_EMPTY_SHARD; a base or an offset not a multiple of 16, offsets not ascending and disjoint
+ * within a region, the two regions' byte ranges overlapping, or counts beyond the kernels'
+ * 32-bit indices -> CEC_ERR_INVALID_ARGUMENT; then CEC_ERR_NO_DEVICE.  n_parts == 0 -> CEC_OK. */
+int cec_split_layout(size_t data_shards, size_t parity_shards, const size_t* chunk_lens,
+                     size_t n_parts, size_t* data_offsets, size_t* parity_offsets,
+                     size_t* data_bytes, size_t* parity_bytes);
+int cec_encode_hash_split(const cec_codec* codec, const uint8_t* data_base,
+                          const size_t* data_offsets, uint8_t* parity_base,
+                          const size_t* parity_offsets, const size_t* chunk_lens, size_t n_parts,
+                          uint8_t* digests, void* stream);
 
 /* SHA-256 of chunks [first_chunk, first_chunk + n_chunks) of every part.
  * digests: device buffer, digest of (part k, chunk first_chunk + c) at (k*n_chunks + c)*32. */
@@ -676,5 +703,9 @@ uint8_t cec_synth_byte(uint64_t seed, uint64_t part, uint64_t chunk, uint64_t of
 #ifdef __cplusplus
 }
 #endif
+
+/* The ragged write pipeline (cec_parts_pipeline_*) has a header of its own, which this one
+ * brings along. */
+#include "chunky_ec_parts.h"
 
 #endif /* CHUNKY_EC_H */

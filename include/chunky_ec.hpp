@@ -369,6 +369,34 @@ inline cec_multi* cached_multi(size_t d, size_t p, size_t L, size_t parts, size_
     }
     return e.multi.get();
 }
+
+// The calling thread's most recent ragged write pipeline (FileWriteBuilder::write_many_stream),
+// kept like the scheduler above: per (d, p, slot bytes, parts per slot, depth) and device.
+struct CachedPartsPipeline {
+    std::vector<size_t> key;
+    std::shared_ptr<ReedSolomon> codec;
+    std::shared_ptr<cec_parts_pipeline> pipe;
+};
+inline CachedPartsPipeline& cached_parts_pipeline_entry() {
+    thread_local CachedPartsPipeline e;
+    return e;
+}
+inline cec_parts_pipeline* cached_parts_pipeline(size_t d, size_t p, size_t slot_bytes,
+                                                 size_t max_parts, size_t depth) {
+    CachedPartsPipeline& e = cached_parts_pipeline_entry();
+    int device = 0;
+    check(cec_current_device(&device));
+    const std::vector<size_t> key{d, p, slot_bytes, max_parts, depth, size_t(device)};
+    if (!e.pipe || e.key != key) {
+        e.pipe.reset();
+        e.codec = std::make_shared<ReedSolomon>(d, p);
+        cec_parts_pipeline* raw = nullptr;
+        check(cec_parts_pipeline_new(e.codec->raw(), slot_bytes, max_parts, depth, &raw));
+        e.pipe = std::shared_ptr<cec_parts_pipeline>(raw, cec_parts_pipeline_free);
+        e.key = key;
+    }
+    return e.pipe.get();
+}
 }  // namespace detail
 
 // file::hash::Sha256Hash.
@@ -805,9 +833,10 @@ template <typename T>
 struct ManyWindow {
     std::vector<T> items;
     size_t bytes = 0;
+    size_t cap = kManyWindowBytes, max_items = SIZE_MAX;  // a caller with its own budget sets them
     template <typename Flush>
     void add(T item, size_t size, Flush&& fn) {
-        if (!items.empty() && bytes + size > kManyWindowBytes) flush(fn);
+        if (!items.empty() && (bytes + size > cap || items.size() >= max_items)) flush(fn);
         items.push_back(std::move(item));
         bytes += size;
     }
@@ -2010,15 +2039,10 @@ class FileWriteBuilder {
         const std::vector<std::pair<const uint8_t*, size_t>>& files, ChunkStore& dest) const {
         if (concurrency_ <= 1) throw std::invalid_argument("concurrency must be > 1");  // :128
         const ReedSolomon encoder(data_, parity_);
-        const size_t d = data_, p = parity_, t = d + p, part_cap = data_ * chunk_size_;
+        const size_t d = data_, p = parity_, t = d + p;
         std::vector<FileReference> out(files.size());
-        struct Pending {
-            size_t file;
-            const uint8_t* bytes;
-            size_t length;
-        };
-        detail::ManyWindow<Pending> window;  // budget: data bytes
-        auto flush = [&](const std::vector<Pending>& pend) {
+        detail::ManyWindow<ManyPart> window;  // budget: data bytes
+        auto flush = [&](const std::vector<ManyPart>& pend) {
             const size_t n = pend.size();
             std::vector<const uint8_t*> bufs(n);
             std::vector<size_t> lengths(n), chunksizes(n);
@@ -2033,39 +2057,97 @@ class FileWriteBuilder {
             }
             detail::check(cec_parts_encode(encoder.raw(), bufs.data(), lengths.data(), n,
                                            parity_ptrs.data(), digests.data(), chunksizes.data()));
-            Bytes edge;  // a data chunk that reaches past the file's bytes, zero padded
-            for (size_t k = 0; k < n; ++k) {
-                const size_t L = chunksizes[k], len = pend[k].length;
-                auto bytes_of = [&](size_t i) -> const uint8_t* {
-                    if (i >= d) return &parity[k][(i - d) * L];
-                    if ((i + 1) * L <= len) return pend[k].bytes + i * L;
-                    edge.assign(L, 0);
-                    if (i * L < len) std::memcpy(edge.data(), pend[k].bytes + i * L, len - i * L);
-                    return edge.data();
-                };
-                out[pend[k].file].parts.push_back(
-                    FilePart::from_digests(dest, &digests[k * t * 32], L, d, t, bytes_of));
-            }
+            for (size_t k = 0; k < n; ++k)
+                out[pend[k].file].parts.push_back(many_part(
+                    dest, pend[k], chunksizes[k], &digests[k * t * 32],
+                    [&](size_t i) { return &parity[k][i * chunksizes[k]]; }));
         };
-        for (size_t f = 0; f < files.size(); ++f) {
-            const uint8_t* bytes = files[f].first;
-            const size_t n = files[f].second;
-            const size_t full = n / part_cap;
-            size_t off = 0;
-            if (batch_ && full >= 2) {
-                window.flush(flush);  // earlier files' parts reach dest before this file's
-                write_full_parts(bytes, full, dest, out[f]);
-                off = full * part_cap;
-            }
-            for (; off < n; off += part_cap) {
-                const size_t length = std::min(part_cap, n - off);
-                window.add(Pending{f, bytes + off, length}, length, flush);
-            }
-            out[f].length = n;
-        }
-        window.flush(flush);
+        gather_many(files, dest, out, window, flush, [] {}, [](size_t length) { return length; });
         return out;
     }
+
+    // write_many with the gathered parts streamed through a ragged write pipeline
+    // (cec_parts_pipeline_*) instead of one cec_parts_encode call per window: same results, same
+    // order towards dest.  A window is a slot's batch (submit_from: the engine packs it straight
+    // from the callers' bytes); while later slots are packed, copied and encoded, the oldest is
+    // collected: its parts' chunks go to dest.write_shard with the parity read in the slot's
+    // page-locked region, no copy in between.  The pipeline is the calling thread's, kept between
+    // calls (see release_thread_buffers); many_slots() sets its slots.
+    std::vector<FileReference> write_many_stream(
+        const std::vector<std::pair<const uint8_t*, size_t>>& files, ChunkStore& dest) const {
+        if (concurrency_ <= 1) throw std::invalid_argument("concurrency must be > 1");  // :128
+        const size_t d = data_, p = parity_, t = d + p;
+        // never smaller than one part, so every part fits a slot
+        const size_t slot_bytes = std::max(many_slot_bytes_, d * cec_ragged_stride(chunk_size_));
+        cec_parts_pipeline* pl =
+            detail::cached_parts_pipeline(d, p, slot_bytes, kManySlotParts, many_depth_);
+        std::vector<FileReference> out(files.size());
+        struct Batch {
+            size_t slot;
+            std::vector<ManyPart> parts;
+            std::vector<size_t> chunksizes;
+        };
+        std::deque<Batch> flying;  // oldest first
+        auto collect = [&] {
+            Batch b = std::move(flying.front());
+            flying.pop_front();
+            const size_t n = b.parts.size();
+            const uint8_t *parity = nullptr, *digests = nullptr;
+            size_t got = 0;
+            detail::check(cec_parts_pipeline_wait(pl, b.slot, &parity, &digests, &got));
+            if (got != n) throw std::logic_error("write_many_stream: a slot lost its batch");
+            std::vector<size_t> doffs(n), poffs(n);
+            size_t data_bytes = 0, parity_bytes = 0;
+            detail::check(cec_split_layout(d, p, b.chunksizes.data(), n, doffs.data(), poffs.data(),
+                                           &data_bytes, &parity_bytes));
+            for (size_t k = 0; k < n; ++k) {
+                const size_t cs = cec_ragged_stride(b.chunksizes[k]);
+                out[b.parts[k].file].parts.push_back(
+                    many_part(dest, b.parts[k], b.chunksizes[k], digests + k * t * 32,
+                              [&](size_t i) { return parity + poffs[k] + i * cs; }));
+            }
+        };
+        auto settle = [&] {
+            while (!flying.empty()) collect();
+        };
+        detail::ManyWindow<ManyPart> window;  // budget: a slot's padded data bytes and parts
+        window.cap = slot_bytes;
+        window.max_items = kManySlotParts;
+        auto flush = [&](const std::vector<ManyPart>& pend) {
+            if (flying.size() == many_depth_) collect();  // the slot that comes round next
+            const size_t n = pend.size();
+            std::vector<const uint8_t*> bufs(n);
+            std::vector<size_t> lengths(n);
+            for (size_t k = 0; k < n; ++k) {
+                bufs[k] = pend[k].bytes;
+                lengths[k] = pend[k].length;
+            }
+            Batch b{0, pend, std::vector<size_t>(n)};
+            uint8_t* region = nullptr;
+            detail::check(cec_parts_pipeline_acquire(pl, &b.slot, &region));
+            detail::check(cec_parts_pipeline_submit_from(pl, b.slot, bufs.data(), lengths.data(), n,
+                                                         b.chunksizes.data()));
+            flying.push_back(std::move(b));
+        };
+        try {
+            gather_many(files, dest, out, window, flush, settle,
+                        [&](size_t length) { return d * cec_ragged_stride((length + d - 1) / d); });
+        } catch (...) {
+            (void)cec_parts_pipeline_drain(pl);  // nothing of this call stays in flight
+            throw;
+        }
+        return out;
+    }
+
+    // The slots of write_many_stream's pipeline: data bytes per slot (raised to one part's where
+    // smaller) and slots in flight.
+    FileWriteBuilder& many_slots(size_t slot_bytes, size_t depth) {
+        if (depth == 0) throw std::invalid_argument("many_slots: depth must be > 0");
+        many_slot_bytes_ = slot_bytes;
+        many_depth_ = depth;
+        return *this;
+    }
+    static constexpr size_t kManySlotParts = 4096;  // parts a slot's batch holds at most
 
    public:
     // The page-locked windows of the calling thread's batched writes (see release_thread_buffers).
@@ -2088,6 +2170,61 @@ class FileWriteBuilder {
     size_t depth_ = 4;
     size_t concurrency_ = 10;  // the reference's default (writer.rs:56)
     std::vector<int> devices_;
+    size_t many_slot_bytes_ = size_t(64) << 20;  // write_many_stream's slots (many_slots)
+    size_t many_depth_ = 3;
+
+    // A part the many-files calls gathered: `length` bytes of file `file`.
+    struct ManyPart {
+        size_t file;
+        const uint8_t* bytes;
+        size_t length;
+    };
+
+    // The gather loop of write_many / write_many_stream.  The full parts of a file with at least
+    // two of them go through write_full_parts when batch() is set, after flush and settle() have
+    // brought every earlier part to dest; every other part goes into `window` with the budget
+    // size_of(length), which hands full windows to flush.
+    template <typename Flush, typename Settle, typename SizeOf>
+    void gather_many(const std::vector<std::pair<const uint8_t*, size_t>>& files, ChunkStore& dest,
+                     std::vector<FileReference>& out, detail::ManyWindow<ManyPart>& window,
+                     Flush&& flush, Settle&& settle, SizeOf&& size_of) const {
+        const size_t part_cap = data_ * chunk_size_;
+        for (size_t f = 0; f < files.size(); ++f) {
+            const uint8_t* bytes = files[f].first;
+            const size_t n = files[f].second;
+            const size_t full = n / part_cap;
+            size_t off = 0;
+            if (batch_ && full >= 2) {
+                window.flush(flush);  // earlier files' parts reach dest before this file's
+                settle();
+                write_full_parts(bytes, full, dest, out[f]);
+                off = full * part_cap;
+            }
+            for (; off < n; off += part_cap) {
+                const size_t length = std::min(part_cap, n - off);
+                window.add(ManyPart{f, bytes + off, length}, size_of(length), flush);
+            }
+            out[f].length = n;
+        }
+        window.flush(flush);
+        settle();
+    }
+
+    // A gathered part of chunk size L written to dest: data chunks from the file's bytes (the one
+    // that reaches past them zero padded), parity chunk i from parity_of(i).
+    template <typename ParityOf>
+    FilePart many_part(ChunkStore& dest, const ManyPart& part, size_t L, const uint8_t* digests,
+                       ParityOf&& parity_of) const {
+        const size_t d = data_, len = part.length;
+        Bytes edge;
+        return FilePart::from_digests(dest, digests, L, d, d + parity_, [&](size_t i) -> const uint8_t* {
+            if (i >= d) return parity_of(i - d);
+            if ((i + 1) * L <= len) return part.bytes + i * L;
+            edge.assign(L, 0);
+            if (i * L < len) std::memcpy(edge.data(), part.bytes + i * L, len - i * L);
+            return edge.data();
+        });
+    }
 
     // The `full` parts of d*chunk_size bytes through the multi-GPU scheduler, in windows of
     // batch * depth * shards parts with two windows in flight: same FileParts and stored chunks as
@@ -2164,6 +2301,7 @@ inline void release_thread_buffers() {
         w.prepass.release();
     }
     detail::cached_multi_entry() = detail::CachedMulti{};
+    detail::cached_parts_pipeline_entry() = detail::CachedPartsPipeline{};
 }
 
 }  // namespace chunky_ec

@@ -8,13 +8,19 @@ RS(10,4).  Three arms produce the same parts:
      each part that call needs is made before the clock starts)
   b  one cec_parts_encode call over all parts, straight from the files' bytes
   c  the CPU oracle (the crate's path restated in C) on 16 threads
+  d  the parts pipeline: cec_parts_pipeline_submit_from per slot-sized batch of consecutive
+     parts, straight from the files' bytes, one arm per --depths entry (3 and 2 slots in flight
+     by default, --slot-mib of data each; --no-per-part leaves the a arms out); the oldest
+     slot is collected while the later ones run.  The digests are copied out; the parity stays in
+     the slot's pinned region, where FileWriteBuilder reads it (compared with b's once, untimed)
 
 Every arm is warmed up, then the arms alternate three times in one process; the device is
 synchronised before each clock reading.  Reported: GB/s of file bytes and parts/s per repeat.
 All arms' digests must agree (asserted).
 
 --device: 4096 x RS(10,4) x 64 KiB parts, device resident: cec_encode_hash_ragged with uniform
-lengths against cec_encode_hash_batch on the same bytes; both times and the ratio.
+lengths and cec_encode_hash_split (the same parts, data and parity in regions of their own)
+against cec_encode_hash_batch on the same bytes; the times and the ratios.
 
 --read: the read side on the same seeded files and shapes.  Every part is stored as the oracle
 encodes it and its data chunk k % d is erased, so every part is decoded from d - 1 data chunks and
@@ -42,6 +48,7 @@ Every arm must find every chunk good, and the one chunk that is flipped before t
 (asserted).
 
     python tools/small_files_bench.py [--files 4096] [--repeats 3] [--shapes 3,2:10,4]
+                                      [--slot-mib 64] [--depths 3,2] [--no-per-part]
     python tools/small_files_bench.py --device
     python tools/small_files_bench.py --read
     python tools/small_files_bench.py --verify
@@ -151,6 +158,64 @@ class Workload:
             list(ex.map(lambda k: self._one(fn, dig, k), range(count or self.n)))
         return dig
 
+    def make_pipeline(self, slot_bytes, depth, max_parts=4096):
+        """A cec_parts_pipeline and the batches the parts fall into (consecutive parts while
+        their padded data fits a slot and their count max_parts), made before any clock starts,
+        as FileWriteBuilder keeps its pipeline between calls."""
+        d = self.d
+        slot_bytes = max(slot_bytes, d * ce.ragged_stride(CHUNK))
+        pl = ce.PartsPipeline(self.rs, slot_bytes, max_parts, depth)
+        batches, k0, used = [], 0, 0
+        for k, L in enumerate(self.L):
+            b = d * ce.ragged_stride(L)
+            if k > k0 and (used + b > slot_bytes or k - k0 == max_parts):
+                batches.append((k0, k))
+                k0, used = k, 0
+            used += b
+        batches.append((k0, self.n))
+        pp = ctypes.POINTER(U8P)
+        szp = ctypes.POINTER(ctypes.c_size_t)
+        step = ctypes.sizeof(ctypes.c_size_t)
+        args = [(ctypes.cast(ctypes.addressof(self.ptrs) + a * ctypes.sizeof(U8P), pp),
+                 ctypes.cast(ctypes.addressof(self.lens) + a * step, szp), b - a,
+                 ctypes.cast(ctypes.addressof(self.chunksizes) + a * step, szp))
+                for a, b in batches]
+        return pl, batches, args
+
+    def arm_pipeline(self, pipe, check_parity=False):
+        """Every batch through the pipeline's slots with submit_from; while later slots run the
+        oldest is collected: its digests copied out, its parity left in the slot's pinned region
+        (where FileWriteBuilder reads it) unless check_parity compares it with self.parity."""
+        pl, batches, args = pipe
+        dig = self.digests()
+        lib, h, t = ce._lib, pl._h, self.t
+        slot, ptr, par, dg, n = (ctypes.c_size_t(0), U8P(), U8P(), U8P(), ctypes.c_size_t(0))
+        pending = []
+
+        def collect():
+            s, (a, b) = pending.pop(0)
+            ce._check(lib.cec_parts_pipeline_wait(h, s, ctypes.byref(par), ctypes.byref(dg),
+                                                  ctypes.byref(n)))
+            assert n.value == b - a
+            ctypes.memmove(dig.ctypes.data + a * t * 32, dg, (b - a) * t * 32)
+            if check_parity:
+                _, poffs, _, pb = ce.split_layout(self.d, self.p, self.L[a:b])
+                got = np.ctypeslib.as_array(par, shape=(pb,))
+                for k in range(a, b):
+                    L, cs = self.L[k], ce.ragged_stride(self.L[k])
+                    for i in range(self.p):
+                        at, to = poffs[k - a] + i * cs, int(self.par_off[k]) + i * L
+                        assert np.array_equal(got[at:at + L], self.parity[to:to + L]), (k, i)
+        for rng, (bufs, lens, cnt, cs) in zip(batches, args):
+            if len(pending) == pl.depth:
+                collect()
+            ce._check(lib.cec_parts_pipeline_acquire(h, ctypes.byref(slot), ctypes.byref(ptr)))
+            ce._check(lib.cec_parts_pipeline_submit_from(h, slot.value, bufs, lens, cnt, cs))
+            pending.append((slot.value, rng))
+        while pending:
+            collect()
+        return dig
+
 
 def timed(fn):
     torch.cuda.synchronize()
@@ -172,10 +237,22 @@ def host_staged(args):
                 ("a: part_encode x 256 threads", lambda c=None: w.arm_percall(256, c)),
                 ("b: one parts_encode call", lambda c=None: w.arm_ragged(c)),
                 ("c: CPU oracle x 16 threads", lambda c=None: w.arm_cpu(16, c))]
+        slot = args.slot_mib << 20
+        if args.no_per_part:  # a quick look at arm d: the per-part arms take most of a run
+            arms = [arm for arm in arms if not arm[0].startswith("a")]
+        pipes = {depth: w.make_pipeline(slot, depth) for depth in args.depths}
+        d_names = {depth: f"d: parts pipeline (submit_from) {args.slot_mib} MiB x {depth}"
+                   for depth in pipes}
+        for depth, pipe in pipes.items():
+            arms.append((d_names[depth], lambda c=None, pipe=pipe: w.arm_pipeline(pipe)))
         warm = min(w.n, 512)
-        for name, fn in arms:  # warm-up: b on the whole input (its staging is sized by it)
-            sec, _ = timed(lambda: fn(None if name.startswith("b") else warm))
+        for name, fn in arms:  # warm-up: b and d on the whole input (b's staging is sized by it)
+            sec, _ = timed(lambda: fn(None if name[0] in "bd" else warm))
             print(f"   warm-up {name}: {sec:.3f} s", flush=True)
+        for depth, pipe in pipes.items():  # d's parity, left in the slots, against b's (untimed)
+            w.arm_pipeline(pipe, check_parity=True)
+        print(f"   d: {len(pipes[args.depths[0]][1])} batches; parity in the slots equals b's",
+              flush=True)
         secs = {name: [] for name, _ in arms}
         ref = None
         for rep in range(args.repeats):
@@ -193,15 +270,26 @@ def host_staged(args):
         row = {"d": d, "p": p, "files": len(files), "parts": w.n, "file_bytes": w.file_bytes,
                "seconds": secs,
                "gbps": {k: [w.file_bytes / s / 1e9 for s in v] for k, v in secs.items()}}
-        a, b = secs["a: part_encode x 256 threads"], secs["b: one parts_encode call"]
-        spread = max(max(a) - min(a), max(b) - min(b))
-        row["b_vs_a256"] = {"a_best_s": min(a), "b_worst_s": max(b), "spread_s": spread,
-                            "b_wins_by_more_than_spread": max(b) + spread < min(a)}
-        print(f"   b vs a(256): a best {min(a):.3f} s, b worst {max(b):.3f} s, largest spread "
-              f"{spread:.3f} s -> b wins by more than the spread: "
-              f"{row['b_vs_a256']['b_wins_by_more_than_spread']}", flush=True)
+        b = secs["b: one parts_encode call"]
+        if not args.no_per_part:
+            a = secs["a: part_encode x 256 threads"]
+            spread = max(max(a) - min(a), max(b) - min(b))
+            row["b_vs_a256"] = {"a_best_s": min(a), "b_worst_s": max(b), "spread_s": spread,
+                                "b_wins_by_more_than_spread": max(b) + spread < min(a)}
+            print(f"   b vs a(256): a best {min(a):.3f} s, b worst {max(b):.3f} s, largest spread "
+                  f"{spread:.3f} s -> b wins by more than the spread: "
+                  f"{row['b_vs_a256']['b_wins_by_more_than_spread']}", flush=True)
+        for depth, name in d_names.items():  # the same rule for the pipeline against b
+            dd = secs[name]
+            spread = max(max(dd) - min(dd), max(b) - min(b))
+            wins = max(dd) + spread < min(b)
+            row[f"d{depth}_vs_b"] = {"b_best_s": min(b), "d_worst_s": max(dd), "spread_s": spread,
+                                     "d_wins_by_more_than_spread": wins}
+            print(f"   d (depth {depth}) vs b: b best {min(b):.3f} s, d worst {max(dd):.3f} s, "
+                  f"largest spread {spread:.3f} s -> d wins by more than the spread: {wins}",
+                  flush=True)
         results.append(row)
-        del w
+        del w, pipes
     print(json.dumps({"tool": "small_files_bench", "mode": "host", "results": results}))
 
 
@@ -534,6 +622,17 @@ def device_mode(args):
     def ragged():
         ce.encode_hash_ragged(rs, buf.data_ptr(), offs, lens, dig_r.data_ptr())
 
+    # the same data chunks in a region of their own, the parity in another
+    sdata = buf[:, :d].contiguous()
+    spar = torch.zeros((n, p, L), dtype=torch.uint8, device=dev)
+    dig_s = torch.zeros_like(dig_u)
+    doffs, poffs, db, pb = ce.split_layout(d, p, lens)
+    assert db == sdata.numel() and pb == spar.numel()
+
+    def split():
+        ce.encode_hash_split(rs, sdata.data_ptr(), doffs, spar.data_ptr(), poffs, lens,
+                             dig_s.data_ptr())
+
     def run(fn):
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -543,24 +642,32 @@ def device_mode(args):
         torch.cuda.synchronize()
         return e0.elapsed_time(e1)
 
-    for fn in (uniform, ragged):
+    for fn in (uniform, ragged, split):
         run(fn)
     uniform()
     torch.cuda.synchronize()
     parity = buf[:, d:].clone()
     ragged()
+    split()
     torch.cuda.synchronize()
     assert torch.equal(parity, buf[:, d:]) and torch.equal(dig_u, dig_r), "results differ"
-    ms = {"encode_hash_batch": [], "encode_hash_ragged": []}
+    assert torch.equal(parity, spar) and torch.equal(dig_u, dig_s), "split results differ"
+    ms = {"encode_hash_batch": [], "encode_hash_ragged": [], "encode_hash_split": []}
     for rep in range(args.repeats):
         ms["encode_hash_batch"].append(run(uniform))
         ms["encode_hash_ragged"].append(run(ragged))
+        ms["encode_hash_split"].append(run(split))
     print(f"== device resident, {n} x RS({d},{p}) x {L} B ({n * d * L / 2**30:.2f} GiB of data)")
     for k, v in ms.items():
         print(f"   {k}: " + "  ".join(f"{x:.3f} ms" for x in v))
     ratio = min(ms["encode_hash_ragged"]) / min(ms["encode_hash_batch"])
+    split_ratio = min(ms["encode_hash_split"]) / min(ms["encode_hash_ragged"])
+    spread = max(max(v) - min(v) for v in ms.values())
     print(f"   ragged / uniform (best of {args.repeats}): {ratio:.3f}   (same parity, same digests)")
-    print(json.dumps({"tool": "small_files_bench", "mode": "device", "ms": ms, "ratio": ratio}))
+    print(f"   split / ragged (best of {args.repeats}): {split_ratio:.3f}   largest spread between "
+          f"repeats of an arm: {spread:.3f} ms")
+    print(json.dumps({"tool": "small_files_bench", "mode": "device", "ms": ms, "ratio": ratio,
+                      "split_over_ragged": split_ratio, "spread_ms": spread}))
 
 
 def main():
@@ -568,6 +675,10 @@ def main():
     ap.add_argument("--files", type=int, default=4096)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--shapes", default="3,2:10,4")
+    ap.add_argument("--slot-mib", type=int, default=64, help="arm d: data bytes per slot")
+    ap.add_argument("--depths", type=lambda s: [int(x) for x in s.split(",")], default=[3, 2],
+                    help="arm d: one arm per number of slots in flight")
+    ap.add_argument("--no-per-part", action="store_true", help="host mode: leave out the a arms")
     ap.add_argument("--device", action="store_true")
     ap.add_argument("--read", action="store_true")
     ap.add_argument("--verify", action="store_true")
