@@ -251,8 +251,11 @@ def test_two_rank_gloo_drives_hip_path_vs_oracle():
 # Zero-copy pipelines and per-call DMA
 # ----------------------------------------------------------------------------------------------
 
-def test_pipeline_submit_from_pinned_and_pageable():
-    d, p, L, P = 10, 4, 4096, 6
+@pytest.mark.parametrize("d,p,L", [(10, 4, 4096), (3, 2, 683)])
+def test_pipeline_submit_from_pinned_and_pageable(d, p, L):
+    """Caller buffers, a full batch and a partial one.  At L = 683 the device chunk stride is
+    padded to 768, so data and parity cross column by column."""
+    P = 6
     rs = ce.ReedSolomon(d, p)
     pl = ce.Pipeline(rs, L, P, 2, ce.PIPE_EXTERNAL)
     src = _write_inputs(P, d, L, 9)
@@ -266,9 +269,10 @@ def test_pipeline_submit_from_pinned_and_pageable():
     s1, _ = pl.acquire()
     pageable = src.copy()
     par2 = np.zeros((P, p, L), np.uint8)
-    pl.submit_from(s1, pageable, P, par2, None)  # digests into the slot's own buffer
+    pl.submit_from(s1, pageable, P - 1, par2, None)  # digests into the slot's own buffer
     _, dig_b = pl.wait(s1)
-    _check_write(src, par2, dig_b, d, p)
+    assert dig_b.shape[0] == P - 1 and not par2[P - 1].any()
+    _check_write(src[:P - 1], par2, dig_b, d, p)
 
 
 def test_per_call_mixed_pinned_and_pageable_callers_bit_exact():
@@ -672,6 +676,58 @@ def test_read_pipeline_resilver_flag_vs_oracle():
         want = [data[k, j] for j in range(d)] + par
         for i in range(t):
             assert ctypes.string_at(ptrs[k * t + i], L) == want[i].tobytes(), (k, i)
+
+
+def test_read_pipeline_every_mode_in_turn_padded_stride():
+    """One PIPE_EXTERNAL pipeline of depth 1 (every batch reuses the slot) takes the same parts
+    from caller buffers as a verify, a resilver, a rebuilt-only and a plain read batch, and then
+    in the reverse order.  L = 683: the device chunk stride is padded to 768, so runs of chunks
+    and blocks of columns cross as 2-D copies.  A verify batch decodes nothing and reports every
+    part CEC_OK (its result is the verified flags), and data_chunks gives it no pointers."""
+    import ctypes
+    d, p, L, P = 3, 2, 683, 6
+    t = d + p
+    data, chunks, present, expected, ok, status = _read_case(P, d, p, L, 9)
+    # what this seed has to give (no device used yet): a clean part, a part with a corrupted
+    # loaded chunk and still d good ones (wait() decodes it again), a part with fewer than d
+    bad = (present != 0) & (ok == 0)
+    clean = [k for k in range(P) if not status[k] and not bad[k].any()]
+    redo = [k for k in range(P) if not status[k] and bad[k].any()]
+    assert clean and redo and any(status)
+    full = np.zeros((P, t, L), np.uint8)
+    for k in range(P):
+        st, par = oracle.encode_sep(d, p, [data[k, j] for j in range(d)])
+        assert st == 0
+        full[k, :d] = data[k]
+        full[k, d:] = np.stack(par)
+    rs = ce.ReedSolomon(d, p)
+    rp = ce.ReadPipeline(rs, L, P, 1, ce.PIPE_EXTERNAL)
+    hch, hout = ce.HostBuffer(P * t * L), ce.HostBuffer(P * t * L)
+    hch.view(P, t, L)[:] = chunks
+    modes = [ce.READ_VERIFY_ONLY, ce.READ_RESILVER, ce.ReadPipeline.REBUILT_ONLY, 0]
+    for mode in modes + modes[::-1]:
+        verify = mode == ce.READ_VERIFY_ONLY
+        w = {ce.READ_VERIFY_ONLY: 0, ce.READ_RESILVER: t}.get(mode, d)
+        hout.array[:] = 0
+        slot, c, _, _ = rp.acquire()
+        assert slot == 0 and c is None
+        rp.submit_ex(slot, P, chunks=hch, present=present, expected=expected,
+                     data=None if verify else hout, mode=mode)
+        _, ver, stt = rp.wait(slot)
+        assert list(stt) == ([0] * P if verify else status), mode
+        assert np.array_equal(ver, ok), mode
+        if verify:
+            assert not rp.data_chunks(slot, P, t).any()
+            continue
+        ptrs = rp.data_chunks(slot, P, w)
+        for k in range(P):
+            if status[k]:
+                continue
+            for i in range(w):
+                got = ctypes.string_at(int(ptrs[k, i]), L)
+                assert got == full[k, i].tobytes(), (mode, k, i)
+                if mode == ce.ReadPipeline.REBUILT_ONLY and k not in redo and ok[k, i]:
+                    assert int(ptrs[k, i]) == hch.ptr + (k * t + i) * L, (k, i)
 
 
 # ----------------------------------------------------------------------------------------------
