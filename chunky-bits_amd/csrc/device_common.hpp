@@ -8,6 +8,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdint>
 
 namespace cec {
@@ -16,6 +17,28 @@ namespace cec {
 // was not ready, a pointer query on pageable memory), so the hipGetLastError() after the next
 // launch reports that launch only.
 inline void clear_stale_error() { (void)hipGetLastError(); }
+
+constexpr uint32_t kCuLdsBytes = 160u * 1024u;  // LDS of one gfx950 (MI355X) CU
+
+// A nonzero property of the current device, asked once per device through query(dev) and kept in
+// the caller's `cache` (zero-initialised).  The scheduler's worker threads come here at the same
+// time, hence relaxed atomics: threads that race on a device's first call each ask and store the
+// same value.  `unknown` when there is no current device.
+constexpr int kMaxDevices = 64;
+template <typename Query>
+uint32_t per_device(std::atomic<uint32_t> (&cache)[kMaxDevices], uint32_t unknown, Query query) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) {
+        clear_stale_error();
+        return unknown;
+    }
+    uint32_t v = cache[dev].load(std::memory_order_relaxed);
+    if (!v) {
+        v = query(dev);
+        cache[dev].store(v, std::memory_order_relaxed);
+    }
+    return v;
+}
 
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
     return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);

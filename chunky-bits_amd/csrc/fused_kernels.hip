@@ -213,7 +213,7 @@ __global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams 
         // slots until the SHA waves park at the step barrier, which then waits for them.
         if (a.enc_prio == 1u) __builtin_amdgcn_s_setprio(1);
         cu32* pat = as_const(a.pat);
-        cu32* tab = pat + 1 + d + P;  // input j, row r at (j*P + r) * 5
+        cu32* tab = PatView(pat, d, P).tab;  // input j, row r at (j*P + r) * 5
         const uint32_t et = threadIdx.x - kSha;  // table builders: et < kEncThreads
         // Fewer column tasks than encoder threads (wide stripes, 128-byte steps): deal them
         // round-robin over the 4 encoder waves so every SIMD's SHA wave shares its issue slots
@@ -412,13 +412,11 @@ __global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams 
 template <int PMAX, int STEP, int DT, int SW = 4, bool ENC3 = false>
 hipError_t launch_p(const FusedParams& a, hipStream_t s) {
     const size_t lds = size_t(2) * a.parts_per_wg * (a.d + a.p) * (STEP + 16);  // ring
-    const size_t tabs = size_t(DT ? DT : kMaxFusedData) * 256 * (PMAX <= 4 ? 4 : 8);
-    if (lds + tabs > 160 * 1024) return hipErrorInvalidValue;
+    constexpr size_t tabs = size_t(DT ? DT : kMaxFusedData) * 256 * (PMAX <= 4 ? 4 : 8);
+    if (lds + tabs > kCuLdsBytes) return hipErrorInvalidValue;
     static const bool attr = hipFuncSetAttribute(
         reinterpret_cast<const void*>(&encode_hash_kernel<PMAX, STEP, DT, SW, ENC3>),
-        hipFuncAttributeMaxDynamicSharedMemorySize,
-        int(160 * 1024 - size_t(DT ? DT : kMaxFusedData) * 256 * (PMAX <= 4 ? 4 : 8))) ==
-        hipSuccess;
+        hipFuncAttributeMaxDynamicSharedMemorySize, int(kCuLdsBytes - tabs)) == hipSuccess;
     if (!attr) return hipErrorInvalidValue;
     const uint32_t grid = (a.n_parts + a.parts_per_wg - 1) / a.parts_per_wg;
     clear_stale_error();
@@ -483,7 +481,7 @@ hipError_t launch_encode_hash(const FusedParams& in, bool vec16, hipStream_t s) 
             const uint32_t want = uint32_t((uint64_t(a.n_parts) + cus - 1) / cus);
             a.parts_per_wg = std::min(cap, want);
             a.enc_prio = 1u;  // encoder waves at s_setprio 1 (see the kernel's encoder branch)
-            if (size_t(2) * a.parts_per_wg * t * (64 + 16) + size_t(20) * 256 * 8 <= 160 * 1024) {
+            if (size_t(2) * a.parts_per_wg * t * (64 + 16) + size_t(20) * 256 * 8 <= kCuLdsBytes) {
                 if (a.parts_per_wg * t <= 7 * 64 && a.parts_per_wg * (64u / 8u) <= 128)
                     return launch_p<8, 64, 20, 8, true>(a, s);
                 return launch_p<8, 64, 20, 8>(a, s);
@@ -497,7 +495,7 @@ hipError_t launch_encode_hash(const FusedParams& in, bool vec16, hipStream_t s) 
     a.enc_prio = 0u;
     a.parts_per_wg = parts_per_group(t, 256);
     if (a.d <= uint32_t(kMaxFusedData) &&
-        size_t(2) * a.parts_per_wg * t * (256 + 16) + tabs <= 160 * 1024)
+        size_t(2) * a.parts_per_wg * t * (256 + 16) + tabs <= kCuLdsBytes)
         return launch_step<256>(a, s);
     a.parts_per_wg = parts_per_group(t, 128, uint32_t(col_width(int(a.d))));
     return launch_step<128>(a, s);

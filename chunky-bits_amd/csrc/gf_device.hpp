@@ -4,9 +4,24 @@
 #pragma once
 
 #include "device_common.hpp"
+#include "gf256.hpp"
 
 namespace cec {
 namespace gf {
+
+// Rows [row0, n_out) of the pattern record `pat` (d inputs, n_out rows; layout: gf256.hpp).
+// tab is row0's table of input 0; input j's tables for these rows start at tab + j*tab_stride.
+struct PatView {
+    cu32* in_idx;
+    cu32* out_idx;
+    cu32* tab;
+    uint32_t tab_stride;
+    __device__ __forceinline__ PatView(cu32* pat, uint32_t d, uint32_t n_out, uint32_t row0 = 0)
+        : in_idx(pat + 1),
+          out_idx(pat + 1 + d + row0),
+          tab(pat + 1 + d + n_out + size_t(row0) * kTabWords),
+          tab_stride(n_out * kTabWords) {}
+};
 
 struct Sel {
     uint32_t s0, s1, s2;

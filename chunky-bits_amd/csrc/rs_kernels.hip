@@ -70,25 +70,63 @@ __device__ __forceinline__ void st16(uint8_t* p, uint4 v) {
     }
 }
 
+// acc[r][c] = 0 for RG rows x V 16-byte columns.
+template <int RG, int V>
+__device__ __forceinline__ void acc_zero(uint32_t (&acc)[RG][V][4]) {
+#pragma unroll
+    for (int r = 0; r < RG; ++r)
+#pragma unroll
+        for (int c = 0; c < V; ++c) acc[r][c][0] = acc[r][c][1] = acc[r][c][2] = acc[r][c][3] = 0u;
+}
+
+// acc[r] ^= coef[r] (x) v for one input's V columns; tj: the input's RG tables.
+template <int RG, int V>
+__device__ __forceinline__ void mul_input(uint32_t (&acc)[RG][V][4], const uint4 (&v)[V],
+                                          cu32* tj) {
+#pragma unroll
+    for (int c = 0; c < V; ++c) {
+        const Sel s0 = selectors(v[c].x), s1 = selectors(v[c].y), s2 = selectors(v[c].z),
+                  s3 = selectors(v[c].w);
+#pragma unroll
+        for (int r = 0; r < RG; ++r) {
+            cu32* t = tj + r * kTabWords;
+            const uint32_t t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3], t4 = t[4];
+            acc[r][c][0] ^= gmul(s0, t0, t1, t2, t3, t4);
+            acc[r][c][1] ^= gmul(s1, t0, t1, t2, t3, t4);
+            acc[r][c][2] ^= gmul(s2, t0, t1, t2, t3, t4);
+            acc[r][c][3] ^= gmul(s3, t0, t1, t2, t3, t4);
+        }
+    }
+}
+
+// One row's V columns to dst (the row's chunk at the lane's first column): FULL whole 16-byte
+// columns kSpan apart, else the first n bytes of the one column.
+template <bool FULL, bool NT, int V>
+__device__ __forceinline__ void row_store(const uint32_t (&acc)[V][4], uint8_t* dst, uint64_t n) {
+#pragma unroll
+    for (int c = 0; c < V; ++c) {
+        if (FULL)
+            st16<NT>(dst + c * kSpan, make_uint4(acc[c][0], acc[c][1], acc[c][2], acc[c][3]));
+        else
+            store_partial(dst, acc[c], n);
+    }
+}
+
 // V 16-byte columns (x + c*kSpan, c < V) of a part: acc[r] = XOR_j coef[r][j] (x) in_j[...].
 // FULL: every lane of the block has V*16 valid bytes and the layout is 16-byte aligned
 // (otherwise V == 1 with a byte-granular load/store of a rem < 16 tail).
-// tab points at row0's table of input 0; input j's RG tables start at tab + j*tab_stride.
+// p: the RG rows' view of the part's pattern record.
 // GROUP inputs (x V columns) are loaded before any is multiplied; NT selects non-temporal
 // loads/stores (streamed once, never re-read).  out_disp (wave-uniform) is added to every output
 // address: 0 where a part's outputs lie among its inputs' chunks, the distance to the part's
 // place in a parity region of its own in the split ragged layout.
 template <int RG, bool FULL, int GROUP, int V, bool NT>
 __device__ __forceinline__ void apply_column(uint8_t* pbase, uint64_t cs, uint64_t x,
-                                             uint64_t rem, uint32_t d, uint32_t tab_stride,
-                                             cu32* in_idx, cu32* out_idx, cu32* tab,
+                                             uint64_t rem, uint32_t d, const PatView& p,
                                              uint64_t out_disp = 0) {
     static_assert(FULL || V == 1, "ragged columns are single");
     uint32_t acc[RG][V][4];
-#pragma unroll
-    for (int r = 0; r < RG; ++r)
-#pragma unroll
-        for (int c = 0; c < V; ++c) acc[r][c][0] = acc[r][c][1] = acc[r][c][2] = acc[r][c][3] = 0u;
+    acc_zero(acc);
     const uint64_t n = rem < 16 ? rem : 16;
 
 #pragma unroll 1
@@ -99,7 +137,7 @@ __device__ __forceinline__ void apply_column(uint8_t* pbase, uint64_t cs, uint64
 #pragma unroll
             for (int c = 0; c < V; ++c) v[u][c] = make_uint4(0u, 0u, 0u, 0u);
             if (j0 + u < d) {
-                const uint8_t* src = pbase + uint64_t(in_idx[j0 + u]) * cs + x;
+                const uint8_t* src = pbase + uint64_t(p.in_idx[j0 + u]) * cs + x;
 #pragma unroll
                 for (int c = 0; c < V; ++c) {
                     if (FULL) v[u][c] = ld16<NT>(src + c * kSpan);
@@ -108,43 +146,41 @@ __device__ __forceinline__ void apply_column(uint8_t* pbase, uint64_t cs, uint64
             }
         }
 #pragma unroll
-        for (int u = 0; u < GROUP; ++u) {
-            if (j0 + u < d) {
-                cu32* tj = tab + size_t(j0 + u) * tab_stride;
-#pragma unroll
-                for (int c = 0; c < V; ++c) {
-                    const Sel s0 = selectors(v[u][c].x), s1 = selectors(v[u][c].y),
-                              s2 = selectors(v[u][c].z), s3 = selectors(v[u][c].w);
-#pragma unroll
-                    for (int r = 0; r < RG; ++r) {
-                        cu32* t = tj + r * kTabWords;
-                        const uint32_t t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3], t4 = t[4];
-                        acc[r][c][0] ^= gmul(s0, t0, t1, t2, t3, t4);
-                        acc[r][c][1] ^= gmul(s1, t0, t1, t2, t3, t4);
-                        acc[r][c][2] ^= gmul(s2, t0, t1, t2, t3, t4);
-                        acc[r][c][3] ^= gmul(s3, t0, t1, t2, t3, t4);
-                    }
-                }
-            }
-        }
+        for (int u = 0; u < GROUP; ++u)
+            if (j0 + u < d) mul_input(acc, v[u], p.tab + size_t(j0 + u) * p.tab_stride);
     }
 #pragma unroll
-    for (int r = 0; r < RG; ++r) {
-        uint8_t* dst = pbase + (uint64_t(out_idx[r]) * cs + out_disp) + x;
-#pragma unroll
-        for (int c = 0; c < V; ++c) {
-            if (FULL)
-                st16<NT>(dst + c * kSpan,
-                         make_uint4(acc[r][c][0], acc[r][c][1], acc[r][c][2], acc[r][c][3]));
-            else
-                store_partial(dst, acc[r][c], n);
+    for (int r = 0; r < RG; ++r)
+        row_store<FULL, NT>(acc[r], pbase + (uint64_t(p.out_idx[r]) * cs + out_disp) + x, n);
+}
+
+// The column tile `tile` (tile_bytes) of one part, RG rows: full column steps (kSpan*V bytes of an
+// aligned layout, VEC) go to full(pbase, cs, x), x the lane's first column; the rest (ragged end,
+// unaligned layouts) takes the byte-granular single-column path.
+template <int RG, bool VEC, int V, typename Full>
+__device__ __forceinline__ void walk_tile(const ApplyParams& a, uint32_t part, uint32_t tile,
+                                          uint32_t tile_bytes, uint32_t d, const PatView& p,
+                                          Full&& full) {
+    uint8_t* pbase = a.base + uint64_t(part) * a.part_stride;
+    const uint64_t len = a.len;
+    const uint64_t cs = a.chunk_stride;
+    const uint64_t t0 = uint64_t(tile) * tile_bytes;
+    const uint64_t t1 = t0 + tile_bytes < len ? t0 + tile_bytes : len;
+#pragma unroll 1
+    for (uint64_t xb = t0; xb < t1; xb += kSpan * V) {  // block-uniform
+        const uint64_t x = xb + uint64_t(threadIdx.x) * 16u;
+        if (VEC && xb + kSpan * V <= len) {
+            full(pbase, cs, x);
+        } else {
+#pragma unroll 1
+            for (uint64_t xc = x; xc < t1 && xc < xb + kSpan * V; xc += kSpan)
+                apply_column<RG, false, 4, 1, false>(pbase, cs, xc, len - xc, d, p);
         }
     }
 }
 
 // One 16 KiB column tile of one part, rows [row0, row0 + RG) of its pattern record (n_out rows
-// in all).  Full column steps (kSpan*V bytes, aligned layout) take the V-wide path; the rest
-// (ragged end, unaligned layouts) the byte-granular single-column path.
+// in all).
 // VEC (16-byte aligned layout): two columns per lane per step, non-temporal loads and stores;
 // else one byte-granular column.  Both load 4 inputs before any is multiplied.  Measured on C2
 // encode (MI355X): non-temporal 10.79 ms, plain 11.20, one column 11.25, one column
@@ -155,29 +191,11 @@ __device__ __forceinline__ void apply_tile(const ApplyParams& a, cu32* pat, uint
                                            uint32_t tile_bytes) {
     constexpr int GROUP = 4, V = VEC ? 2 : 1;
     constexpr bool NT = VEC;
-    const uint32_t d = a.d;
-    cu32* in_idx = pat + 1;
-    cu32* out_idx = pat + 1 + d + row0;
-    cu32* tab = pat + 1 + d + n_out + size_t(row0) * kTabWords;
-    const uint32_t tab_stride = n_out * kTabWords;
-    uint8_t* pbase = a.base + uint64_t(part) * a.part_stride;
-    const uint64_t len = a.len;
-    const uint64_t cs = a.chunk_stride;
-    const uint64_t t0 = uint64_t(tile) * tile_bytes;
-    const uint64_t t1 = t0 + tile_bytes < len ? t0 + tile_bytes : len;
-#pragma unroll 1
-    for (uint64_t xb = t0; xb < t1; xb += kSpan * V) {  // block-uniform
-        const uint64_t x = xb + uint64_t(threadIdx.x) * 16u;
-        if (VEC && xb + kSpan * V <= len) {
-            apply_column<RG, true, GROUP, V, NT>(pbase, cs, x, len - x, d, tab_stride, in_idx,
-                                                 out_idx, tab);
-        } else {
-#pragma unroll 1
-            for (uint64_t xc = x; xc < t1 && xc < xb + kSpan * V; xc += kSpan)
-                apply_column<RG, false, 4, 1, false>(pbase, cs, xc, len - xc, d, tab_stride,
-                                                     in_idx, out_idx, tab);
-        }
-    }
+    const PatView p(pat, a.d, n_out, row0);
+    walk_tile<RG, VEC, V>(a, part, tile, tile_bytes, a.d, p,
+                          [&](uint8_t* pbase, uint64_t cs, uint64_t x) {
+        apply_column<RG, true, GROUP, V, NT>(pbase, cs, x, a.len - x, a.d, p);
+    });
 }
 
 // ---- compile-time d: the same multiply with every input's loads issued one group ahead ----
@@ -201,25 +219,8 @@ template <int D, int RG, int G, int J0, int V>
 __device__ __forceinline__ void vp_mul(uint32_t (&acc)[RG][V][4], uint4 (&v)[G][V], cu32* tab,
                                        uint32_t tab_stride) {
 #pragma unroll
-    for (int u = 0; u < G; ++u) {
-        if (J0 + u < D) {
-            cu32* tj = tab + size_t(J0 + u) * tab_stride;
-#pragma unroll
-            for (int c = 0; c < V; ++c) {
-                const Sel s0 = selectors(v[u][c].x), s1 = selectors(v[u][c].y),
-                          s2 = selectors(v[u][c].z), s3 = selectors(v[u][c].w);
-#pragma unroll
-                for (int r = 0; r < RG; ++r) {
-                    cu32* t = tj + r * kTabWords;
-                    const uint32_t t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3], t4 = t[4];
-                    acc[r][c][0] ^= gmul(s0, t0, t1, t2, t3, t4);
-                    acc[r][c][1] ^= gmul(s1, t0, t1, t2, t3, t4);
-                    acc[r][c][2] ^= gmul(s2, t0, t1, t2, t3, t4);
-                    acc[r][c][3] ^= gmul(s3, t0, t1, t2, t3, t4);
-                }
-            }
-        }
-    }
+    for (int u = 0; u < G; ++u)
+        if (J0 + u < D) mul_input(acc, v[u], tab + size_t(J0 + u) * tab_stride);
 }
 
 template <int D, int RG, int G, int J0, int V>
@@ -238,24 +239,15 @@ struct VpSteps {
 // apply_column<RG, true, ., V, true> for d == D.
 template <int D, int RG, int G, int V>
 __device__ __forceinline__ void vp_column(uint8_t* pbase, uint64_t cs, uint64_t x,
-                                          uint32_t tab_stride, cu32* in_idx, cu32* out_idx,
-                                          cu32* tab) {
+                                          const PatView& p) {
     uint32_t acc[RG][V][4];
+    acc_zero(acc);
+    uint4 v[2][G][V];
+    vp_load<D, G, 0, V>(v[0], pbase, cs, x, p.in_idx);
+    VpSteps<D, RG, G, 0, V>::run(acc, v, pbase, cs, x, p.in_idx, p.tab, p.tab_stride);
 #pragma unroll
     for (int r = 0; r < RG; ++r)
-#pragma unroll
-        for (int c = 0; c < V; ++c) acc[r][c][0] = acc[r][c][1] = acc[r][c][2] = acc[r][c][3] = 0u;
-    uint4 v[2][G][V];
-    vp_load<D, G, 0, V>(v[0], pbase, cs, x, in_idx);
-    VpSteps<D, RG, G, 0, V>::run(acc, v, pbase, cs, x, in_idx, tab, tab_stride);
-#pragma unroll
-    for (int r = 0; r < RG; ++r) {
-        uint8_t* dst = pbase + uint64_t(out_idx[r]) * cs + x;
-#pragma unroll
-        for (int c = 0; c < V; ++c)
-            st16<true>(dst + c * kSpan,
-                       make_uint4(acc[r][c][0], acc[r][c][1], acc[r][c][2], acc[r][c][3]));
-    }
+        row_store<true, true>(acc[r], pbase + uint64_t(p.out_idx[r]) * cs + x, 16);
 }
 
 // apply_tile with d == D (aligned layout, non-temporal, two columns per lane): full steps take
@@ -264,27 +256,11 @@ template <int D, int RG, int G>
 __device__ __forceinline__ void apply_tile_cd(const ApplyParams& a, cu32* pat, uint32_t part,
                                               uint32_t tile, uint32_t n_out, uint32_t tile_bytes) {
     constexpr int V = 2;
-    cu32* in_idx = pat + 1;
-    cu32* out_idx = pat + 1 + D;
-    cu32* tab = pat + 1 + D + n_out;
-    const uint32_t tab_stride = n_out * kTabWords;
-    uint8_t* pbase = a.base + uint64_t(part) * a.part_stride;
-    const uint64_t len = a.len;
-    const uint64_t cs = a.chunk_stride;
-    const uint64_t t0 = uint64_t(tile) * tile_bytes;
-    const uint64_t t1 = t0 + tile_bytes < len ? t0 + tile_bytes : len;
-#pragma unroll 1
-    for (uint64_t xb = t0; xb < t1; xb += kSpan * V) {  // block-uniform
-        const uint64_t x = xb + uint64_t(threadIdx.x) * 16u;
-        if (xb + kSpan * V <= len) {
-            vp_column<D, RG, G, V>(pbase, cs, x, tab_stride, in_idx, out_idx, tab);
-        } else {
-#pragma unroll 1
-            for (uint64_t xc = x; xc < t1 && xc < xb + kSpan * V; xc += kSpan)
-                apply_column<RG, false, 4, 1, false>(pbase, cs, xc, len - xc, D, tab_stride,
-                                                     in_idx, out_idx, tab);
-        }
-    }
+    const PatView p(pat, D, n_out);
+    walk_tile<RG, true, V>(a, part, tile, tile_bytes, D, p,
+                           [&](uint8_t* pbase, uint64_t cs, uint64_t x) {
+        vp_column<D, RG, G, V>(pbase, cs, x, p);
+    });
 }
 
 // XCD-aware block order.  The dispatcher deals a grid's blocks to the 8 XCDs round-robin (block
@@ -301,20 +277,28 @@ __device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t n) {
     return x * q + (x < r ? x : r) + i;
 }
 
+// This block's listed part and column tile of it (grid.x = listed parts * tiles_per_part).  xcd:
+// block order of xcd_block (else launch order).
+struct BlockTile {
+    uint32_t lp, tile;
+};
+__device__ __forceinline__ BlockTile block_tile(uint32_t tiles_per_part, bool xcd) {
+    const uint32_t bx = xcd ? xcd_block(blockIdx.x, gridDim.x) : blockIdx.x;
+    const uint32_t lp = bx / tiles_per_part;
+    return {lp, bx - lp * tiles_per_part};
+}
+
 // grid.x = n_parts * tiles_per_part (one 16 KiB column tile of one part per block),
-// grid.y = row groups of exactly RG output rows starting at row_base.  xcd: block order of
-// xcd_block (else launch order).
+// grid.y = row groups of exactly RG output rows starting at row_base.
 template <int RG, bool VEC>
 __global__ __launch_bounds__(kApplyThreads) void rs_apply_kernel(ApplyParams a,
                                                                  uint32_t tiles_per_part,
                                                                  uint32_t row_base, bool xcd,
                                                                  uint32_t tile_bytes) {
-    const uint32_t bx = xcd ? xcd_block(blockIdx.x, gridDim.x) : blockIdx.x;
-    const uint32_t lp = bx / tiles_per_part;
-    const uint32_t tile = bx - lp * tiles_per_part;
-    const uint32_t part = a.part_ids ? as_const(a.part_ids)[lp] : lp;
-    cu32* pat = as_const(a.pat) + (a.part_pat ? as_const(a.part_pat)[lp] : 0u);
-    apply_tile<RG, VEC>(a, pat, part, tile, a.n_rows, row_base + blockIdx.y * RG, tile_bytes);
+    const BlockTile b = block_tile(tiles_per_part, xcd);
+    const uint32_t part = a.part_ids ? as_const(a.part_ids)[b.lp] : b.lp;
+    cu32* pat = as_const(a.pat) + (a.part_pat ? as_const(a.part_pat)[b.lp] : 0u);
+    apply_tile<RG, VEC>(a, pat, part, b.tile, a.n_rows, row_base + blockIdx.y * RG, tile_bytes);
 }
 
 // Reconstruct with mixed erasure counts in ONE launch: every listed part's pattern carries its
@@ -330,7 +314,7 @@ __global__ __launch_bounds__(kApplyThreads) void rs_apply_kernel(ApplyParams a,
 constexpr int kCdGroup = 5;
 
 template <int RG, int MAXRG, typename F>
-__device__ __forceinline__ void rg_dispatch(uint32_t n, F&& f) {
+__host__ __device__ __forceinline__ void rg_dispatch(uint32_t n, F&& f) {
     if (n == RG) f(std::integral_constant<int, RG>{});
     else if constexpr (RG < MAXRG) rg_dispatch<RG + 1, MAXRG>(n, f);
     // n > MAXRG or 0: never listed -- the host routes n_out > 8 to row-group launches and checks
@@ -341,18 +325,16 @@ template <bool VEC, int MAXRG, int CD = 0>
 __global__ __launch_bounds__(kApplyThreads) void rs_apply_var_kernel(ApplyParams a,
                                                                      uint32_t tiles_per_part,
                                                                      bool xcd, uint32_t tile_bytes) {
-    const uint32_t bx = xcd ? xcd_block(blockIdx.x, gridDim.x) : blockIdx.x;
-    const uint32_t lp = bx / tiles_per_part;
-    const uint32_t tile = bx - lp * tiles_per_part;
-    const uint32_t part = as_const(a.part_ids)[lp];
-    cu32* pat = as_const(a.pat) + as_const(a.part_pat)[lp];
+    const BlockTile b = block_tile(tiles_per_part, xcd);
+    const uint32_t part = as_const(a.part_ids)[b.lp];
+    cu32* pat = as_const(a.pat) + as_const(a.part_pat)[b.lp];
     rg_dispatch<1, MAXRG>(pat[0], [&](auto rg) {
         constexpr int RG = decltype(rg)::value;
         if constexpr (CD > 0) {
             static_assert(VEC, "compile-time d: aligned build");
-            apply_tile_cd<CD, RG, kCdGroup>(a, pat, part, tile, RG, tile_bytes);
+            apply_tile_cd<CD, RG, kCdGroup>(a, pat, part, b.tile, RG, tile_bytes);
         } else {
-            apply_tile<RG, VEC>(a, pat, part, tile, RG, 0, tile_bytes);
+            apply_tile<RG, VEC>(a, pat, part, b.tile, RG, 0, tile_bytes);
         }
     });
 }
@@ -376,15 +358,21 @@ constexpr uint64_t kRaggedUnit = 4096;                  // bytes of one chunk's 
 constexpr uint64_t kRaggedStep = 64u * 16u;             // bytes per wave per column step
 constexpr uint32_t kRaggedWaves = kApplyThreads / 64;   // units per workgroup
 
-// The part that owns work unit u: pre[lo] <= u < pre[lo + 1] (wave-uniform scalar loads).
-__device__ __forceinline__ uint32_t ragged_find(cu32* pre, uint32_t n_parts, uint32_t u) {
-    uint32_t lo = 0, hi = n_parts;  // pre[lo] <= u < pre[hi]
+// Work unit u < a.total_units: the listed part that owns it, pre[lp] <= u < pre[lp + 1] (wave-
+// uniform scalar loads), and the unit's first column in it.
+struct WaveUnit {
+    uint32_t lp;
+    uint64_t x0;
+};
+__device__ __forceinline__ WaveUnit wave_unit(const RaggedParams& a, uint32_t u) {
+    cu32* pre = as_const(a.units);
+    uint32_t lo = 0, hi = a.n_parts;  // pre[lo] <= u < pre[hi]
     while (hi - lo > 1) {
         const uint32_t mid = lo + (hi - lo) / 2;
         if (pre[mid] <= u) lo = mid;
         else hi = mid;
     }
-    return lo;
+    return {lo, uint64_t(u - pre[lo]) * kRaggedUnit};
 }
 
 // One 4 KiB unit (columns from x0) of the part described by pm = {off lo, off hi, L lo, L hi}:
@@ -399,21 +387,16 @@ __device__ __forceinline__ void ragged_unit(uint8_t* base, cu32* pm, uint64_t x0
     const uint64_t disp = SPLIT ? uint64_t(pm[4]) | (uint64_t(pm[5]) << 32) : 0;
     const uint64_t cs = (len + 15) & ~uint64_t(15);
     uint8_t* pbase = base + off;
-    cu32* in_idx = pat + 1;
-    cu32* out_idx = pat + 1 + d + row0;
-    cu32* tab = pat + 1 + d + n_out + size_t(row0) * kTabWords;
-    const uint32_t tab_stride = n_out * kTabWords;
+    const PatView p(pat, d, n_out, row0);
     const uint64_t x1 = x0 + kRaggedUnit < len ? x0 + kRaggedUnit : len;
     const uint64_t lane_x = uint64_t(threadIdx.x & 63u) * 16u;
 #pragma unroll 1
     for (uint64_t xb = x0; xb < x1; xb += kRaggedStep) {  // wave-uniform
         const uint64_t x = xb + lane_x;
         if (x + 16 <= len) {  // every lane of a step that is not the part's last
-            apply_column<RG, true, 4, 1, false>(pbase, cs, x, len - x, d, tab_stride, in_idx,
-                                                out_idx, tab, disp);
+            apply_column<RG, true, 4, 1, false>(pbase, cs, x, len - x, d, p, disp);
         } else if (x < len) {
-            apply_column<RG, false, 4, 1, false>(pbase, cs, x, len - x, d, tab_stride, in_idx,
-                                                 out_idx, tab, disp);
+            apply_column<RG, false, 4, 1, false>(pbase, cs, x, len - x, d, p, disp);
         }
     }
 }
@@ -427,12 +410,10 @@ __global__ __launch_bounds__(kApplyThreads) void rs_apply_ragged_kernel(RaggedPa
     const uint32_t u = __builtin_amdgcn_readfirstlane(blockIdx.x * kRaggedWaves +
                                                       (threadIdx.x >> 6));
     if (u >= a.total_units) return;  // wave-uniform
-    cu32* pre = as_const(a.units);
-    const uint32_t lo = ragged_find(pre, a.n_parts, u);
-    cu32* pat = as_const(a.pat) + (a.part_pat ? as_const(a.part_pat)[lo] : 0u);
-    ragged_unit<RG, SPLIT>(a.base, as_const(a.parts) + size_t(lo) * (SPLIT ? 6 : 4),
-                           uint64_t(u - pre[lo]) * kRaggedUnit, a.d, pat, a.n_rows,
-                           row_base + blockIdx.y * RG);
+    const WaveUnit w = wave_unit(a, u);
+    cu32* pat = as_const(a.pat) + (a.part_pat ? as_const(a.part_pat)[w.lp] : 0u);
+    ragged_unit<RG, SPLIT>(a.base, as_const(a.parts) + size_t(w.lp) * (SPLIT ? 6 : 4), w.x0, a.d,
+                           pat, a.n_rows, row_base + blockIdx.y * RG);
 }
 
 // Ragged reconstruct: the listed parts are the ones that need a rebuild, each
@@ -451,14 +432,12 @@ __global__ __launch_bounds__(kApplyThreads) void rs_reconstruct_ragged_kernel(Ra
     const uint32_t u = __builtin_amdgcn_readfirstlane(blockIdx.x * kRaggedWaves +
                                                       (threadIdx.x >> 6));
     if (u >= a.total_units) return;  // wave-uniform
-    cu32* pre = as_const(a.units);
-    const uint32_t lo = ragged_find(pre, a.n_parts, u);
-    cu32* pat = as_const(a.pat) + as_const(a.part_pat)[lo];
-    cu32* pm = as_const(a.parts) + size_t(lo) * 4;
-    const uint64_t x0 = uint64_t(u - pre[lo]) * kRaggedUnit;
+    const WaveUnit w = wave_unit(a, u);
+    cu32* pat = as_const(a.pat) + as_const(a.part_pat)[w.lp];
+    cu32* pm = as_const(a.parts) + size_t(w.lp) * 4;
     rg_dispatch<1, MAXRG>(pat[0], [&](auto rg) {
         constexpr int RG = decltype(rg)::value;
-        ragged_unit<RG>(a.base, pm, x0, a.d, pat, RG, 0);
+        ragged_unit<RG>(a.base, pm, w.x0, a.d, pat, RG, 0);
     });
 }
 
@@ -606,31 +585,13 @@ template <int D, int P>
 __global__ __launch_bounds__(kApplyThreads) void rs_encode_bs_kernel(ApplyParams a,
                                                                      uint32_t tiles_per_part,
                                                                      bool xcd, uint32_t tile_bytes) {
-    const uint32_t bx = xcd ? xcd_block(blockIdx.x, gridDim.x) : blockIdx.x;
-    const uint32_t lp = bx / tiles_per_part;
-    const uint32_t tile = bx - lp * tiles_per_part;
-    const uint32_t part = a.part_ids ? as_const(a.part_ids)[lp] : lp;
-    cu32* pat = as_const(a.pat);
-    cu32* in_idx = pat + 1;
-    cu32* out_idx = pat + 1 + D;
-    cu32* tab = pat + 1 + D + P;
-    uint8_t* pbase = a.base + uint64_t(part) * a.part_stride;
-    const uint64_t len = a.len;
-    const uint64_t cs = a.chunk_stride;
-    const uint64_t t0 = uint64_t(tile) * tile_bytes;
-    const uint64_t t1 = t0 + tile_bytes < len ? t0 + tile_bytes : len;
-#pragma unroll 1
-    for (uint64_t xb = t0; xb < t1; xb += 2 * kSpan) {  // block-uniform
-        const uint64_t x = xb + uint64_t(threadIdx.x) * 16u;
-        if (xb + 2 * kSpan <= len) {
-            bs_column<D, P>(pbase, cs, x, in_idx, out_idx);
-        } else {
-#pragma unroll 1
-            for (uint64_t xc = x; xc < t1 && xc < xb + 2 * kSpan; xc += kSpan)
-                apply_column<P, false, 4, 1, false>(pbase, cs, xc, len - xc, D, P * kTabWords,
-                                                    in_idx, out_idx, tab);
-        }
-    }
+    const BlockTile b = block_tile(tiles_per_part, xcd);
+    const uint32_t part = a.part_ids ? as_const(a.part_ids)[b.lp] : b.lp;
+    const PatView p(as_const(a.pat), D, P);
+    walk_tile<P, true, 2>(a, part, b.tile, tile_bytes, D, p,
+                          [&](uint8_t* pbase, uint64_t cs, uint64_t x) {
+        bs_column<D, P>(pbase, cs, x, p.in_idx, p.out_idx);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -681,27 +642,20 @@ __global__ __launch_bounds__(256) void fill_kernel(FillParams a, bool aligned8) 
 // what the runtime reports (hipDeviceAttributeMaxSharedMemoryPerMultiprocessor); 0 when
 // unknown, which turns the residency caps below off rather than mis-sizing them.
 uint32_t lds_per_cu() {
-    static std::atomic<uint32_t> cache[64];  // 0 = not read yet, 1 = unknown
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    uint32_t v = cache[dev].load(std::memory_order_relaxed);
-    if (!v) {
+    static std::atomic<uint32_t> cache[kMaxDevices];  // 0 = not read yet, 1 = unknown
+    const uint32_t v = per_device(cache, 1u, [](int dev) {
         hipDeviceProp_t prop;
         int attr = 0;
+        uint32_t lds = 1;
         if (hipGetDeviceProperties(&prop, dev) == hipSuccess &&
             std::strncmp(prop.gcnArchName, "gfx950", 6) == 0)
-            v = 160u * 1024u;
+            lds = kCuLdsBytes;
         else if (hipDeviceGetAttribute(&attr, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor,
                                        dev) == hipSuccess && attr > 0)
-            v = uint32_t(attr);
-        else
-            v = 1;
-        (void)hipGetLastError();
-        cache[dev].store(v, std::memory_order_relaxed);
-    }
+            lds = uint32_t(attr);
+        clear_stale_error();
+        return lds;
+    });
     return v == 1 ? 0 : v;
 }
 
@@ -773,40 +727,58 @@ hipError_t for_part_ranges(const ApplyParams& a, uint64_t max_parts, Fn fn) {
     return hipSuccess;
 }
 
-template <int RG>
-hipError_t launch_rg(const ApplyParams& a, uint32_t row_base, uint32_t groups, bool vec16,
-                     hipStream_t s) {
-    const uint64_t tb = kApplyTile;
+// One launch per part range of `kern` over tiles of tb bytes: grid.x = listed parts * tiles,
+// grid.y = groups, at most `cap` blocks per CU (apply_lds); the kernel's arguments are the range's
+// ApplyParams, the tiles per part, `extra`, the XCD order and tb.
+template <typename K, typename... Extra>
+hipError_t launch_tiled(const ApplyParams& a, K kern, uint64_t tb, uint32_t groups, int cap,
+                        hipStream_t s, Extra... extra) {
     const uint64_t tiles = (a.len + tb - 1) / tb;
     const uint64_t max_blocks = max_apply_blocks();
     if (tiles > max_blocks) return hipErrorInvalidValue;
     return for_part_ranges(a, max_blocks / tiles, [&](const ApplyParams& b) {
         const dim3 grid(uint32_t(b.n_parts * tiles), groups);
-        // layouts that are not 16-byte aligned take the byte-granular build
-        auto* kern = vec16 ? &rs_apply_kernel<RG, true> : &rs_apply_kernel<RG, false>;
-        // 1-3 rows: 3 blocks per CU (RS(2,1) / RS(4,2) / RS(8,2) / RS(6,3) encode 1-2 %
-        // faster than by registers, profiles/r3_vperm_shapes_ab/); 4+ rows: no gain
-        const uint32_t lds = apply_lds(b.lds_reserve, RG <= 3 ? 3 : 0, uint64_t(grid.x) * groups);
+        const uint32_t lds = apply_lds(b.lds_reserve, cap, uint64_t(grid.x) * groups);
         if (!allow_lds(kern, lds)) return hipErrorInvalidValue;
         clear_stale_error();
-        hipLaunchKernelGGL(kern, grid, dim3(kApplyThreads), lds, s, b, uint32_t(tiles), row_base,
+        hipLaunchKernelGGL(kern, grid, dim3(kApplyThreads), lds, s, b, uint32_t(tiles), extra...,
                            /*xcd=*/true, uint32_t(tb));
         return hipGetLastError();
     });
 }
 
-hipError_t launch_rows(const ApplyParams& a, uint32_t rg, uint32_t row_base, uint32_t groups,
-                       bool vec16, hipStream_t s) {
-    switch (rg) {
-        case 1: return launch_rg<1>(a, row_base, groups, vec16, s);
-        case 2: return launch_rg<2>(a, row_base, groups, vec16, s);
-        case 3: return launch_rg<3>(a, row_base, groups, vec16, s);
-        case 4: return launch_rg<4>(a, row_base, groups, vec16, s);
-        case 5: return launch_rg<5>(a, row_base, groups, vec16, s);
-        case 6: return launch_rg<6>(a, row_base, groups, vec16, s);
-        case 7: return launch_rg<7>(a, row_base, groups, vec16, s);
-        default: return launch_rg<8>(a, row_base, groups, vec16, s);
-    }
+template <int RG>
+hipError_t launch_rg(const ApplyParams& a, uint32_t row_base, uint32_t groups, bool vec16,
+                     hipStream_t s) {
+    // layouts that are not 16-byte aligned take the byte-granular build
+    auto* kern = vec16 ? &rs_apply_kernel<RG, true> : &rs_apply_kernel<RG, false>;
+    // 1-3 rows: 3 blocks per CU (RS(2,1) / RS(4,2) / RS(8,2) / RS(6,3) encode 1-2 %
+    // faster than by registers, profiles/r3_vperm_shapes_ab/); 4+ rows: no gain
+    return launch_tiled(a, kern, kApplyTile, groups, RG <= 3 ? 3 : 0, s, row_base);
+}
+
+// Rows are processed in groups of kMaxApplyRows (8) plus one remainder group, so every kernel
+// instance handles exactly RG rows (no per-row predicate in the inner loop):
+// fn(std::integral_constant<int, RG>, row_base, groups) per launch.
+template <typename Fn>
+hipError_t for_row_groups(uint32_t n_rows, Fn fn) {
+    const uint32_t full = n_rows / kMaxApplyRows, rem = n_rows % kMaxApplyRows;
+    hipError_t e = hipSuccess;
+    if (full) e = fn(std::integral_constant<int, int(kMaxApplyRows)>{}, 0u, full);
+    if (rem && e == hipSuccess)
+        rg_dispatch<1, kMaxApplyRows - 1>(rem, [&](auto rg) {
+            e = fn(rg, full * kMaxApplyRows, 1u);
+        });
+    return e;
+}
+
+// The row class (MAXRG: 2, 4 or 8) of a launch whose widest record has `rows` rows (0: unknown,
+// the 8-row class): fn(std::integral_constant<int, MAXRG>).
+template <typename Fn>
+hipError_t with_row_class(uint32_t rows, Fn fn) {
+    if (rows && rows <= 2) return fn(std::integral_constant<int, 2>{});
+    if (rows && rows <= 4) return fn(std::integral_constant<int, 4>{});
+    return fn(std::integral_constant<int, 8>{});
 }
 
 // CEC_APPLY_BS (test knob; unset = 1): 0 sends the compiled shapes' encodes to
@@ -815,23 +787,10 @@ bool apply_bs() { return knobs().apply_bs; }
 
 template <int D, int P>
 hipError_t launch_bs(const ApplyParams& a, hipStream_t s) {
-    const uint64_t tb = kBsTile;
-    const uint64_t tiles = (a.len + tb - 1) / tb;
-    const uint64_t max_blocks = max_apply_blocks();
-    if (tiles > max_blocks) return hipErrorInvalidValue;
-    return for_part_ranges(a, max_blocks / tiles, [&](const ApplyParams& b) {
-        auto* kern = &rs_encode_bs_kernel<D, P>;
-        const uint64_t n_blocks = b.n_parts * tiles;
-        // measured per shape: RS(10,4) 2 blocks per CU, RS(3,2) 3 (6.71 vs 6.92-7.23 ms for 8 192
-        // parts x 1 MiB, profiles/r3_c1enc_ab/), RS(20,8) its register-bound 3
-        const int cap = D == 10 && P == 4 ? 2 : D == 3 && P == 2 ? 3 : 0;
-        const uint32_t lds = apply_lds(b.lds_reserve, cap, n_blocks);
-        if (!allow_lds(kern, lds)) return hipErrorInvalidValue;
-        clear_stale_error();
-        hipLaunchKernelGGL(kern, dim3(uint32_t(n_blocks)), dim3(kApplyThreads), lds, s, b,
-                           uint32_t(tiles), /*xcd=*/true, uint32_t(tb));
-        return hipGetLastError();
-    });
+    // measured per shape: RS(10,4) 2 blocks per CU, RS(3,2) 3 (6.71 vs 6.92-7.23 ms for 8 192
+    // parts x 1 MiB, profiles/r3_c1enc_ab/), RS(20,8) its register-bound 3
+    const int cap = D == 10 && P == 4 ? 2 : D == 3 && P == 2 ? 3 : 0;
+    return launch_tiled(a, &rs_encode_bs_kernel<D, P>, kBsTile, 1, cap, s);
 }
 
 // The compiled bit-sliced shapes: the reference's example clusters (RS(3,2), examples/*.yaml)
@@ -872,17 +831,11 @@ hipError_t launch_rs_encode(const ApplyParams& a, bool vec16, hipStream_t s) {
     return launch_rs_apply(a, vec16, s);
 }
 
-// Rows are processed in groups of kMaxApplyRows (8) plus one remainder group, so every kernel
-// instance handles exactly RG rows (no per-row predicate in the inner loop).
 hipError_t launch_rs_apply(const ApplyParams& a, bool vec16, hipStream_t s) {
     if (a.n_parts == 0 || a.n_rows == 0 || a.len == 0) return hipSuccess;
-    const uint32_t full = a.n_rows / kMaxApplyRows, rem = a.n_rows % kMaxApplyRows;
-    if (full) {
-        hipError_t e = launch_rows(a, kMaxApplyRows, 0, full, vec16, s);
-        if (e != hipSuccess) return e;
-    }
-    if (rem) return launch_rows(a, rem, full * kMaxApplyRows, 1, vec16, s);
-    return hipSuccess;
+    return for_row_groups(a.n_rows, [&](auto rg, uint32_t row_base, uint32_t groups) {
+        return launch_rg<decltype(rg)::value>(a, row_base, groups, vec16, s);
+    });
 }
 
 // Listed parts (part_ids / part_pat) whose patterns have 1..kMaxApplyRows rows each: one launch.
@@ -891,38 +844,18 @@ hipError_t launch_rs_apply_var(const ApplyParams& a, bool vec16, hipStream_t s) 
     if (a.n_parts == 0 || a.len == 0) return hipSuccess;
     if (!a.part_ids || !a.part_pat) return hipErrorInvalidValue;
     if (a.n_rows > kMaxApplyRows) return hipErrorInvalidValue;
-    const uint64_t tb = kBsTile;  // 8 KiB with the caps (see kBsTile)
-    const uint64_t tiles = (a.len + tb - 1) / tb;
-    const uint64_t max_blocks = max_apply_blocks();
-    if (tiles > max_blocks) return hipErrorInvalidValue;
     // not under a caller's LDS reservation: the read path's decode beside the SHA-256
     // verification (capi.cpp kDecodeLds) loses with it (c3r 44.0-44.5 vs 42.6-42.8 ms,
     // profiles/r3_c3r_ab/): its loads run ahead into the SHA chains' bandwidth
     const bool cd = a.lds_reserve == 0;
-    const uint32_t rows = a.n_rows ? a.n_rows : kMaxApplyRows;
-    const int cls = rows <= 2 ? 2 : rows <= 4 ? 4 : 8;  // MAXRG
-    return for_part_ranges(a, max_blocks / tiles, [&](const ApplyParams& b) {
-        const dim3 grid(uint32_t(b.n_parts * tiles));
-        // 2-row class: 2 blocks per CU, 4-row class: 3, 8-row: by registers (3)
-        const uint32_t lds = apply_lds(b.lds_reserve, cls == 2 ? 2 : cls == 4 ? 3 : 0, grid.x);
-        auto go = [&](auto* kern) {
-            if (!allow_lds(kern, lds)) return hipErrorInvalidValue;
-            clear_stale_error();
-            hipLaunchKernelGGL(kern, grid, dim3(kApplyThreads), lds, s, b,
-                               uint32_t(tiles), /*xcd=*/true, uint32_t(tb));
-            return hipGetLastError();
-        };
-        auto by_class = [&](auto k2, auto k4, auto k8) {
-            return cls == 2 ? go(k2) : cls == 4 ? go(k4) : go(k8);
-        };
-        if (vec16 && b.d == 10 && cd)
-            return by_class(&rs_apply_var_kernel<true, 2, 10>, &rs_apply_var_kernel<true, 4, 10>,
-                            &rs_apply_var_kernel<true, 8, 10>);
-        if (vec16)
-            return by_class(&rs_apply_var_kernel<true, 2>, &rs_apply_var_kernel<true, 4>,
-                            &rs_apply_var_kernel<true, 8>);
-        return by_class(&rs_apply_var_kernel<false, 2>, &rs_apply_var_kernel<false, 4>,
-                        &rs_apply_var_kernel<false, 8>);
+    return with_row_class(a.n_rows, [&](auto cls) {
+        constexpr int MAXRG = decltype(cls)::value;
+        auto* kern = !vec16             ? &rs_apply_var_kernel<false, MAXRG>
+                     : a.d == 10 && cd ? &rs_apply_var_kernel<true, MAXRG, 10>
+                                       : &rs_apply_var_kernel<true, MAXRG>;
+        // 8 KiB tiles with the caps (see kBsTile); 2-row class: 2 blocks per CU, 4-row class: 3,
+        // 8-row: by registers (3)
+        return launch_tiled(a, kern, kBsTile, 1, MAXRG == 2 ? 2 : MAXRG == 4 ? 3 : 0, s);
     });
 }
 
@@ -946,33 +879,15 @@ hipError_t launch_ragged_rg(const RaggedParams& a, uint32_t row_base, uint32_t g
     return hipGetLastError();
 }
 
-hipError_t launch_ragged_rows(const RaggedParams& a, uint32_t rg, uint32_t row_base,
-                              uint32_t groups, hipStream_t s) {
-    switch (rg) {
-        case 1: return launch_ragged_rg<1>(a, row_base, groups, s);
-        case 2: return launch_ragged_rg<2>(a, row_base, groups, s);
-        case 3: return launch_ragged_rg<3>(a, row_base, groups, s);
-        case 4: return launch_ragged_rg<4>(a, row_base, groups, s);
-        case 5: return launch_ragged_rg<5>(a, row_base, groups, s);
-        case 6: return launch_ragged_rg<6>(a, row_base, groups, s);
-        case 7: return launch_ragged_rg<7>(a, row_base, groups, s);
-        default: return launch_ragged_rg<8>(a, row_base, groups, s);
-    }
-}
-
 }  // namespace
 
 // Row groups as launch_rs_apply: up to kMaxApplyRows rows (every compiled shape) is one launch.
 hipError_t launch_rs_encode_ragged(const RaggedParams& a, hipStream_t s) {
     if (a.n_parts == 0 || a.n_rows == 0 || a.total_units == 0) return hipSuccess;
     if (a.total_units > ragged_max_units()) return hipErrorInvalidValue;
-    const uint32_t full = a.n_rows / kMaxApplyRows, rem = a.n_rows % kMaxApplyRows;
-    if (full) {
-        const hipError_t e = launch_ragged_rows(a, kMaxApplyRows, 0, full, s);
-        if (e != hipSuccess) return e;
-    }
-    if (rem) return launch_ragged_rows(a, rem, full * kMaxApplyRows, 1, s);
-    return hipSuccess;
+    return for_row_groups(a.n_rows, [&](auto rg, uint32_t row_base, uint32_t groups) {
+        return launch_ragged_rg<decltype(rg)::value>(a, row_base, groups, s);
+    });
 }
 
 // Listed parts with a record each of 1..kMaxApplyRows rows: one launch, in the row class of
@@ -981,16 +896,13 @@ hipError_t launch_rs_reconstruct_ragged(const RaggedParams& a, hipStream_t s) {
     if (a.n_parts == 0 || a.total_units == 0) return hipSuccess;
     if (!a.part_pat || a.split || a.n_rows > kMaxApplyRows) return hipErrorInvalidValue;
     if (a.total_units > ragged_max_units()) return hipErrorInvalidValue;
-    const uint32_t rows = a.n_rows ? a.n_rows : kMaxApplyRows;
     const dim3 grid((a.total_units + kRaggedWaves - 1) / kRaggedWaves);
     clear_stale_error();
-    if (rows <= 2)
-        hipLaunchKernelGGL(rs_reconstruct_ragged_kernel<2>, grid, dim3(kApplyThreads), 0, s, a);
-    else if (rows <= 4)
-        hipLaunchKernelGGL(rs_reconstruct_ragged_kernel<4>, grid, dim3(kApplyThreads), 0, s, a);
-    else
-        hipLaunchKernelGGL(rs_reconstruct_ragged_kernel<8>, grid, dim3(kApplyThreads), 0, s, a);
-    return hipGetLastError();
+    return with_row_class(a.n_rows, [&](auto cls) {
+        hipLaunchKernelGGL(rs_reconstruct_ragged_kernel<decltype(cls)::value>, grid,
+                           dim3(kApplyThreads), 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_fill(const FillParams& a, hipStream_t s) {

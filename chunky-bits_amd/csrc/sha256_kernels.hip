@@ -284,19 +284,14 @@ hipError_t launch_split(const ShaParams& a, bool vec16, hipStream_t s) {
 
 }  // namespace
 
-// CUs of the current device (cached per device ordinal).
+// CUs of the current device (cached per device ordinal); 256 when unknown.
 int device_cus() {
-    static int cache[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cache[dev]) {
+    static std::atomic<uint32_t> cache[kMaxDevices];
+    return int(per_device(cache, 256u, [](int dev) {
         int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            n <= 0)
-            n = 256;
-        cache[dev] = n;
-    }
-    return cache[dev];
+        return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) ==
+                           hipSuccess && n > 0 ? uint32_t(n) : 256u;
+    }));
 }
 
 // Chunks up to which a launch takes the split kernel: its 2 waves per 64 chunks then fill at

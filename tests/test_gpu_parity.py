@@ -498,21 +498,32 @@ def test_sha256_batch_subrange(variant, knob_env):
             assert hd[k, c].tobytes() == hashlib.sha256(host[k, 2 + c, :L].tobytes()).digest()
 
 
+# The compile-time-d reconstruct (rs_kernels.hip apply_tile_cd: RS(10,4), aligned strides) at
+# chunk lengths that end inside an 8 KiB step: one 16-byte column past a tile, a last step 16 bytes
+# short, a 5-byte last column; 6 parts, widest pattern in the 2-row and in the 4-row class.
+_CD_TAILS = [(10, 4, L, 6, m) for L in (8192 + 16, 3 * 8192 - 16, 16384 + 5) for m in (2, 4)]
+
+
 @pytest.mark.parametrize("data_only", [False, True])
-@pytest.mark.parametrize("d,p,L", [(10, 4, 16384), (3, 2, 683), (20, 8, 4096 + 5),
-                                   (10, 4, 12368),   # partial last 8 KiB step (2-column path)
-                                   (10, 6, 3 * 8192 + 16),  # compile-time d=10, 8-row class
-                                   (6, 10, 1024)])   # up to 10 rows: shared + row-group launches
-def test_reconstruct_batch_random_patterns(d, p, L, data_only):
-    n_parts, t = 96, d + p
-    buf, batch = _device_parts(n_parts, t, L, None, seed=L + d)
+@pytest.mark.parametrize("d,p,L,n_parts,max_miss", [
+    (10, 4, 16384, 96, 4), (3, 2, 683, 96, 2), (20, 8, 4096 + 5, 96, 8),
+    (10, 4, 12368, 96, 4),   # partial last 8 KiB step (2-column path)
+    (10, 6, 3 * 8192 + 16, 96, 6),  # compile-time d=10, 8-row class
+    (6, 10, 1024, 96, 10),   # up to 10 rows: shared + row-group launches
+] + _CD_TAILS, ids=["10-4-16384", "3-2-683", "20-8-4101", "10-4-12368", "10-6-24592", "6-10-1024"] +
+    ["10-4-%d-%dparts-miss%d" % c[2:] for c in _CD_TAILS])
+def test_reconstruct_batch_random_patterns(d, p, L, n_parts, max_miss, data_only):
+    t = d + p
+    # the added cases keep 16-byte aligned strides (the aligned builds) whatever L
+    cstride = (L + 15) & ~15 if n_parts == 6 else None
+    buf, batch = _device_parts(n_parts, t, L, cstride, seed=L + d)
     rs = ce.ReedSolomon(d, p)
     ce.encode_batch(rs, batch)
     ref = buf.clone()
     rng = np.random.default_rng(d * 7 + L)
     present = np.ones((n_parts, t), dtype=np.uint8)
     for k in range(n_parts):
-        n_miss = k % (p + 1)  # includes parts with nothing missing
+        n_miss = k % (max_miss + 1)  # includes parts with nothing missing
         present[k, rng.choice(t, n_miss, replace=False)] = 0
     # erase (zero) the missing chunks
     mask = torch.from_numpy(present).to(DEV).bool()
@@ -526,14 +537,15 @@ def test_reconstruct_batch_random_patterns(d, p, L, data_only):
                 assert np.array_equal(got[k, i], want[k, i]), (k, i)
             else:  # data_only leaves missing parity untouched (None in the crate)
                 assert not got[k, i].any()
-    # cross-check a few parts against the oracle's reconstruct on the erased inputs
-    for k in range(0, n_parts, 17):
-        shards = [want[k, i].tobytes() if present[k, i] else None for i in range(t)]
+    # cross-check a few parts (every part of a small batch) against the oracle's reconstruct on
+    # the erased inputs
+    for k in range(0, n_parts, 17 if n_parts > 17 else 1):
+        shards = [want[k, i, :L].tobytes() if present[k, i] else None for i in range(t)]
         st, out = oracle.reconstruct(d, p, shards, data_only=data_only)
         assert st == 0
         for i in range(t):
             if out[i] is not None:
-                assert out[i].tobytes() == got[k, i].tobytes()
+                assert out[i].tobytes() == got[k, i, :L].tobytes()
 
 
 @pytest.mark.parametrize("d,p,max_miss", [(10, 4, 1), (10, 4, 2), (10, 4, 3), (20, 8, 5),
