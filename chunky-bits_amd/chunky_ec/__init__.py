@@ -155,6 +155,8 @@ _sig("cec_verify_ragged", [ctypes.c_size_t, _vp, _szp, _szp, ctypes.c_size_t, _u
 _sig("cec_parts_verify", [ctypes.POINTER(_u8p), _szp, ctypes.c_size_t, _u8p, _u8p])
 _sig("cec_coalesce_stats", [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
      None)
+_sig("cec_ragged_stats", [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
+     None)
 _sig("cec_encode_batch", [_vp, ctypes.POINTER(PartBatchStruct), _vp])
 _sig("cec_encode_hash_batch", [_vp, ctypes.POINTER(PartBatchStruct), _vp, _vp])
 _sig("cec_sha256_batch", [ctypes.POINTER(PartBatchStruct), ctypes.c_size_t, ctypes.c_size_t,
@@ -880,6 +882,14 @@ def coalesce_stats():
     calls, launches = ctypes.c_uint64(0), ctypes.c_uint64(0)
     _lib.cec_coalesce_stats(ctypes.byref(calls), ctypes.byref(launches))
     return calls.value, launches.value
+
+
+def ragged_stats():
+    """(fused, two_pass): ragged encode launch sequences queued by each path since load
+    (cec_ragged_stats)."""
+    fused, two_pass = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _lib.cec_ragged_stats(ctypes.byref(fused), ctypes.byref(two_pass))
+    return fused.value, two_pass.value
 
 
 def synth_byte(seed: int, part: int, chunk: int, offset: int) -> int:

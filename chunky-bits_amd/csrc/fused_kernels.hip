@@ -156,6 +156,44 @@ __device__ __forceinline__ void ring_tail_words(const uint8_t* tp, uint32_t rem,
     }
 }
 
+// One part as a thread sees it: its first data chunk, chunk length and stride, where an output
+// row's chunk lies relative to `pb + (d + r) * cs` (split layout), and its index in the caller's
+// order (where its digests go).
+struct PartView {
+    uint8_t* pb;
+    uint64_t L, cs, disp;
+    uint32_t k;
+};
+
+// Part q of the launch (q < n_parts).  Uniform batch: part q itself, the batch's len and stride.
+// Ragged: part order[q], from its record {off lo, off hi, L lo, L hi[, disp lo, disp hi]}.
+template <bool RG, typename Params>
+__device__ __forceinline__ PartView part_view(const Params& a, uint32_t q) {
+    if constexpr (!RG) {
+        return {a.base + uint64_t(q) * a.part_stride, a.len, a.chunk_stride, 0u, q};
+    } else {
+        const uint32_t k = a.order[q];
+        const uint32_t* pm = a.parts + size_t(k) * (a.split ? 6u : 4u);
+        const uint64_t off = uint64_t(pm[0]) | (uint64_t(pm[1]) << 32);
+        const uint64_t L = uint64_t(pm[2]) | (uint64_t(pm[3]) << 32);
+        const uint64_t disp = a.split ? uint64_t(pm[4]) | (uint64_t(pm[5]) << 32) : 0u;
+        return {a.base + off, L, (L + 15u) & ~uint64_t(15), disp, k};
+    }
+}
+
+// The longest chunk length among the workgroup's parts, as wave-uniform words (scalar loads):
+// the batch's len, or the L of the ragged group's first part.
+template <bool RG, typename Params>
+__device__ __forceinline__ uint64_t group_len(const Params& a, uint32_t part0) {
+    if constexpr (!RG) {
+        return a.len;
+    } else {
+        const uint32_t k = as_const(a.order)[part0];
+        cu32* pm = as_const(a.parts) + size_t(k) * (a.split ? 6u : 4u);
+        return uint64_t(pm[2]) | (uint64_t(pm[3]) << 32);
+    }
+}
+
 // PMAX: parity rows (exact when a.p == PMAX; rows r >= a.p skipped by uniform guards).
 // Up to kMaxFusedData data inputs are held in registers per encoder thread (next step's
 // prefetch).  Aligned (16-byte) layouts only; others use the separate kernels.
@@ -170,9 +208,18 @@ __device__ __forceinline__ void ring_tail_words(const uint8_t* tp, uint32_t rem,
 // G*STEP/CW <= 128), while encoder waves 8-10 only build the product tables and join the
 // barriers.  The SIMDs with two SHA waves then carry no encoder work at all.  The ENC3 build
 // keeps the ring big-endian (lds_store_words).
-template <int PMAX, int STEP, int DT, int SW = 4, bool ENC3 = false>
-__global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams a) {
+//
+// RG: the ragged build (encode_hash_ragged_kernel, FusedRaggedParams).  Workgroup w takes the G
+// parts order[w*G ..] (sorted by chunk length, longest first), each with its own {off, L} and, in
+// the split layout, its own output displacement.  Every thread works with its own part's L: an
+// encoder task skips the steps behind its part's last column, a SHA lane takes its tail blocks at
+// its own last step and afterwards only joins the barriers.  The step count, and with it the
+// number of barriers every wave passes, comes from the group's first (longest) part, read as
+// wave-uniform words before the waves split into encoders and SHA lanes.
+template <int PMAX, int STEP, int DT, int SW, bool ENC3, bool RG, typename Params>
+__device__ __forceinline__ void encode_hash_body(const Params& a) {
     static_assert(!ENC3 || SW == 8, "ENC3 needs the two-SHA-wave build");
+    static_assert(!RG || (DT == 0 && SW == 4 && !ENC3), "the ragged build is the generic one");
     constexpr bool BE = ENC3;
     constexpr uint32_t kSha = 64u * SW;
     constexpr int DMAX = DT ? DT : kMaxFusedData;
@@ -198,9 +245,9 @@ __global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams 
     const uint32_t rows = G * t;
     const uint32_t part0 = blockIdx.x * G;
     const uint32_t g_here = min(G, a.n_parts - part0);
-    const uint64_t L = a.len;
-    const uint64_t cs = a.chunk_stride;
-    const uint32_t n_steps = uint32_t((L + STEP - 1) / STEP);
+    // The workgroup's step count, one barrier each: from wave-uniform words, by this one
+    // expression, before the waves split (a ragged thread's own L only bounds its work).
+    const uint32_t n_steps = uint32_t((group_len<RG>(a, part0) + STEP - 1) / STEP);
 
     const uint32_t wave = threadIdx.x >> 6;
     if (threadIdx.x >= kSha || (ENC3 && wave == 7u)) {
@@ -211,7 +258,9 @@ __global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams 
         // HBM, then issue the next step's d loads (all in flight at once) before the barrier.
         // Two SHA waves saturate their SIMD: without priority the encoders would get no issue
         // slots until the SHA waves park at the step barrier, which then waits for them.
-        if (a.enc_prio == 1u) __builtin_amdgcn_s_setprio(1);
+        if constexpr (!RG) {
+            if (a.enc_prio == 1u) __builtin_amdgcn_s_setprio(1);
+        }
         cu32* pat = as_const(a.pat);
         cu32* tab = PatView(pat, d, P).tab;  // input j, row r at (j*P + r) * 5
         const uint32_t et = threadIdx.x - kSha;  // table builders: et < kEncThreads
@@ -224,7 +273,13 @@ __global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams 
                               : G * kCols < kEncThreads ? (et & 63u) * 4u + (et >> 6) : et;
         const bool has_task = task < g_here * kCols;
         const uint32_t g = task / kCols, col = task - g * kCols;
-        uint8_t* pb = a.base + uint64_t(part0 + g) * a.part_stride;
+        // (a ragged thread without a task reads the group's first part: a record that exists)
+        const PartView pt = part_view<RG>(a, part0 + (RG && !has_task ? 0u : g));
+        uint8_t* const pb = pt.pb;
+        // where output row r's chunk lies, less (d + r) * cs
+        uint8_t* const ob = RG ? reinterpret_cast<uint8_t*>(reinterpret_cast<uint64_t>(pb) + pt.disp)
+                               : pb;
+        const uint64_t L = pt.L, cs = pt.cs;
         uint32_t v[DMAX][NW];
         auto load_step = [&](uint32_t s) {
             const uint64_t x = uint64_t(s) * STEP + col * CW;
@@ -346,7 +401,7 @@ __global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams 
             for (int r = 0; r < PMAX; ++r) {
                 if (uint32_t(r) >= P) break;
                 lds_store_words<NW, BE>(lrow + size_t(d + r) * kRow, out[r]);
-                store_words<NW, RAGGED>(pb + uint64_t(d + r) * cs + x, n, out[r]);
+                store_words<NW, RAGGED>(ob + uint64_t(d + r) * cs + x, n, out[r]);
             }
         };
         __syncthreads();  // tables built (the SHA waves join this barrier too)
@@ -364,12 +419,19 @@ __global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams 
         }
     } else {
         // ------------------------------ SHA lanes ------------------------------
-        if (a.enc_prio == 2u) __builtin_amdgcn_s_setprio(1);  // A/B: SHA waves first
+        if constexpr (!RG) {
+            if (a.enc_prio == 2u) __builtin_amdgcn_s_setprio(1);  // A/B: SHA waves first
+        }
         const uint32_t lane = threadIdx.x;
         const bool valid = lane < g_here * t;
         uint32_t st[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) st[i] = kH0[i];
+        // The lane's own chunk length and the step that holds its last bytes (uniform batch: the
+        // batch's).  A ragged lane without a chunk reads the group's first part and hashes nothing.
+        const PartView pt = part_view<RG>(a, RG ? part0 + (valid ? lane / t : 0u) : part0);
+        const uint64_t L = pt.L;
+        const uint32_t my_steps = RG ? uint32_t((L + STEP - 1) / STEP) : n_steps;
         const uint64_t nfull = L >> 6;
         uint32_t w[16];
         __syncthreads();  // encoders' product tables built
@@ -388,7 +450,7 @@ __global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams 
                     else block_words(qq, w);
                     compress(st, w);
                 }
-                if (s + 1 == n_steps) {
+                if (s + 1 == my_steps) {
                     const uint32_t rem = uint32_t(L - 64 * nfull);
                     const uint32_t tb = tail_blocks(rem);
                     const uint8_t* tp = row + (64 * nfull - uint64_t(s) * STEP);
@@ -404,25 +466,52 @@ __global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams 
         }
         if (valid) {
             const uint32_t g = lane / t, i = lane - g * t;
-            store_digest(a.digests + (uint64_t(part0 + g) * t + i) * 32u, st);
+            store_digest(a.digests + (uint64_t(RG ? pt.k : part0 + g) * t + i) * 32u, st);
         }
     }
 }
 
 template <int PMAX, int STEP, int DT, int SW = 4, bool ENC3 = false>
-hipError_t launch_p(const FusedParams& a, hipStream_t s) {
+__global__ __launch_bounds__(64 * (SW + 4)) void encode_hash_kernel(FusedParams a) {
+    encode_hash_body<PMAX, STEP, DT, SW, ENC3, false>(a);
+}
+
+// The ragged build: the generic-d body (d <= kMaxFusedData, 16-byte columns with the byte path
+// for a chunk's last 1-15 bytes), one SHA wave per SIMD.
+template <int PMAX, int STEP>
+__global__ __launch_bounds__(64 * 8) void encode_hash_ragged_kernel(FusedRaggedParams a) {
+    encode_hash_body<PMAX, STEP, 0, 4, false, true>(a);
+}
+
+// One launch of a build of the body (Kern) with 64 * WAVES threads per workgroup: the ring of its
+// a.parts_per_wg parts in dynamic LDS behind TABS bytes of product tables.
+template <auto Kern, int STEP, size_t TABS, int WAVES, typename Params>
+hipError_t launch_build(const Params& a, hipStream_t s) {
     const size_t lds = size_t(2) * a.parts_per_wg * (a.d + a.p) * (STEP + 16);  // ring
-    constexpr size_t tabs = size_t(DT ? DT : kMaxFusedData) * 256 * (PMAX <= 4 ? 4 : 8);
-    if (lds + tabs > kCuLdsBytes) return hipErrorInvalidValue;
+    if (lds + TABS > kCuLdsBytes) return hipErrorInvalidValue;
     static const bool attr = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&encode_hash_kernel<PMAX, STEP, DT, SW, ENC3>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, int(kCuLdsBytes - tabs)) == hipSuccess;
+        reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+        int(kCuLdsBytes - TABS)) == hipSuccess;
     if (!attr) return hipErrorInvalidValue;
     const uint32_t grid = (a.n_parts + a.parts_per_wg - 1) / a.parts_per_wg;
     clear_stale_error();
-    hipLaunchKernelGGL((encode_hash_kernel<PMAX, STEP, DT, SW, ENC3>), dim3(grid),
-                       dim3(64 * (SW + 4)), lds, s, a);
+    hipLaunchKernelGGL(Kern, dim3(grid), dim3(64 * WAVES), lds, s, a);
     return hipGetLastError();
+}
+
+constexpr size_t tabs_bytes(int dt, int pmax) {
+    return size_t(dt ? dt : kMaxFusedData) * 256 * (pmax <= 4 ? 4 : 8);
+}
+
+template <int PMAX, int STEP, int DT, int SW = 4, bool ENC3 = false>
+hipError_t launch_p(const FusedParams& a, hipStream_t s) {
+    return launch_build<&encode_hash_kernel<PMAX, STEP, DT, SW, ENC3>, STEP, tabs_bytes(DT, PMAX),
+                        SW + 4>(a, s);
+}
+
+template <int PMAX, int STEP>
+hipError_t launch_ragged_p(const FusedRaggedParams& a, hipStream_t s) {
+    return launch_build<&encode_hash_ragged_kernel<PMAX, STEP>, STEP, tabs_bytes(0, PMAX), 8>(a, s);
 }
 
 // CEC_FUSED_MODE (test knob): 3 = the generic-d build on every shape it covers (tests against
@@ -499,6 +588,25 @@ hipError_t launch_encode_hash(const FusedParams& in, bool vec16, hipStream_t s) 
         return launch_step<256>(a, s);
     a.parts_per_wg = parts_per_group(t, 128, uint32_t(col_width(int(a.d))));
     return launch_step<128>(a, s);
+}
+
+// The ragged build has the generic build's scope; RS(20,p) and p > 8 stay on the two-pass path.
+bool fused_ragged_covers(uint32_t d, uint32_t p) {
+    return p >= 1 && p <= 8 && d >= 1 && d <= uint32_t(kMaxFusedData);
+}
+
+// Steps as in launch_encode_hash: 256 bytes when the ring and the tables fit the CU's LDS, else
+// 128 (p > 4 only: with 4-byte entries the ring of 256 SHA lanes always fits).
+hipError_t launch_encode_hash_ragged(const FusedRaggedParams& in, hipStream_t s) {
+    if (in.n_parts == 0) return hipSuccess;
+    if (!fused_ragged_covers(in.d, in.p)) return hipErrorInvalidValue;
+    FusedRaggedParams a = in;
+    const uint32_t t = a.d + a.p;
+    a.parts_per_wg = parts_per_group(t, 256);
+    if (size_t(2) * a.parts_per_wg * t * (256 + 16) + tabs_bytes(0, int(a.p)) <= kCuLdsBytes)
+        return a.p <= 4 ? launch_ragged_p<4, 256>(a, s) : launch_ragged_p<8, 256>(a, s);
+    a.parts_per_wg = parts_per_group(t, 128);
+    return launch_ragged_p<8, 128>(a, s);
 }
 
 }  // namespace cec

@@ -138,6 +138,29 @@ uint64_t ragged_max_units();  // most units one launch can address (grid and ind
 bool fused_supported(uint32_t d, uint32_t p);
 bool fused_covers(uint32_t d, uint32_t p, uint64_t len);
 hipError_t launch_encode_hash(const FusedParams& a, bool vec16, hipStream_t s);
+
+// Fused encode_sep + SHA-256 over a ragged batch in one launch (fused_kernels.hip): the layout
+// and the part records of RaggedParams ({off, L} per part, split: {off, L, disp}; every output
+// row's chunk at its address plus disp[k], not one byte of the data chunks written), exactly L_k
+// bytes of each parity chunk written, digests at (k * (d + p) + i) * 32 of the caller's order.
+// `order` lists the parts by chunk length, longest first: workgroup w takes parts
+// order[w * G ..], G = parts_per_wg, and runs as many steps as its first part needs.
+// Chunk lengths below 2^39 (the step count is 32-bit).
+struct FusedRaggedParams {
+    uint8_t* base;          // split: only read
+    const uint32_t* pat;    // the codec's encode record
+    const uint32_t* order;  // [n_parts]
+    const uint32_t* parts;  // [n_parts][4], split: [n_parts][6]
+    uint8_t* digests;
+    uint32_t n_parts;
+    uint32_t d;
+    uint32_t p;
+    uint32_t split;
+    uint32_t parts_per_wg;  // set by launch_encode_hash_ragged
+};
+// d <= 16 and p <= 8 (the generic fused build's scope); other shapes take the two-pass path.
+bool fused_ragged_covers(uint32_t d, uint32_t p);
+hipError_t launch_encode_hash_ragged(const FusedRaggedParams& a, hipStream_t s);
 hipError_t launch_sha256(const ShaParams& a, bool vec16, hipStream_t s);
 // Whether launch_sha256 takes the split producer/rounds kernel for `chunks` chunks (small
 // launches: lower latency per chain); callers pick separate encode + SHA over the fused kernel

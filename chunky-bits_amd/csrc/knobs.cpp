@@ -33,6 +33,8 @@ Knobs* parse() {
     if (const char* e = std::getenv("CEC_FUSED_MODE")) k->fused_mode = std::atoi(e);
     if (const char* e = std::getenv("CEC_FUSED"))
         k->fused = e[0] == '0' ? 0 : e[0] == '1' ? 1 : -1;
+    if (const char* e = std::getenv("CEC_RAGGED_FUSED"))  // "0" or "1"; anything else: unset
+        k->ragged_fused = (e[0] == '0' || e[0] == '1') && e[1] == '\0' ? e[0] - '0' : -1;
     k->coalesce_us = uint32_t(number("CEC_COALESCE_US", 200));
     k->coalesce_max_bytes = std::max<size_t>(size_t(number("CEC_COALESCE_MAX_MIB", 1024)), 1)
                             << 20;

@@ -3,7 +3,7 @@
 // Every knob is parsed into one immutable snapshot on first use; the launch paths read the
 // snapshot, never the environment.  The knobs are capacities and diagnostics, plus the test
 // knobs that force one of the library's own paths at test sizes (CEC_APPLY_BS,
-// CEC_APPLY_MAX_BLOCKS, CEC_SHA_VARIANT 1/2, CEC_FUSED_MODE 3, CEC_FUSED).
+// CEC_APPLY_MAX_BLOCKS, CEC_SHA_VARIANT 1/2, CEC_FUSED_MODE 3, CEC_FUSED, CEC_RAGGED_FUSED).
 // The reference calls the hot path from tokio worker threads (writer.rs:200-210 spawns a task
 // per part; file_part.rs:161 runs the encode inside block_in_place), and getenv racing a setenv
 // elsewhere in the host process is undefined behaviour; a snapshot read is a plain load.
@@ -28,6 +28,7 @@ struct Knobs {
     int fused_mode = 0;             // CEC_FUSED_MODE (raw value; only 3 is honoured)
     // capi.cpp (fused), percall.cpp, ragged.cpp
     int fused = -1;                 // CEC_FUSED 0/1 (-1: by batch size)
+    int ragged_fused = -1;          // CEC_RAGGED_FUSED 0/1 (-1: by batch size, ragged.cpp)
     uint32_t coalesce_us = 200;     // CEC_COALESCE_US
     size_t coalesce_max_bytes = size_t(1024) << 20;  // CEC_COALESCE_MAX_MIB
     bool coalesce_trace = false;    // CEC_COALESCE_TRACE

@@ -102,8 +102,9 @@ int cec::split_check(size_t d, size_t p, const uint8_t* data, const size_t* doff
 namespace {
 
 // The per-part device records of the parts ids[0 .. count) (null: parts 0 .. count - 1):
-// units[count + 1] = the prefix array of their work units, parts[4 * count] = {off lo, off hi,
-// L lo, L hi}.  Returns the unit total, at most the whole batch's, which ragged_check bounded.
+// units[count + 1] = the prefix array of their work units (null: not wanted), parts[4 * count] =
+// {off lo, off hi, L lo, L hi}.  Returns the unit total, at most the whole batch's, which
+// ragged_check bounded.
 // With `disp` (the split layout, kernels.hpp RaggedParams::split) a record has two more words,
 // {disp lo, disp hi}: parts[6 * count].
 uint32_t part_records(const size_t* offs, const size_t* lens, const uint32_t* ids, size_t count,
@@ -114,7 +115,7 @@ uint32_t part_records(const size_t* offs, const size_t* lens, const uint32_t* id
     for (size_t q = 0; q < count; ++q) {
         const size_t k = ids ? ids[q] : q;
         const uint64_t off = offs[k], L = lens[k];
-        units[q] = uint32_t(acc);
+        if (units) units[q] = uint32_t(acc);
         acc += (L - 1) / unit + 1;
         parts[w * q + 0] = uint32_t(off);
         parts[w * q + 1] = uint32_t(off >> 32);
@@ -125,8 +126,14 @@ uint32_t part_records(const size_t* offs, const size_t* lens, const uint32_t* id
             parts[w * q + 5] = uint32_t(disp[k] >> 32);
         }
     }
-    units[count] = uint32_t(acc);
+    if (units) units[count] = uint32_t(acc);
     return uint32_t(acc);
+}
+
+// order[n] = the parts stably sorted by chunk length, longest first.
+void length_order(const size_t* lens, size_t n, uint32_t* order) {
+    std::iota(order, order + n, 0u);
+    std::stable_sort(order, order + n, [&](uint32_t x, uint32_t y) { return lens[x] > lens[y]; });
 }
 
 // The SHA-256 list of a ragged batch: ptrs / h_len of the items k * t + i that pass `pick` (the
@@ -139,9 +146,7 @@ template <typename Pick, typename At>
 size_t sha_list(const size_t* lens, size_t n, size_t t, Pick pick, At at, uint64_t* ptrs,
                 uint64_t* h_len, uint32_t* order) {
     std::vector<uint32_t> by_len(n);
-    std::iota(by_len.begin(), by_len.end(), 0u);
-    std::stable_sort(by_len.begin(), by_len.end(),
-                     [&](uint32_t x, uint32_t y) { return lens[x] > lens[y]; });
+    length_order(lens, n, by_len.data());
     size_t count = 0;
     for (const size_t k : by_len) {
         const size_t cs = ragged_stride(lens[k]);
@@ -158,22 +163,59 @@ size_t sha_list(const size_t* lens, size_t n, size_t t, Pick pick, At at, uint64
 
 }  // namespace
 
-// [ptrs u64 x items][lens u64 x items][order u32 x items][units u32 x n+1][parts u32 x 4n or 6n]
+// Two-pass: [ptrs u64 x items][lens u64 x items][order u32 x items][units u32 x n+1]
+// [parts u32 x 4n or 6n]; fused: [order u32 x n][parts u32 x 4n or 6n], which is less.
 size_t cec::ragged_words_bytes(size_t t, size_t n) { return n * t * 20 + (n + 1) * 4 + n * 24; }
 
-// The launches of a checked ragged encode on `s`: one upload of the per-part words (the SHA-256
-// list, the part records), the GF(2^8) kernel, the SHA-256 kernel.  The host arrays are copied
-// into the words' page-locked side before this returns.  Part k's data chunks lie at
-// data + doffs[k]; its parity chunks behind them (poffs null: the layout of cec_ragged_layout,
-// records without a displacement) or at parity + poffs[k] (the split layout).
+namespace {
+
+// Ragged encode launch sequences since load, by path (cec_ragged_stats).
+std::atomic<uint64_t> g_fused_seqs{0}, g_two_pass_seqs{0};
+
+// What an unset CEC_RAGGED_FUSED selects for a launch too large for the split SHA-256 kernel:
+// fused only if its worst repeat is below two-pass's best repeat in all three configurations of
+// tools/small_files_bench.py --device.  One run (profiles/small_files/device_fused.log), event
+// intervals of three alternating repeats, two-pass against fused:
+//   4096 x RS(10,4) x 64 KiB, uniform lengths      3.75-3.93 ms   3.33-3.45 ms   fused wins
+//   4096 files of 1 KiB-4 MiB as RS(3,2) parts    42.58-42.68 ms 42.24-42.29 ms  fused wins
+//   the same files as RS(10,4) parts              17.76-17.83 ms 19.26-19.27 ms  two-pass wins
+// The mixed batches are bound by the SHA-256 chain of their longest chunk, which the fused
+// workgroup's lane waves walk with a barrier per step beside the encoders: not in all three, so
+// two-pass stays and the kernel is reached through the knob.
+constexpr bool kRaggedFusedDefault = false;
+
+// Whether a ragged encode of n parts of these (checked) lengths takes the fused kernel
+// (fused_kernels.hip encode_hash_ragged_kernel) or the GF(2^8) launch and the SHA-256 list launch.
+// As prefer_fused for the uniform batches: CEC_RAGGED_FUSED 0 / 1 forces one, else two-pass while
+// the SHA-256 launch would take the split kernel (lower latency per chain), and above that what
+// the measurement says.  Shapes the fused kernel does not cover take two passes whatever the knob.
+bool ragged_prefers_fused(size_t d, size_t p, const size_t* lens, size_t n) {
+    if (!fused_ragged_covers(uint32_t(d), uint32_t(p))) return false;
+    for (size_t k = 0; k < n; ++k)
+        if (lens[k] >> 39) return false;  // the kernel's 32-bit step count
+    const int f = knobs().ragged_fused;
+    return f >= 0 ? f == 1 : !use_split(n * (d + p)) && kRaggedFusedDefault;
+}
+
+}  // namespace
+
+// The launches of a checked ragged encode on `s`: one upload of the per-part words, then the
+// fused kernel (part order, part records), or the GF(2^8) kernel and the SHA-256 kernel (the
+// SHA-256 list, the part records).  The host arrays are copied into the words' page-locked side
+// before this returns.  Part k's data chunks lie at data + doffs[k]; its parity chunks behind
+// them (poffs null: the layout of cec_ragged_layout, records without a displacement) or at
+// parity + poffs[k] (the split layout).
 int cec::ragged_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, uint8_t* parity,
                        const size_t* poffs, const size_t* lens, size_t n, uint8_t* digests,
                        hipStream_t s, uint8_t* hwords, uint8_t* dwords) {
     const size_t d = c->d, t = c->d + c->p, items = n * t;
     uint32_t* drec = nullptr;
     CEC_TRY(c->encode_record(&drec));
+    const bool fused = ragged_prefers_fused(d, c->p, lens, n);
+    // fused: the part order where the SHA-256 list and the unit prefix would be
     const size_t o_len = items * 8, o_ord = o_len + items * 8, o_units = o_ord + items * 4,
-                 o_parts = o_units + (n + 1) * 4, bytes = o_parts + n * (poffs ? 24 : 16);
+                 o_parts = fused ? n * 4 : o_units + (n + 1) * 4,
+                 bytes = o_parts + n * (poffs ? 24 : 16);
     Scratch sc;  // the words of a caller that has none: released on s behind the launches below
     if (!hwords) {
         CEC_TRY(sc.acquire(bytes, s));
@@ -185,19 +227,38 @@ int cec::ragged_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, u
     for (size_t k = 0; k < disp.size(); ++k)
         disp[k] = (reinterpret_cast<uint64_t>(parity) + poffs[k]) -
                   (reinterpret_cast<uint64_t>(data) + doffs[k] + d * ragged_stride(lens[k]));
-    sha_list(
-        lens, n, t, [](size_t) { return true; },
-        [&](size_t k, size_t i, size_t cs) {
-            return i < d || !poffs ? data + doffs[k] + i * cs : parity + poffs[k] + (i - d) * cs;
-        },
-        reinterpret_cast<uint64_t*>(hwords), reinterpret_cast<uint64_t*>(hwords + o_len),
-        reinterpret_cast<uint32_t*>(hwords + o_ord));
-    RaggedParams a{};
-    a.total_units = part_records(doffs, lens, nullptr, n,
-                                 reinterpret_cast<uint32_t*>(hwords + o_units),
-                                 reinterpret_cast<uint32_t*>(hwords + o_parts),
-                                 poffs ? disp.data() : nullptr);
+    if (fused)
+        length_order(lens, n, reinterpret_cast<uint32_t*>(hwords));
+    else
+        sha_list(
+            lens, n, t, [](size_t) { return true; },
+            [&](size_t k, size_t i, size_t cs) {
+                return i < d || !poffs ? data + doffs[k] + i * cs
+                                       : parity + poffs[k] + (i - d) * cs;
+            },
+            reinterpret_cast<uint64_t*>(hwords), reinterpret_cast<uint64_t*>(hwords + o_len),
+            reinterpret_cast<uint32_t*>(hwords + o_ord));
+    const uint32_t total_units = part_records(
+        doffs, lens, nullptr, n, fused ? nullptr : reinterpret_cast<uint32_t*>(hwords + o_units),
+        reinterpret_cast<uint32_t*>(hwords + o_parts), poffs ? disp.data() : nullptr);
     HIP_TRY(hipMemcpyAsync(dwords, hwords, bytes, hipMemcpyHostToDevice, s));
+    if (fused) {
+        FusedRaggedParams f{};
+        f.base = const_cast<uint8_t*>(data);  // split: only read
+        f.pat = drec;
+        f.order = reinterpret_cast<const uint32_t*>(dwords);
+        f.parts = reinterpret_cast<const uint32_t*>(dwords + o_parts);
+        f.digests = digests;
+        f.n_parts = uint32_t(n);
+        f.d = uint32_t(d);
+        f.p = uint32_t(c->p);
+        f.split = poffs ? 1u : 0u;
+        HIP_TRY(launch_encode_hash_ragged(f, s));
+        g_fused_seqs.fetch_add(1, std::memory_order_relaxed);
+        return CEC_OK;
+    }
+    RaggedParams a{};
+    a.total_units = total_units;
     a.base = const_cast<uint8_t*>(data);  // split: only read
     a.pat = drec;
     a.units = reinterpret_cast<const uint32_t*>(dwords + o_units);
@@ -216,6 +277,7 @@ int cec::ragged_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, u
     h.items = reinterpret_cast<const uint32_t*>(dwords + o_ord);
     h.n_items = uint32_t(items);
     HIP_TRY(launch_sha256(h, true, s));
+    g_two_pass_seqs.fetch_add(1, std::memory_order_relaxed);
     return CEC_OK;
 }
 
@@ -603,6 +665,11 @@ int parts_verify_round(Arena& a, const uint8_t* const* bufs, const size_t* lens,
 extern "C" {
 
 size_t cec_ragged_stride(size_t chunk_len) { return ragged_stride(chunk_len); }
+
+void cec_ragged_stats(uint64_t* fused, uint64_t* two_pass) {
+    if (fused) *fused = g_fused_seqs.load();
+    if (two_pass) *two_pass = g_two_pass_seqs.load();
+}
 
 int cec_ragged_layout(size_t total_shards, const size_t* chunk_lens, size_t n_parts,
                       size_t* part_offsets, size_t* total_bytes) {

@@ -384,6 +384,7 @@ pub mod sys {
             capacity: usize,
         ) -> c_int;
         pub fn cec_coalesce_stats(calls: *mut u64, launches: *mut u64);
+        pub fn cec_ragged_stats(fused: *mut u64, two_pass: *mut u64);
         pub fn cec_build_info() -> *const std::os::raw::c_char;
         pub fn cec_build_id() -> *const std::os::raw::c_char;
         pub fn cec_current_device(device: *mut c_int) -> c_int;
@@ -924,6 +925,14 @@ pub fn parts_encode(codec: &ReedSolomon, bufs: &[&[u8]]) -> Result<Vec<EncodedPa
 /// Chunk stride of a ragged batch: `chunk_len` rounded up to 16 (`cec_ragged_stride`).
 pub fn ragged_stride(chunk_len: usize) -> usize {
     unsafe { sys::cec_ragged_stride(chunk_len) }
+}
+
+/// Ragged encode launch sequences queued since load, process-wide (`cec_ragged_stats`): those that
+/// took the fused encode + SHA-256 kernel, and those that took the two-pass path.
+pub fn ragged_stats() -> (u64, u64) {
+    let (mut fused, mut two_pass) = (0u64, 0u64);
+    unsafe { sys::cec_ragged_stats(&mut fused, &mut two_pass) };
+    (fused, two_pass)
 }
 
 /// The packed ragged layout (`cec_ragged_layout`) of parts of `total_shards` chunks with these

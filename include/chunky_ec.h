@@ -324,6 +324,14 @@ int cec_encode_hash_split(const cec_codec* codec, const uint8_t* data_base,
                           const size_t* parity_offsets, const size_t* chunk_lens, size_t n_parts,
                           uint8_t* digests, void* stream);
 
+/* The ragged encodes (cec_encode_hash_ragged, cec_encode_hash_split, and cec_parts_encode and
+ * cec_parts_pipeline_* on top of them) run as one fused encode + SHA-256 launch or as two passes,
+ * a GF(2^8) launch and a SHA-256 launch, with identical results.  Shapes beyond d <= 16, p <= 8
+ * always take two passes; CEC_RAGGED_FUSED (environment, 0 / 1) forces one path for the others.
+ * cec_ragged_stats: launch sequences queued by each path since load, process-wide (either
+ * pointer may be null), the ragged counterpart of cec_coalesce_stats. */
+void cec_ragged_stats(uint64_t* fused, uint64_t* two_pass);
+
 /* SHA-256 of chunks [first_chunk, first_chunk + n_chunks) of every part.
  * digests: device buffer, digest of (part k, chunk first_chunk + c) at (k*n_chunks + c)*32. */
 int cec_sha256_batch(const cec_part_batch* batch, size_t first_chunk, size_t n_chunks,

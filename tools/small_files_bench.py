@@ -19,8 +19,14 @@ synchronised before each clock reading.  Reported: GB/s of file bytes and parts/
 All arms' digests must agree (asserted).
 
 --device: 4096 x RS(10,4) x 64 KiB parts, device resident: cec_encode_hash_ragged with uniform
-lengths and cec_encode_hash_split (the same parts, data and parity in regions of their own)
-against cec_encode_hash_batch on the same bytes; the times and the ratios.
+lengths, by its two-pass path (CEC_RAGGED_FUSED=0) and by the fused kernel (=1), and
+cec_encode_hash_split (the same parts, data and parity in regions of their own) against
+cec_encode_hash_batch on the same bytes; the times and the ratios.  Then the files of the
+host-staged workload as packed device-resident parts at RS(3,2) and at RS(10,4): one
+cec_encode_hash_ragged call by either path.  Arms alternate after a warm-up, each call timed
+between two stream events; all arms' parity and digests must be equal (asserted).  The fused
+kernel becomes the default for large ragged launches only if its worst repeat is below the
+two-pass path's best in all three configurations.
 
 --read: the read side on the same seeded files and shapes.  Every part is stored as the oracle
 encodes it and its data chunk k % d is erased, so every part is decoded from d - 1 data chunks and
@@ -602,7 +608,43 @@ def device_read(args):
                       "ratio": ratio}))
 
 
-def device_mode(args):
+KNOB = "CEC_RAGGED_FUSED"
+
+
+def set_knob(value):
+    """CEC_RAGGED_FUSED = value (None: unset) from the next call on."""
+    if value is None:
+        os.environ.pop(KNOB, None)
+    else:
+        os.environ[KNOB] = value
+    ce.reload_knobs()
+
+
+def event_ms(fn, knob=None):
+    """One call of fn between two stream events, the knob set before the first."""
+    set_knob(knob)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    set_knob(None)
+    return e0.elapsed_time(e1)
+
+
+def fused_verdict(name, two_pass, fused):
+    """The rule of the pipeline's arm d, without a margin fixed in advance: fused wins a
+    configuration when its worst repeat is below two-pass's best."""
+    wins = max(fused) < min(two_pass)
+    print(f"   {name}: two-pass {min(two_pass):.3f}-{max(two_pass):.3f} ms, fused "
+          f"{min(fused):.3f}-{max(fused):.3f} ms, two-pass best / fused worst "
+          f"{min(two_pass) / max(fused):.3f} -> fused's worst below two-pass's best: {wins}",
+          flush=True)
+    return {"two_pass_ms": two_pass, "fused_ms": fused, "fused_wins": wins}
+
+
+def device_uniform(args):
     d, p, n, L = 10, 4, 4096, 65536
     t = d + p
     dev = torch.device("cuda", 0)
@@ -633,41 +675,105 @@ def device_mode(args):
         ce.encode_hash_split(rs, sdata.data_ptr(), doffs, spar.data_ptr(), poffs, lens,
                              dig_s.data_ptr())
 
-    def run(fn):
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1)
-
-    for fn in (uniform, ragged, split):
-        run(fn)
+    # (name, call, CEC_RAGGED_FUSED): the ragged call by both of its paths, the split call by
+    # the default
+    arms = [("encode_hash_batch", uniform, None), ("encode_hash_ragged", ragged, "0"),
+            ("encode_hash_ragged fused", ragged, "1"), ("encode_hash_split", split, None)]
+    for _, fn, knob in arms:
+        event_ms(fn, knob)
     uniform()
     torch.cuda.synchronize()
     parity = buf[:, d:].clone()
-    ragged()
+    for knob in ("0", "1"):  # each path's parity and digests against the uniform call's
+        buf[:, d:] = 0
+        dig_r.zero_()
+        before = ce.ragged_stats()
+        event_ms(ragged, knob)
+        after = ce.ragged_stats()
+        assert (after[0] - before[0], after[1] - before[1]) == ((1, 0) if knob == "1" else (0, 1))
+        assert torch.equal(parity, buf[:, d:]) and torch.equal(dig_u, dig_r), "results differ"
     split()
     torch.cuda.synchronize()
-    assert torch.equal(parity, buf[:, d:]) and torch.equal(dig_u, dig_r), "results differ"
     assert torch.equal(parity, spar) and torch.equal(dig_u, dig_s), "split results differ"
-    ms = {"encode_hash_batch": [], "encode_hash_ragged": [], "encode_hash_split": []}
+    ms = {name: [] for name, _, _ in arms}
     for rep in range(args.repeats):
-        ms["encode_hash_batch"].append(run(uniform))
-        ms["encode_hash_ragged"].append(run(ragged))
-        ms["encode_hash_split"].append(run(split))
+        for name, fn, knob in arms:
+            ms[name].append(event_ms(fn, knob))
     print(f"== device resident, {n} x RS({d},{p}) x {L} B ({n * d * L / 2**30:.2f} GiB of data)")
     for k, v in ms.items():
         print(f"   {k}: " + "  ".join(f"{x:.3f} ms" for x in v))
     ratio = min(ms["encode_hash_ragged"]) / min(ms["encode_hash_batch"])
+    fused_ratio = min(ms["encode_hash_ragged fused"]) / min(ms["encode_hash_batch"])
     split_ratio = min(ms["encode_hash_split"]) / min(ms["encode_hash_ragged"])
     spread = max(max(v) - min(v) for v in ms.values())
     print(f"   ragged / uniform (best of {args.repeats}): {ratio:.3f}   (same parity, same digests)")
+    print(f"   fused ragged / uniform (best of {args.repeats}): {fused_ratio:.3f}")
     print(f"   split / ragged (best of {args.repeats}): {split_ratio:.3f}   largest spread between "
           f"repeats of an arm: {spread:.3f} ms")
-    print(json.dumps({"tool": "small_files_bench", "mode": "device", "ms": ms, "ratio": ratio,
-                      "split_over_ragged": split_ratio, "spread_ms": spread}))
+    verdict = fused_verdict("uniform 64 KiB", ms["encode_hash_ragged"],
+                            ms["encode_hash_ragged fused"])
+    return {"ms": ms, "ratio": ratio, "fused_over_uniform": fused_ratio,
+            "split_over_ragged": split_ratio, "spread_ms": spread}, verdict
+
+
+def device_mixed(args, pool, files, d, p):
+    """The tool's own files as packed device-resident parts of d x 1 MiB at most: one
+    cec_encode_hash_ragged call over all of them, by the two-pass and by the fused path."""
+    t = d + p
+    dev = torch.device("cuda", 0)
+    rs = ce.ReedSolomon(d, p)
+    parts = cut_parts(files, d)
+    n = len(parts)
+    lens = [(ln + d - 1) // d for _, ln in parts]
+    offs, total = ce.ragged_layout(t, lens)
+    host = np.zeros(total, np.uint8)
+    for (o, ln), off, L in zip(parts, offs, lens):  # chunk j = bytes [j*L, (j+1)*L), zeros behind
+        cs = ce.ragged_stride(L)
+        for j in range(d):
+            have = max(0, min(L, ln - j * L))
+            host[off + j * cs:off + j * cs + have] = pool[o + j * L:o + j * L + have]
+    start = torch.from_numpy(host).to(dev)
+    del host
+    buf = start.clone()
+    dig = torch.zeros((n, t, 32), dtype=torch.uint8, device=dev)
+
+    def ragged():
+        ce.encode_hash_ragged(rs, buf.data_ptr(), offs, lens, dig.data_ptr())
+
+    results = {}
+    for knob in ("0", "1"):  # warm-up, and each path's whole buffer and digests kept
+        buf.copy_(start)
+        dig.zero_()
+        event_ms(ragged, knob)
+        results[knob] = (buf.clone(), dig.clone())
+    assert torch.equal(results["0"][0], results["1"][0]), "buffers differ"
+    assert torch.equal(results["0"][1], results["1"][1]), "digests differ"
+    assert not torch.equal(results["0"][0], start)
+    del results
+    ms = {"0": [], "1": []}
+    for rep in range(args.repeats):
+        for knob in ("0", "1"):
+            ms[knob].append(event_ms(ragged, knob))
+    print(f"== device resident, mixed lengths: {len(files)} files as {n} packed RS({d},{p}) parts, "
+          f"chunk lengths {min(lens)}-{max(lens)} B, {sum(ln for _, ln in parts) / 2**30:.2f} GiB "
+          f"of data (same buffer, same digests by both paths)")
+    print("   two-pass: " + "  ".join(f"{x:.3f} ms" for x in ms["0"]))
+    print("   fused:    " + "  ".join(f"{x:.3f} ms" for x in ms["1"]))
+    return fused_verdict(f"mixed RS({d},{p})", ms["0"], ms["1"])
+
+
+def device_mode(args):
+    uniform, v1 = device_uniform(args)
+    pool, files = make_files(args.files)
+    verdicts = {"uniform_10_4_64k": v1}
+    for d, p in ((3, 2), (10, 4)):
+        verdicts[f"mixed_{d}_{p}"] = device_mixed(args, pool, files, d, p)
+    fused_default = all(v["fused_wins"] for v in verdicts.values())
+    print(f"== fused's worst repeat below two-pass's best in all three configurations: "
+          f"{fused_default} -> the default for large ragged launches is "
+          f"{'fused' if fused_default else 'two-pass'}")
+    print(json.dumps({"tool": "small_files_bench", "mode": "device", **uniform,
+                      "fused": verdicts, "fused_default": fused_default}))
 
 
 def main():
