@@ -149,6 +149,12 @@ _sig("cec_read_ragged", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp, _u8p,
                          ctypes.POINTER(ctypes.c_int), _vp])
 _sig("cec_resilver_ragged", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp, _u8p,
                              ctypes.POINTER(ctypes.c_int), _vp])
+_sig("cec_read_ragged_async", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp, _u8p,
+                               ctypes.POINTER(ctypes.c_int), _vp])
+_sig("cec_resilver_ragged_async", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp, _u8p,
+                                   ctypes.POINTER(ctypes.c_int), _vp])
+_sig("cec_ragged_read_stats", [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
+     None)
 _sig("cec_parts_read", [_vp, ctypes.POINTER(_u8p), _szp, ctypes.c_size_t, _u8p, _u8p, ctypes.c_int,
                         _u8p, ctypes.POINTER(ctypes.c_int)])
 _sig("cec_verify_ragged", [ctypes.c_size_t, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp, _u8p, _vp])
@@ -767,6 +773,56 @@ def resilver_ragged(codec: ReedSolomon, base_ptr: int, part_offsets: Sequence[in
     """:func:`resilver_batch` over parts of different chunk lengths (``cec_resilver_ragged``)."""
     return _verify_rebuild_ragged(_lib.cec_resilver_ragged, codec, base_ptr, part_offsets,
                                   chunk_lens, present, expected_ptr, stream)
+
+
+def _verify_rebuild_ragged_async(fn, codec, base_ptr, part_offsets, chunk_lens, present,
+                                 expected_ptr, verified, part_status, stream):
+    offs, lens, n = _ragged_args(part_offsets, chunk_lens)
+    items = n * codec.total_shard_count()
+    pres = bytes(present)
+    assert len(pres) == items
+    if n and (_out_nbytes(verified) < items or
+              _out_nbytes(part_status) < n * ctypes.sizeof(ctypes.c_int)):
+        raise ValueError("verified needs n*(d+p) bytes and part_status n C ints")
+    ver = ctypes.cast(_addr(verified), _u8p) if n else _u8p()
+    st = ctypes.cast(_addr(part_status), ctypes.POINTER(ctypes.c_int)) if n else None
+    _check(fn(codec.handle, base_ptr, offs, lens, n, ctypes.cast(ctypes.c_char_p(pres), _u8p),
+              expected_ptr, ver, st, _stream_ptr(stream)))
+
+
+def _out_nbytes(buf) -> int:
+    return buf.nbytes if hasattr(buf, "nbytes") else _nbytes(buf)
+
+
+def read_ragged_async(codec: ReedSolomon, base_ptr: int, part_offsets: Sequence[int],
+                      chunk_lens: Sequence[int], present, expected_ptr: int, verified,
+                      part_status, stream=None) -> None:
+    """:func:`read_ragged` without the wait (``cec_read_ragged_async``): the decode is planned
+    on the device, so the call only queues work on ``stream``.  ``verified`` (``n*(d+p)`` bytes)
+    and ``part_status`` (``n`` C ints) are host buffers (a :class:`HostBuffer`, a numpy array or
+    any writable buffer) that copies queued on the stream fill: valid once the stream's work is
+    done, and to be kept alive until then.  Only page-locked buffers (:class:`HostBuffer`) keep
+    the call from blocking."""
+    _verify_rebuild_ragged_async(_lib.cec_read_ragged_async, codec, base_ptr, part_offsets,
+                                 chunk_lens, present, expected_ptr, verified, part_status, stream)
+
+
+def resilver_ragged_async(codec: ReedSolomon, base_ptr: int, part_offsets: Sequence[int],
+                          chunk_lens: Sequence[int], present, expected_ptr: int, verified,
+                          part_status, stream=None) -> None:
+    """:func:`resilver_ragged` without the wait (``cec_resilver_ragged_async``); outputs as
+    :func:`read_ragged_async`."""
+    _verify_rebuild_ragged_async(_lib.cec_resilver_ragged_async, codec, base_ptr, part_offsets,
+                                 chunk_lens, present, expected_ptr, verified, part_status, stream)
+
+
+def ragged_read_stats():
+    """(device_planned, host_planned): ``*_ragged_async`` calls since load by who planned the
+    decode (cec_ragged_read_stats); host_planned counts the shapes outside the device planner's
+    scope (d > 32 or p > 8), which take the synchronous path inside the call."""
+    dev, host = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _lib.cec_ragged_read_stats(ctypes.byref(dev), ctypes.byref(host))
+    return dev.value, host.value
 
 
 def parts_read(codec: ReedSolomon, parts: Sequence[Sequence], expected: Sequence,

@@ -28,8 +28,8 @@ thread_local std::string g_last_error;
 // zeros on its later passes, and metadata words uploaded into it read as zeros (round 2's
 // fork/join read shape loses whole outputs the same way, with the free queued behind the work
 // or only after a sync).  hipMalloc'd memory never showed it (profiles/r3_repro/).
-// Instead a process-wide pool of device buffers, each with a page-locked host mirror
-// and an event: a buffer is handed out only once the event recorded after its last use has
+// Instead a process-wide pool of device buffers, each with a page-locked host mirror (device-only
+// ones, for what never crosses the link, go without) and an event: a buffer is handed out only once the event recorded after its last use has
 // completed, the words go up from the mirror (a truly asynchronous copy, no host lifetime to
 // manage), and its release records the event on the stream of the work that used it.
 // ------------------------------------------------------------------------------------------
@@ -37,12 +37,13 @@ class ScratchPool {
    public:
     using Buf = ScratchBuf;
 
-    // A buffer of >= bytes on `device` whose last use has completed.
-    hipError_t acquire(int device, size_t bytes, Buf** out) {
+    // A buffer of >= bytes on `device` whose last use has completed; with a page-locked mirror,
+    // or (mirror false) one without.
+    hipError_t acquire(int device, size_t bytes, bool mirror, Buf** out) {
         std::unique_lock<std::mutex> lk(mu_);
         Buf* best = nullptr;
         for (Buf* b : bufs_) {
-            if (b->device != device || b->in_use) continue;
+            if (b->device != device || b->in_use || (b->host != nullptr) != mirror) continue;
             if (b->pending) {
                 const hipError_t q = hipEventQuery(b->done);
                 if (q == hipErrorNotReady) {
@@ -71,7 +72,7 @@ class ScratchPool {
         b->device = device;
         b->cap = std::max<size_t>(size_t(64) << 10, size_t(1) << (64 - __builtin_clzll(bytes | 1)));
         hipError_t e = hipMalloc(reinterpret_cast<void**>(&b->dev), b->cap);
-        if (e == hipSuccess)
+        if (e == hipSuccess && mirror)
             e = hipHostMalloc(reinterpret_cast<void**>(&b->host), b->cap, hipHostMallocDefault);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&b->done, hipEventDisableTiming);
         if (e != hipSuccess) {
@@ -224,10 +225,10 @@ Scratch::~Scratch() {
     if (buf_) scratch_pool().release(buf_, stream_);
 }
 
-int Scratch::acquire(size_t bytes, hipStream_t s) {
+int Scratch::acquire(size_t bytes, hipStream_t s, bool mirror) {
     int dev = 0;
     CEC_TRY(current_device(&dev));
-    HIP_TRY(scratch_pool().acquire(dev, bytes, &buf_));
+    HIP_TRY(scratch_pool().acquire(dev, bytes, mirror, &buf_));
     stream_ = s;
     return CEC_OK;
 }

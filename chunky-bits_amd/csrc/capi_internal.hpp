@@ -61,7 +61,7 @@ inline size_t coalesce_max_bytes() { return knobs().coalesce_max_bytes; }
 struct ScratchBuf {
     int device = 0;
     uint8_t* dev = nullptr;
-    uint8_t* host = nullptr;  // page-locked mirror of the same size
+    uint8_t* host = nullptr;  // page-locked mirror of the same size (null: a device-only buffer)
     size_t cap = 0;
     hipEvent_t done = nullptr;
     bool in_use = false;   // handed out, release not called yet
@@ -76,7 +76,8 @@ class Scratch {
     Scratch(const Scratch&) = delete;
     Scratch& operator=(const Scratch&) = delete;
     ~Scratch();
-    int acquire(size_t bytes, hipStream_t s);
+    // mirror false: device memory only (host() is null), for what never crosses the link
+    int acquire(size_t bytes, hipStream_t s, bool mirror = true);
     uint8_t* dev() const { return buf_->dev; }
     uint8_t* host() const { return buf_->host; }
 
@@ -289,8 +290,9 @@ int ragged_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, uint8_
 
 #pragma GCC visibility pop
 
-// The codec behind the C-ABI's handle: the coding matrix, the encode record (one device copy per
-// device) and the decode records by erasure pattern.
+// The codec behind the C-ABI's handle: the coding matrix (one device copy per device, for the
+// on-device decode planner), the encode record (one device copy per device) and the decode
+// records by erasure pattern.
 struct cec_codec {
     size_t d = 0, p = 0;
     cec::ByteMatrix m;             // (d+p) x d
@@ -298,6 +300,7 @@ struct cec_codec {
     bool bs = false;               // parity rows = a compiled bit-sliced shape (bs_encode_matches)
     std::mutex mu;
     std::unordered_map<int, uint32_t*> dev_enc;  // encode record per device
+    std::unordered_map<int, uint8_t*> dev_mat;   // coding matrix per device (matrix_device)
     // Decode records, least recently used first out once kDecCacheCap patterns are cached (every
     // 1..4-erasure pattern of RS(10,4), both modes, is 2 940).
     static constexpr size_t kDecCacheCap = 4096;
@@ -311,26 +314,43 @@ struct cec_codec {
         for (auto& kv : dev_enc) {
             if (hipSetDevice(kv.first) == hipSuccess) (void)hipFree(kv.second);
         }
+        for (auto& kv : dev_mat) {
+            if (hipSetDevice(kv.first) == hipSuccess) (void)hipFree(kv.second);
+        }
         (void)hipSetDevice(cur);
+    }
+
+    // Device copy of `bytes` bytes at `src` on the current device, made on first use and kept in
+    // `copies`.
+    template <typename T>
+    int device_copy(std::unordered_map<int, T*>& copies, const void* src, size_t bytes, T** out) {
+        int dev = 0;
+        CEC_TRY(cec::current_device(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = copies.find(dev);
+        if (it != copies.end()) {
+            *out = it->second;
+            return CEC_OK;
+        }
+        T* ptr = nullptr;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ptr), bytes));
+        const hipError_t e = hipMemcpy(ptr, src, bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(ptr);
+            return cec::hip_fail(e, "hipMemcpy (codec device copy)");
+        }
+        copies[dev] = ptr;
+        *out = ptr;
+        return CEC_OK;
     }
 
     // Device copy of the encode record on the current device.
     int encode_record(uint32_t** out) {
-        int dev = 0;
-        CEC_TRY(cec::current_device(&dev));
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = dev_enc.find(dev);
-        if (it != dev_enc.end()) {
-            *out = it->second;
-            return CEC_OK;
-        }
-        uint32_t* ptr = nullptr;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ptr), enc.size() * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy(ptr, enc.data(), enc.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        dev_enc[dev] = ptr;
-        *out = ptr;
-        return CEC_OK;
+        return device_copy(dev_enc, enc.data(), enc.size() * sizeof(uint32_t), out);
     }
+
+    // Device copy of the coding matrix ((d+p) x d bytes, row-major) on the current device.
+    int matrix_device(uint8_t** out) { return device_copy(dev_mat, m.v.data(), m.v.size(), out); }
 
     // Decode record for a present set: inputs = first d present chunks (the crate's choice,
     // reconstruct_internal), outputs = missing data (+ missing parity unless data_only).

@@ -135,6 +135,37 @@ hipError_t launch_rs_encode_ragged(const RaggedParams& a, hipStream_t s);
 hipError_t launch_rs_reconstruct_ragged(const RaggedParams& a, hipStream_t s);
 uint64_t ragged_unit_bytes();
 uint64_t ragged_max_units();  // most units one launch can address (grid and index limits)
+
+// The decode plan of a ragged read, built on the device from the verification's flags
+// (plan_kernels.hip): one wave per part, everything device memory.  For part k of d + p chunks:
+//   verified[k][i] = 1 if present[k][i] == CEC_PRESENT_VERIFIED, ok[k][i] if it is otherwise
+//                    nonzero (the chunk was hashed), 0 if it is absent;
+//   part_status[k] = CEC_OK with at least d verified chunks, else CEC_TOO_FEW_SHARDS_PRESENT;
+//   records + k * slot_words = the part's pattern record (gf256.hpp), the one
+//                    cec_codec::decode_record builds for its verified set: inputs the first d
+//                    verified chunks, outputs the unverified data chunks, then (data_only == 0)
+//                    the unverified parity chunks.  Word 0 = 0, and nothing behind it written,
+//                    for a part that cannot be decoded or has nothing to rebuild.
+// matrix: the codec's (d+p) x d coding matrix, row-major bytes.  max_rows: the most rows a part
+// can need (p, or min(p, d) under data_only); slot_words >= pattern_words(d, max_rows).
+struct PlanParams {
+    const uint8_t* present;   // [n_parts][d+p]
+    const uint8_t* ok;        // [n_parts][d+p]
+    const uint8_t* matrix;
+    uint8_t* verified;        // [n_parts][d+p]
+    int32_t* part_status;     // [n_parts]
+    uint32_t* records;        // [n_parts][slot_words]
+    uint32_t n_parts;
+    uint32_t d;
+    uint32_t p;
+    uint32_t slot_words;
+    uint32_t max_rows;
+    uint32_t data_only;
+};
+// d <= 32 (a lane per column of [A | I]) and p <= 8 (max_var_rows(), the shared reconstruct
+// launch): every compiled shape.
+bool decode_plan_covers(uint32_t d, uint32_t p);
+hipError_t launch_decode_plan(const PlanParams& a, hipStream_t s);
 bool fused_supported(uint32_t d, uint32_t p);
 bool fused_covers(uint32_t d, uint32_t p, uint64_t len);
 hipError_t launch_encode_hash(const FusedParams& a, bool vec16, hipStream_t s);

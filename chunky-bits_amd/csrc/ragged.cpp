@@ -1,6 +1,7 @@
 // ragged.cpp — the ragged half of include/chunky_ec.h: parts of different chunk lengths in one
 // launch sequence (cec_encode_hash_ragged, cec_encode_hash_split, cec_reconstruct_ragged,
-// cec_verify_ragged, cec_read_ragged, cec_resilver_ragged) and the host-staged calls on top of
+// cec_verify_ragged, cec_read_ragged, cec_resilver_ragged and their _async forms, which plan the
+// decode on the device and never wait) and the host-staged calls on top of
 // them (cec_parts_encode, cec_parts_read, cec_parts_verify).  Part k's chunk i lies at
 // base + off[k] + i * stride(L_k), stride = L rounded up to 16; the split layout keeps the parity
 // chunks in a region of their own.  Host work only; every step of the path has one home here
@@ -330,41 +331,59 @@ int reconstruct_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const si
     return CEC_OK;
 }
 
+// Bytes of the SHA-256 list of a ragged verification: [ptrs u64 x items][lens u64 x items]
+// [order u32 x items].
+inline size_t verify_list_bytes(size_t items) { return items * 20; }
+
+// The queued half of a ragged verification for a checked layout of t chunks per part: on `s` one
+// upload, the memset of ok[items] (device) and the SHA-256 list launch in verify mode over the
+// chunks that need hashing (present null: all of them; ok and expected indexed by k*t+i).
+// hwords / dwords: page-locked and device room for the list (verify_list_bytes) and, directly
+// behind it, `tail` bytes of the caller's own words, filled on the page-locked side before the
+// call, which go up in the same copy.  tail == 0: only the listed part of the list goes up, and
+// nothing when nothing is hashed.  No wait; nothing of `base` is written.
+int verify_launch(const uint8_t* base, const size_t* offs, const size_t* lens, size_t n, size_t t,
+                  const uint8_t* present, const uint8_t* expected, uint8_t* hwords,
+                  uint8_t* dwords, size_t tail, uint8_t* ok, hipStream_t s) {
+    const size_t items = n * t, o_len = items * 8, o_ord = o_len + items * 8;
+    const size_t hashed = sha_list(
+        lens, n, t, [&](size_t item) { return !present || needs_hash(present[item]); },
+        [&](size_t k, size_t i, size_t cs) { return base + offs[k] + i * cs; },
+        reinterpret_cast<uint64_t*>(hwords), reinterpret_cast<uint64_t*>(hwords + o_len),
+        reinterpret_cast<uint32_t*>(hwords + o_ord));
+    const size_t up = tail ? verify_list_bytes(items) + tail : hashed ? o_ord + hashed * 4 : 0;
+    if (up) HIP_TRY(hipMemcpyAsync(dwords, hwords, up, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(ok, 0, items, s));
+    if (hashed) {
+        ShaParams h{};
+        h.ptrs = reinterpret_cast<const uint64_t*>(dwords);
+        h.lens = reinterpret_cast<const uint64_t*>(dwords + o_len);
+        h.n_parts = uint32_t(items);
+        h.n_chunks = 1;
+        h.expected = expected;
+        h.ok = ok;
+        h.items = reinterpret_cast<const uint32_t*>(dwords + o_ord);
+        h.n_items = uint32_t(hashed);
+        const hipError_t e = launch_sha256(h, true, s);
+        if (e != hipSuccess) return hip_fail(e, "launch_sha256 (ragged verify)");
+    }
+    return CEC_OK;
+}
+
 // The verification half of the ragged read side for a checked layout of t chunks per part: on `s`
-// the SHA-256 list launch in verify mode over the chunks that need hashing (present null: all of
-// them; ok and expected indexed by k*t+i), then the readback of the flags, the one wait.
+// the verification (verify_launch), then the readback of the flags, the one wait.
 // `verified` is written once they are back: the kernel's flag for a hashed chunk, 1 for a
 // CEC_PRESENT_VERIFIED one, 0 for an absent one.  Nothing of `base` is written.
 int verify_ragged(const uint8_t* base, const size_t* offs, const size_t* lens, size_t n, size_t t,
                   const uint8_t* present, const uint8_t* expected, uint8_t* verified,
                   hipStream_t s) {
     const size_t items = n * t;
-    // [ptrs u64 x items][lens u64 x items][order u32 x items][ok u8 x items]
-    const size_t o_len = items * 8, o_ord = o_len + items * 8, o_ok = o_ord + items * 4,
-                 bytes = o_ok + items;
+    // [the SHA-256 list][ok u8 x items]
+    const size_t o_ok = verify_list_bytes(items), bytes = o_ok + items;
     Scratch sc;  // released on s behind the readback
     CEC_TRY(sc.acquire(bytes, s));
     uint8_t* ok = sc.dev() + o_ok;
-    HIP_TRY(hipMemsetAsync(ok, 0, items, s));
-    const size_t hashed = sha_list(
-        lens, n, t, [&](size_t item) { return !present || needs_hash(present[item]); },
-        [&](size_t k, size_t i, size_t cs) { return base + offs[k] + i * cs; },
-        reinterpret_cast<uint64_t*>(sc.host()), reinterpret_cast<uint64_t*>(sc.host() + o_len),
-        reinterpret_cast<uint32_t*>(sc.host() + o_ord));
-    if (hashed) {
-        HIP_TRY(hipMemcpyAsync(sc.dev(), sc.host(), o_ord + hashed * 4, hipMemcpyHostToDevice, s));
-        ShaParams h{};
-        h.ptrs = reinterpret_cast<const uint64_t*>(sc.dev());
-        h.lens = reinterpret_cast<const uint64_t*>(sc.dev() + o_len);
-        h.n_parts = uint32_t(items);
-        h.n_chunks = 1;
-        h.expected = expected;
-        h.ok = ok;
-        h.items = reinterpret_cast<const uint32_t*>(sc.dev() + o_ord);
-        h.n_items = uint32_t(hashed);
-        const hipError_t e = launch_sha256(h, true, s);
-        if (e != hipSuccess) return hip_fail(e, "launch_sha256 (ragged verify)");
-    }
+    CEC_TRY(verify_launch(base, offs, lens, n, t, present, expected, sc.host(), sc.dev(), 0, ok, s));
     // the flags come back through the mirror, behind the words that went up
     HIP_TRY(hipMemcpyAsync(sc.host() + o_ok, ok, items, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -377,8 +396,8 @@ int verify_ragged(const uint8_t* base, const size_t* offs, const size_t* lens, s
 // Shared body of cec_read_ragged / cec_resilver_ragged for a checked layout: the verification
 // (verify_ragged), then on `s` the rebuild of every decodable part from its first d verified
 // chunks.
-// No speculative decode beside the verification: the chains of a ragged batch are short and
-// nobody has measured whether it pays (not built).
+// No speculative decode beside the verification: the form without the wait (read_ragged_async)
+// has nothing for one to hide.
 int read_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* lens, size_t n,
                 const uint8_t* present, const uint8_t* expected, uint8_t* verified,
                 int* part_status, bool data_only, hipStream_t s) {
@@ -389,10 +408,99 @@ int read_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* l
     return reconstruct_ragged(c, base, offs, lens, n, pres.data(), data_only, s);
 }
 
-// Every check of cec_read_ragged / cec_resilver_ragged, then the work.
+// cec_read_ragged_async / cec_resilver_ragged_async calls since load, by who planned the decode
+// (cec_ragged_read_stats).
+std::atomic<uint64_t> g_device_planned{0}, g_host_planned{0};
+
+// The most rows a part's record can have: every chunk the mode fills may be missing, but never
+// more than p of them in a part that decodes.
+inline size_t plan_rows(size_t d, size_t p, bool data_only) { return data_only ? std::min(p, d) : p; }
+
+// Whether read_ragged_async covers a batch: the planner kernel's shape, and record offsets
+// (k * slot words) that fit the reconstruct launch's 32-bit part_pat.
+bool device_plan_covers(size_t d, size_t p, size_t n, bool data_only) {
+    if (d > 0xFFFFFFFFull || p > 0xFFFFFFFFull || !decode_plan_covers(uint32_t(d), uint32_t(p)))
+        return false;
+    return n <= 0xFFFFFFFFull / pattern_words(d, plan_rows(d, p, data_only));
+}
+
+// cec_read_ragged_async / cec_resilver_ragged_async for a checked layout and a covered shape
+// (device_plan_covers): verification, decode plan and rebuild of every part queued on `s`, then
+// the copies of the flags and the statuses into the caller's (host) memory.  Nothing here waits
+// for the device: the plan is built there (plan_kernels.hip), one record per part in the part's
+// own slot, and rs_reconstruct_ragged_kernel runs over ALL parts, writing nothing for a part
+// whose record is empty (not decodable, or nothing to rebuild).
+// present, offs and lens are copied into the words' page-locked side before this returns.  Both
+// scratch buffers are released on `s` behind the last copy.
+int read_ragged_async(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* lens, size_t n,
+                      const uint8_t* present, const uint8_t* expected, uint8_t* verified,
+                      int* part_status, bool data_only, hipStream_t s) {
+    const size_t d = c->d, t = c->d + c->p, items = n * t;
+    const size_t rows = plan_rows(d, c->p, data_only), slot = pattern_words(d, rows);
+    // what goes up, in one copy: [the SHA-256 list][units u32 x (n + 1)][parts u32 x 4n]
+    // [part_pat u32 x n][present u8 x items]
+    const size_t o_units = verify_list_bytes(items), o_parts = o_units + (n + 1) * 4,
+                 o_pat = o_parts + n * 16, o_pres = o_pat + n * 4, up_bytes = o_pres + items;
+    // what stays on the device: [records u32 x n * slot][status i32 x n][ok u8 x items]
+    // [verified u8 x items]
+    const size_t o_st = n * slot * 4, o_ok = o_st + n * 4, o_ver = o_ok + items,
+                 dev_bytes = o_ver + items;
+    // every allocation before anything is queued
+    Scratch up, dv;
+    CEC_TRY(up.acquire(up_bytes, s));
+    CEC_TRY(dv.acquire(dev_bytes, s, false));
+    uint8_t* dmat = nullptr;
+    CEC_TRY(c->matrix_device(&dmat));
+
+    uint8_t *h = up.host(), *dw = up.dev();
+    const uint32_t total_units =
+        part_records(offs, lens, nullptr, n, reinterpret_cast<uint32_t*>(h + o_units),
+                     reinterpret_cast<uint32_t*>(h + o_parts));
+    uint32_t* part_pat = reinterpret_cast<uint32_t*>(h + o_pat);
+    for (size_t k = 0; k < n; ++k) part_pat[k] = uint32_t(k * slot);
+    std::memcpy(h + o_pres, present, items);
+    uint8_t* ok = dv.dev() + o_ok;
+    CEC_TRY(verify_launch(base, offs, lens, n, t, present, expected, h, dw, up_bytes - o_units, ok,
+                          s));
+    PlanParams pl{};
+    pl.present = dw + o_pres;
+    pl.ok = ok;
+    pl.matrix = dmat;
+    pl.verified = dv.dev() + o_ver;
+    pl.part_status = reinterpret_cast<int32_t*>(dv.dev() + o_st);
+    pl.records = reinterpret_cast<uint32_t*>(dv.dev());
+    pl.n_parts = uint32_t(n);
+    pl.d = uint32_t(d);
+    pl.p = uint32_t(c->p);
+    pl.slot_words = uint32_t(slot);
+    pl.max_rows = uint32_t(rows);
+    pl.data_only = data_only ? 1u : 0u;
+    hipError_t e = launch_decode_plan(pl, s);
+    if (e != hipSuccess) return hip_fail(e, "launch_decode_plan");
+    RaggedParams a{};
+    a.base = base;
+    a.pat = pl.records;
+    a.units = reinterpret_cast<const uint32_t*>(dw + o_units);
+    a.parts = reinterpret_cast<const uint32_t*>(dw + o_parts);
+    a.part_pat = reinterpret_cast<const uint32_t*>(dw + o_pat);
+    a.n_parts = uint32_t(n);
+    a.total_units = total_units;
+    a.d = uint32_t(d);
+    a.n_rows = uint32_t(rows);
+    e = launch_rs_reconstruct_ragged(a, s);
+    if (e != hipSuccess) return hip_fail(e, "launch_rs_reconstruct_ragged (device plan)");
+    HIP_TRY(hipMemcpyAsync(verified, pl.verified, items, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(part_status, pl.part_status, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    return CEC_OK;
+}
+
+// Every check of cec_read_ragged / cec_resilver_ragged and their _async forms, then the work.
+// async: the no-wait path where the planner kernel covers the shape; other shapes take the
+// synchronous path inside the same call (its wait is verify_ragged's).
 int read_ragged_checked(const cec_codec* cc, uint8_t* base, const size_t* offs, const size_t* lens,
                         size_t n, const uint8_t* present, const uint8_t* expected,
-                        uint8_t* verified, int* part_status, bool data_only, void* stream) {
+                        uint8_t* verified, int* part_status, bool data_only, void* stream,
+                        bool async = false) {
     if (!cc) return CEC_ERR_INVALID_ARGUMENT;
     if (n == 0) return CEC_OK;
     if (!base || !offs || !lens || !present || !expected || !verified || !part_status)
@@ -400,8 +508,16 @@ int read_ragged_checked(const cec_codec* cc, uint8_t* base, const size_t* offs, 
     CEC_TRY(ragged_check(cc->d + cc->p, base, offs, lens, n));
     int dev = 0;
     CEC_TRY(current_device(&dev));
-    return read_ragged(const_cast<cec_codec*>(cc), base, offs, lens, n, present, expected,
-                       verified, part_status, data_only, static_cast<hipStream_t>(stream));
+    cec_codec* c = const_cast<cec_codec*>(cc);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (async && device_plan_covers(c->d, c->p, n, data_only)) {
+        g_device_planned.fetch_add(1, std::memory_order_relaxed);
+        return read_ragged_async(c, base, offs, lens, n, present, expected, verified, part_status,
+                                 data_only, s);
+    }
+    if (async) g_host_planned.fetch_add(1, std::memory_order_relaxed);
+    return read_ragged(c, base, offs, lens, n, present, expected, verified, part_status, data_only,
+                       s);
 }
 
 // Host staged (cec_parts_encode, cec_parts_read, cec_parts_verify): the parts packed into an
@@ -779,6 +895,27 @@ int cec_resilver_ragged(const cec_codec* c, uint8_t* base, const size_t* part_of
                         void* stream) {
     return read_ragged_checked(c, base, part_offsets, chunk_lens, n_parts, present, expected,
                                verified, part_status, false, stream);
+}
+
+int cec_read_ragged_async(const cec_codec* c, uint8_t* base, const size_t* part_offsets,
+                          const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                          const uint8_t* expected, uint8_t* verified, int* part_status,
+                          void* stream) {
+    return read_ragged_checked(c, base, part_offsets, chunk_lens, n_parts, present, expected,
+                               verified, part_status, true, stream, true);
+}
+
+int cec_resilver_ragged_async(const cec_codec* c, uint8_t* base, const size_t* part_offsets,
+                              const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                              const uint8_t* expected, uint8_t* verified, int* part_status,
+                              void* stream) {
+    return read_ragged_checked(c, base, part_offsets, chunk_lens, n_parts, present, expected,
+                               verified, part_status, false, stream, true);
+}
+
+void cec_ragged_read_stats(uint64_t* device_planned, uint64_t* host_planned) {
+    if (device_planned) *device_planned = g_device_planned.load();
+    if (host_planned) *host_planned = g_host_planned.load();
 }
 
 int cec_parts_read(const cec_codec* cc, uint8_t* const* shards, const size_t* chunk_lens,

@@ -256,6 +256,31 @@ pub mod sys {
             part_status: *mut c_int,
             stream: *mut c_void,
         ) -> c_int;
+        pub fn cec_read_ragged_async(
+            codec: *const cec_codec,
+            base: *mut u8,
+            part_offsets: *const usize,
+            chunk_lens: *const usize,
+            n_parts: usize,
+            present: *const u8,
+            expected: *const u8,
+            verified: *mut u8,
+            part_status: *mut c_int,
+            stream: *mut c_void,
+        ) -> c_int;
+        pub fn cec_resilver_ragged_async(
+            codec: *const cec_codec,
+            base: *mut u8,
+            part_offsets: *const usize,
+            chunk_lens: *const usize,
+            n_parts: usize,
+            present: *const u8,
+            expected: *const u8,
+            verified: *mut u8,
+            part_status: *mut c_int,
+            stream: *mut c_void,
+        ) -> c_int;
+        pub fn cec_ragged_read_stats(device_planned: *mut u64, host_planned: *mut u64);
         pub fn cec_encode_batch(
             codec: *const cec_codec,
             batch: *const cec_part_batch,
@@ -1120,6 +1145,57 @@ pub unsafe fn read_ragged(
         stream,
     ))?;
     Ok((verified, status))
+}
+
+/// `cec_read_ragged_async` (`resilver` false) / `cec_resilver_ragged_async` (true):
+/// [`read_ragged`] without the wait.  The decode is planned on the device, so the call only
+/// queues work on `stream`; copies queued there fill `verified` (`n * (d+p)` bytes) and
+/// `part_status` (`n` ints).  Only page-locked outputs keep the call from blocking.
+///
+/// # Safety
+/// As [`read_ragged`]; `verified` and `part_status` must point to host memory of those sizes
+/// that stays allocated, and is not read, until the work queued on `stream` is done.
+pub unsafe fn read_ragged_async(
+    codec: &ReedSolomon,
+    base: *mut u8,
+    part_offsets: &[usize],
+    chunk_lens: &[usize],
+    present: &[u8],
+    expected: *const u8,
+    verified: *mut u8,
+    part_status: *mut c_int,
+    resilver: bool,
+    stream: *mut c_void,
+) -> Result<(), CecError> {
+    let t = codec.data_shard_count() + codec.parity_shard_count();
+    let n = chunk_lens.len();
+    if part_offsets.len() != n || present.len() != n * t {
+        return Err(CecError::Engine(EngineError {
+            code: 101,
+            message: "part_offsets, chunk_lens and present differ in length".to_string(),
+        }));
+    }
+    let call = if resilver { sys::cec_resilver_ragged_async } else { sys::cec_read_ragged_async };
+    check(call(
+        codec.raw,
+        base,
+        part_offsets.as_ptr(),
+        chunk_lens.as_ptr(),
+        n,
+        present.as_ptr(),
+        expected,
+        verified,
+        part_status,
+        stream,
+    ))
+}
+
+/// `*_ragged_async` calls since load by who planned the decode, process-wide
+/// (`cec_ragged_read_stats`): (device planned, host planned: shapes outside d <= 32, p <= 8).
+pub fn ragged_read_stats() -> (u64, u64) {
+    let (mut device, mut host) = (0u64, 0u64);
+    unsafe { sys::cec_ragged_read_stats(&mut device, &mut host) };
+    (device, host)
 }
 
 /// `cec_parts_read`: the read counterpart of [`parts_encode`].  `shards[k * (d+p) + i]` is a

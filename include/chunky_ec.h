@@ -29,7 +29,8 @@
  *   parity in regions of their own cec_encode_hash_split, and with slots in flight the ragged
  *   write pipeline cec_parts_pipeline_*, chunky_ec_parts.h), cec_parts_read / cec_read_ragged (read),
  *   cec_parts_read / cec_resilver_ragged (resilver), cec_parts_verify / cec_verify_ragged
- *   (verify).
+ *   (verify); cec_read_ragged_async / cec_resilver_ragged_async are the device-resident read
+ *   and resilver with no wait inside the call.
  *
  * Conventions
  *   - Plain pointers and sizes only; every buffer is owned by the caller.
@@ -429,6 +430,34 @@ int cec_resilver_ragged(const cec_codec* codec, uint8_t* base, const size_t* par
                         const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
                         const uint8_t* expected, uint8_t* verified, int* part_status,
                         void* stream);
+
+/* cec_read_ragged / cec_resilver_ragged without the wait: same arguments, checks (in the same
+ * order, before any device use), meanings and results, but the decode is planned on the device
+ * from the verification's flags, so the call only queues work on `stream` (one upload, the
+ * verification, the plan, the rebuild over all parts, two copies back) and returns.  present,
+ * part_offsets and chunk_lens are copied before the call returns.  The one difference for the
+ * caller: verified (n_parts*(d+p)) and part_status (n_parts) are HOST outputs written by copies
+ * queued on `stream`: valid once that work is done, untouched before then and when the call
+ * returns an error; they must stay allocated until then.  Only page-locked outputs
+ * (cec_host_alloc) keep the call from blocking: pageable ones give the same results, but the
+ * copy into them may wait for the stream inside the call.  A codec's first call on a device also
+ * allocates (its coding matrix's device copy, scratch buffers).  An allocation failure returns
+ * CEC_ERR_OUT_OF_MEMORY before anything is queued.
+ * The device planner covers d <= 32 and p <= 8 (every compiled shape).  Other shapes take
+ * cec_read_ragged's path inside the same call, its wait included: same results, but the call
+ * blocks and the outputs are written before it returns.
+ * cec_ragged_read_stats: _async calls since load by who planned the decode, process-wide (either
+ * pointer may be null); a call counts as host_planned when its shape fell outside the planner's
+ * scope. */
+int cec_read_ragged_async(const cec_codec* codec, uint8_t* base, const size_t* part_offsets,
+                          const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                          const uint8_t* expected, uint8_t* verified, int* part_status,
+                          void* stream);
+int cec_resilver_ragged_async(const cec_codec* codec, uint8_t* base, const size_t* part_offsets,
+                              const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                              const uint8_t* expected, uint8_t* verified, int* part_status,
+                              void* stream);
+void cec_ragged_read_stats(uint64_t* device_planned, uint64_t* host_planned);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Host-staged write pipeline (FileWriteBuilder::write's part loop, writer.rs:166-231)      */

@@ -41,6 +41,13 @@ All arms' rebuilt chunks must equal the erased ones (asserted).
 
 --device --read: 4096 x RS(10,4) x 64 KiB, two erasures per part, device resident:
 cec_reconstruct_ragged with uniform lengths against cec_reconstruct_batch on the same bytes.
+Then cec_read_ragged against cec_read_ragged_async (the decode planned on the device, no wait in
+the call) on that batch and on the seeded files as device-resident RS(10,4) and RS(3,2) parts
+with one data chunk per part erased: (a) one call over all parts, the interval between two stream
+events and the host's time inside the call; (b) the parts in two halves on two streams from one
+thread, wall time to the second synchronise.  Arms alternate after a warm-up; the rebuilt bytes,
+flags and statuses must be equal between the arms (asserted).  The async form counts as a gain
+in (b) only if its worst repeat is below the synchronous form's best.
 
 --verify: the scrub side on the same seeded files and shapes.  Every part is stored as the oracle
 encodes it and every one of its d + p chunks is hashed and compared with its digest:
@@ -608,6 +615,169 @@ def device_read(args):
                       "ratio": ratio}))
 
 
+def _ranges(ms):
+    return {k: [min(v), max(v)] for k, v in ms.items()}
+
+
+def read_async_arms(args, name, rs, buf, start, want, offs, lens, flags, dexp):
+    """cec_read_ragged against cec_read_ragged_async on one device-resident batch (`start`: the
+    buffer with the erased chunks zeroed, `want`: what a read must leave).  (a) one call over
+    all parts: the interval between two stream events around it and the host's wall time inside
+    the call.  (b) the parts cut into two halves on two streams from one thread: wall time from
+    before the first call to after the second stream's synchronise.  Arms alternate after a
+    warm-up; every run's buffer, flags and statuses are compared with `want` and between arms."""
+    n, t = len(lens), rs.total_shard_count()
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    h = n // 2
+    halves = [(0, h), (h, n)]
+    ver = ce.HostBuffer(n * t)
+    st = ce.HostBuffer(n * 4)
+
+    def call(use_async, lo, hi, stream):
+        pres = flags[lo:hi].tobytes()
+        exp = dexp.data_ptr() + lo * t * 32
+        if use_async:
+            ce.read_ragged_async(rs, buf.data_ptr(), offs[lo:hi], lens[lo:hi], pres, exp,
+                                 ver.array[lo * t:hi * t], st.array[lo * 4:hi * 4], stream)
+        else:
+            v, s = ce.read_ragged(rs, buf.data_ptr(), offs[lo:hi], lens[lo:hi], pres, exp, stream)
+            ver.array[lo * t:hi * t] = np.frombuffer(v, np.uint8)
+            st.array[lo * 4:hi * 4] = np.array(s, np.int32).view(np.uint8)
+
+    answers = {}
+
+    def settle(use_async):
+        """After a run: the buffer against `want`, the outputs against the other arm's."""
+        assert torch.equal(buf, want), f"{name}: rebuilt bytes differ (async={use_async})"
+        out = (ver.array.tobytes(), st.array.tobytes())
+        assert answers.setdefault("out", out) == out, f"{name}: flags or statuses differ"
+        assert (st.array.view(np.int32) == ce.OK).all()
+
+    def reset():
+        buf.copy_(start)
+        ver.array[:] = 0xEE
+        st.array[:] = 0xEE
+        torch.cuda.synchronize()
+
+    def single(use_async):
+        reset()
+        s = streams[0]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(s)
+        t0 = time.perf_counter()
+        call(use_async, 0, n, s)
+        t1 = time.perf_counter()
+        e1.record(s)
+        s.synchronize()
+        settle(use_async)
+        return e0.elapsed_time(e1), (t1 - t0) * 1e3
+
+    def pair(use_async):
+        reset()
+        t0 = time.perf_counter()
+        for (lo, hi), s in zip(halves, streams):
+            call(use_async, lo, hi, s)
+        for s in streams:
+            s.synchronize()
+        t1 = time.perf_counter()
+        settle(use_async)
+        return (t1 - t0) * 1e3
+
+    for use_async in (False, True):  # warm-up: code objects, scratch buffers, the codec's copies
+        single(use_async)
+        pair(use_async)
+    ms = {k: [] for k in ("sync_event", "async_event", "sync_call", "async_call", "sync_pair",
+                          "async_pair")}
+    for rep in range(args.repeats):
+        for use_async, arm in ((False, "sync"), (True, "async")):
+            ev, wall = single(use_async)
+            ms[arm + "_event"].append(ev)
+            ms[arm + "_call"].append(wall)
+        for use_async, arm in ((False, "sync"), (True, "async")):
+            ms[arm + "_pair"].append(pair(use_async))
+    spread = max(max(v) - min(v) for v in ms.values())
+    gain = max(ms["async_pair"]) < min(ms["sync_pair"])
+    r = _ranges(ms)
+    print(f"== read, sync against async: {name}, {n} parts, chunk lengths {min(lens)}-{max(lens)} B")
+    for k in ms:
+        print(f"   {k}: " + "  ".join(f"{x:.3f}" for x in ms[k]) +
+              f" ms   range {r[k][0]:.3f}-{r[k][1]:.3f}")
+    print(f"   (a) one call: event interval async / sync (best) "
+          f"{min(ms['async_event']) / min(ms['sync_event']):.3f}; host time inside the call "
+          f"sync {r['sync_call'][0]:.3f}-{r['sync_call'][1]:.3f} ms, "
+          f"async {r['async_call'][0]:.3f}-{r['async_call'][1]:.3f} ms")
+    print(f"   (b) two halves, two streams, one thread: sync {r['sync_pair'][0]:.3f}-"
+          f"{r['sync_pair'][1]:.3f} ms, async {r['async_pair'][0]:.3f}-{r['async_pair'][1]:.3f} ms; "
+          f"largest spread within an arm {spread:.3f} ms -> async's worst below sync's best: {gain}",
+          flush=True)
+    return {"ms": ms, "spread_ms": spread, "async_pair_gain": gain}
+
+
+def device_read_async(args):
+    """The arms of read_async_arms on --device --read's batch and on the tool's own files as
+    device-resident RS(10,4) and RS(3,2) parts with data chunk k % d of part k erased."""
+    dev = torch.device("cuda", 0)
+    results = {}
+    # --device --read's batch
+    d, p, n, L = 10, 4, 4096, 65536
+    t = d + p
+    rs = ce.ReedSolomon(d, p)
+    full = torch.zeros((n, t, L), dtype=torch.uint8, device=dev)
+    dexp = torch.zeros((n, t, 32), dtype=torch.uint8, device=dev)
+    batch = ce.PartBatch.from_tensor(full, L)
+    ce.fill_synthetic(batch, d, 1)
+    ce.encode_hash_batch(rs, batch, dexp.data_ptr())
+    flags = np.ones((n, t), np.uint8)
+    for k in range(n):
+        flags[k, [k % d, (k + 3) % t if (k + 3) % t != k % d else (k + 4) % t]] = 0
+    gone = torch.from_numpy(flags == 0).to(dev)
+    start = full.clone()
+    start[gone] = 0
+    want = start.clone()  # a read rebuilds the data chunks and leaves missing parity alone
+    want[:, :d] = full[:, :d]
+    offs, total = ce.ragged_layout(t, [L] * n)
+    buf = start.clone()
+    results["uniform_10_4_64k"] = read_async_arms(
+        args, f"{n} x RS({d},{p}) x {L} B, two erasures per part", rs, buf.view(-1),
+        start.view(-1), want.view(-1), offs, [L] * n, flags, dexp)
+    del full, start, want, buf, gone, dexp
+    pool, files = make_files(args.files)
+    for d, p in ((10, 4), (3, 2)):
+        t = d + p
+        rs = ce.ReedSolomon(d, p)
+        parts = cut_parts(files, d)
+        n = len(parts)
+        lens = [(ln + d - 1) // d for _, ln in parts]
+        offs, total = ce.ragged_layout(t, lens)
+        host = np.zeros(total, np.uint8)
+        for (o, ln), off, L in zip(parts, offs, lens):
+            cs = ce.ragged_stride(L)
+            for j in range(d):
+                have = max(0, min(L, ln - j * L))
+                host[off + j * cs:off + j * cs + have] = pool[o + j * L:o + j * L + have]
+        want = torch.from_numpy(host).to(dev)
+        del host
+        dexp = torch.zeros((n, t, 32), dtype=torch.uint8, device=dev)
+        ce.encode_hash_ragged(rs, want.data_ptr(), offs, lens, dexp.data_ptr())
+        torch.cuda.synchronize()
+        flags = np.ones((n, t), np.uint8)
+        start = want.clone()
+        for k, (off, L) in enumerate(zip(offs, lens)):
+            flags[k, k % d] = 0
+            at = off + (k % d) * ce.ragged_stride(L)
+            start[at:at + L] = 0
+        buf = start.clone()
+        results[f"mixed_{d}_{p}"] = read_async_arms(
+            args, f"{len(files)} files as RS({d},{p}) parts, one data chunk per part erased", rs,
+            buf, start, want, offs, lens, flags, dexp)
+        del want, start, buf, dexp
+    print(json.dumps({"tool": "small_files_bench", "mode": "device-read-async",
+                      "results": {k: {"ranges_ms": _ranges(v["ms"]), "spread_ms": v["spread_ms"],
+                                      "async_pair_gain": v["async_pair_gain"]}
+                                  for k, v in results.items()},
+                      "read_stats": ce.ragged_read_stats()}))
+
+
 KNOB = "CEC_RAGGED_FUSED"
 
 
@@ -791,7 +961,11 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     if args.device:
-        (device_read if args.read else device_mode)(args)
+        if args.read:
+            device_read(args)
+            device_read_async(args)
+        else:
+            device_mode(args)
     elif args.verify:
         host_verify(args)
     else:
