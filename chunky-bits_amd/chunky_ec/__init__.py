@@ -153,6 +153,26 @@ _sig("cec_read_ragged_async", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp,
                                ctypes.POINTER(ctypes.c_int), _vp])
 _sig("cec_resilver_ragged_async", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp, _u8p,
                                    ctypes.POINTER(ctypes.c_int), _vp])
+_sig("cec_read_ragged_packed_async", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp, ctypes.c_int,
+                                      _u8p, ctypes.POINTER(ctypes.c_int), _vp, ctypes.c_size_t,
+                                      _szp, _vp])
+_sig("cec_parts_reader_new", [_vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
+                              ctypes.POINTER(_vp)])
+_sig("cec_parts_reader_free", [_vp], None)
+_sig("cec_parts_reader_depth", [_vp], ctypes.c_size_t)
+_sig("cec_parts_reader_acquire", [_vp, _szp, ctypes.POINTER(_u8p)])
+_sig("cec_parts_reader_submit", [_vp, ctypes.c_size_t, _szp, ctypes.c_size_t, _u8p, _u8p])
+_sig("cec_parts_reader_submit_from", [_vp, ctypes.c_size_t, ctypes.POINTER(_u8p), _szp,
+                                      ctypes.c_size_t, _u8p, _u8p])
+_sig("cec_parts_reader_wait", [_vp, ctypes.c_size_t, ctypes.POINTER(_u8p),
+                               ctypes.POINTER(ctypes.POINTER(ctypes.c_int)), ctypes.POINTER(_u8p),
+                               ctypes.POINTER(_szp), _szp])
+_sig("cec_parts_reader_scatter", [_vp, ctypes.c_size_t, ctypes.POINTER(_u8p)])
+_sig("cec_parts_reader_query", [_vp, ctypes.c_size_t])
+_sig("cec_parts_reader_drain", [_vp])
+_sig("cec_parts_reader_stats", [_vp, ctypes.POINTER(ctypes.c_uint64),
+                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
+     None)
 _sig("cec_ragged_read_stats", [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
      None)
 _sig("cec_parts_read", [_vp, ctypes.POINTER(_u8p), _szp, ctypes.c_size_t, _u8p, _u8p, ctypes.c_int,
@@ -816,6 +836,34 @@ def resilver_ragged_async(codec: ReedSolomon, base_ptr: int, part_offsets: Seque
                                  chunk_lens, present, expected_ptr, verified, part_status, stream)
 
 
+def read_ragged_packed_async(codec: ReedSolomon, base_ptr: int, part_offsets: Sequence[int],
+                             chunk_lens: Sequence[int], present, expected_ptr: int, data_only: bool,
+                             verified, part_status, rebuilt_ptr: int, rebuilt_cap: int,
+                             rebuilt_offsets, stream=None) -> None:
+    """:func:`read_ragged_async` (``data_only``) / :func:`resilver_ragged_async` with a packed
+    return (``cec_read_ragged_packed_async``): every rebuilt chunk also lands in the device region
+    at ``rebuilt_ptr`` (``rebuilt_cap`` bytes), dense and in part order, and ``rebuilt_offsets``
+    (a host buffer of ``n+1`` ``size_t``) receives the parts' byte offsets into it through a copy
+    queued on the stream, like ``verified`` and ``part_status``.  The r-th rebuilt chunk of part k
+    is ``L_k`` bytes at ``rebuilt_offsets[k] + r * ragged_stride(L_k)``."""
+    offs, lens, n = _ragged_args(part_offsets, chunk_lens)
+    items = n * codec.total_shard_count()
+    pres = bytes(present)
+    assert len(pres) == items
+    if n and (_out_nbytes(verified) < items or
+              _out_nbytes(part_status) < n * ctypes.sizeof(ctypes.c_int) or
+              _out_nbytes(rebuilt_offsets) < (n + 1) * ctypes.sizeof(ctypes.c_size_t)):
+        raise ValueError("verified needs n*(d+p) bytes, part_status n C ints and rebuilt_offsets "
+                         "n+1 size_t")
+    ver = ctypes.cast(_addr(verified), _u8p) if n else _u8p()
+    st = ctypes.cast(_addr(part_status), ctypes.POINTER(ctypes.c_int)) if n else None
+    ro = ctypes.cast(_addr(rebuilt_offsets), _szp)
+    _check(_lib.cec_read_ragged_packed_async(
+        codec.handle, base_ptr, offs, lens, n, ctypes.cast(ctypes.c_char_p(pres), _u8p),
+        expected_ptr, 1 if data_only else 0, ver, st, rebuilt_ptr, rebuilt_cap, ro,
+        _stream_ptr(stream)))
+
+
 def ragged_read_stats():
     """(device_planned, host_planned): ``*_ragged_async`` calls since load by who planned the
     decode (cec_ragged_read_stats); host_planned counts the shapes outside the device planner's
@@ -840,6 +888,20 @@ def parts_read(codec: ReedSolomon, parts: Sequence[Sequence], expected: Sequence
     n = len(parts)
     if n == 0:
         return [], b"", []
+    lens, pres, exp, slots, ptrs = _parts_read_args(d, t, parts, expected, data_only)
+    verified = (ctypes.c_uint8 * (n * t))()
+    status = (ctypes.c_int * n)()
+    _check(_lib.cec_parts_read(codec.handle, ptrs, (ctypes.c_size_t * n)(*lens), n,
+                               ctypes.cast(ctypes.c_char_p(pres), _u8p),
+                               ctypes.cast(ctypes.c_char_p(exp), _u8p), 1 if data_only else 0,
+                               verified, status))
+    return _parts_read_result(d, t, parts, lens, slots, verified, status, data_only)
+
+
+def _parts_read_args(d, t, parts, expected, data_only):
+    """:func:`parts_read`'s arguments in the C call's form: (chunk lengths, loaded flags, digest
+    bytes, the engine's chunk slots by (k, i), their pointer array)."""
+    n = len(parts)
     lens, flags, ptrs, slots = [], bytearray(n * t), [], {}
     for k, chunks in enumerate(parts):
         if len(chunks) != t:
@@ -864,14 +926,11 @@ def parts_read(codec: ReedSolomon, parts: Sequence[Sequence], expected: Sequence
     exp = b"".join(bytes(h) for part in expected for h in part)
     if len(exp) != n * t * 32:
         raise ValueError("expected: d+p digests of 32 bytes per part")
-    verified = (ctypes.c_uint8 * (n * t))()
-    status = (ctypes.c_int * n)()
-    pres = bytes(flags)
-    _check(_lib.cec_parts_read(codec.handle, (_u8p * (n * t))(*ptrs),
-                               (ctypes.c_size_t * n)(*lens), n,
-                               ctypes.cast(ctypes.c_char_p(pres), _u8p),
-                               ctypes.cast(ctypes.c_char_p(exp), _u8p), 1 if data_only else 0,
-                               verified, status))
+    return lens, bytes(flags), exp, slots, (_u8p * max(n * t, 1))(*ptrs)
+
+
+def _parts_read_result(d, t, parts, lens, slots, verified, status, data_only):
+    """:func:`parts_read`'s result from the flags, the statuses and the filled chunk slots."""
     out = []
     for k, chunks in enumerate(parts):
         row = []
@@ -884,7 +943,7 @@ def parts_read(codec: ReedSolomon, parts: Sequence[Sequence], expected: Sequence
             else:
                 row.append(None)
         out.append(row)
-    return out, bytes(verified), list(status)
+    return out, bytes(verified), [int(x) for x in status]
 
 
 def verify_ragged(total_shards: int, base_ptr: int, part_offsets: Sequence[int],
@@ -1109,6 +1168,114 @@ class PartsPipeline:
 
     def drain(self) -> None:
         _check(_lib.cec_parts_pipeline_drain(self._h))
+
+
+class PartsReader:
+    """cec_parts_reader: :func:`parts_read` with `depth` slots in flight, only the rebuilt chunks
+    coming back, packed.
+
+    Per batch: ``slot, stage = rd.acquire()`` (a writable numpy view of the slot's pinned staging
+    region), then either place the loaded chunks at the :func:`ragged_layout` ``(d+p, chunk_lens)``
+    offsets and ``rd.submit(slot, chunk_lens, present, expected)``, or
+    ``rd.submit_from(slot, parts, expected)`` with ``parts`` in :func:`parts_read`'s form (the
+    engine packs); later ``verified, status, rebuilt, offsets = rd.wait(slot)``: numpy views of
+    pinned memory, valid until the slot is acquired again, the r-th rebuilt chunk of part k at
+    ``rebuilt[offsets[k] + r * ragged_stride(L_k):][:L_k]``; or ``rd.collect(slot)``, which gives
+    :func:`parts_read`'s result through ``cec_parts_reader_scatter``.
+    """
+
+    def __init__(self, codec: ReedSolomon, slot_bytes: int, max_parts: int, depth: int = 2,
+                 data_only: bool = True):
+        h = _vp()
+        _check(_lib.cec_parts_reader_new(codec.handle, slot_bytes, max_parts, depth,
+                                         1 if data_only else 0, ctypes.byref(h)))
+        self._h = h
+        self.codec = codec  # keep the codec alive
+        self.d, self.p = codec.data_shard_count(), codec.parity_shard_count()
+        self.slot_bytes = slot_bytes
+        self.max_parts = max_parts
+        self.depth = depth
+        self.data_only = data_only
+        self._batch = [None] * depth  # submit_from's (parts, lens, slots, pointer array)
+
+    def __del__(self, _free=_lib.cec_parts_reader_free):
+        h = getattr(self, "_h", None)
+        if h:
+            _free(h)
+            self._h = None
+
+    def acquire(self):
+        import numpy as np
+        slot = ctypes.c_size_t(0)
+        ptr = _u8p()
+        _check(_lib.cec_parts_reader_acquire(self._h, ctypes.byref(slot), ctypes.byref(ptr)))
+        self._batch[slot.value] = None
+        return slot.value, np.ctypeslib.as_array(ptr, shape=(self.slot_bytes,))
+
+    def submit(self, slot: int, chunk_lens: Sequence[int], present, expected) -> None:
+        """``present``: the ``n*(d+p)`` loaded flags; ``expected``: ``n*(d+p)*32`` digest bytes."""
+        n = len(chunk_lens)
+        lens = (ctypes.c_size_t * max(n, 1))(*chunk_lens)
+        pres, exp = bytes(present), bytes(expected)
+        if len(pres) != n * (self.d + self.p) or len(exp) != len(pres) * 32:
+            raise ValueError("present needs n*(d+p) flags and expected 32 bytes for each")
+        _check(_lib.cec_parts_reader_submit(self._h, slot, lens, n,
+                                            ctypes.cast(ctypes.c_char_p(pres), _u8p),
+                                            ctypes.cast(ctypes.c_char_p(exp), _u8p)))
+
+    def submit_from(self, slot: int, parts: Sequence[Sequence], expected: Sequence) -> None:
+        """``parts`` and ``expected`` as in :func:`parts_read`."""
+        n = len(parts)
+        lens, pres, exp, slots, arr = _parts_read_args(self.d, self.d + self.p, parts, expected,
+                                                       self.data_only)
+        _check(_lib.cec_parts_reader_submit_from(
+            self._h, slot, arr, (ctypes.c_size_t * max(n, 1))(*lens), n,
+            ctypes.cast(ctypes.c_char_p(pres), _u8p), ctypes.cast(ctypes.c_char_p(exp), _u8p)))
+        self._batch[slot] = (parts, lens, slots, arr)
+
+    def wait(self, slot: int):
+        import numpy as np
+        ver, reb = _u8p(), _u8p()
+        st = ctypes.POINTER(ctypes.c_int)()
+        off = _szp()
+        n = ctypes.c_size_t(0)
+        _check(_lib.cec_parts_reader_wait(self._h, slot, ctypes.byref(ver), ctypes.byref(st),
+                                          ctypes.byref(reb), ctypes.byref(off), ctypes.byref(n)))
+        k, t = n.value, self.d + self.p
+        verified = np.ctypeslib.as_array(ver, shape=(max(k * t, 1),))[: k * t]
+        status = np.ctypeslib.as_array(st, shape=(max(k, 1),))[:k]
+        offsets = np.ctypeslib.as_array(off, shape=(k + 1,))
+        total = int(offsets[k])
+        rebuilt = np.ctypeslib.as_array(reb, shape=(max(total, 1),))[:total]
+        return verified, status, rebuilt, offsets
+
+    def collect(self, slot: int):
+        """After :meth:`submit_from`: waits, scatters the rebuilt chunks into the batch's chunk
+        slots (``cec_parts_reader_scatter``) and returns what :func:`parts_read` returns."""
+        if self._batch[slot] is None:
+            raise ValueError("collect needs a batch queued with submit_from on this slot")
+        parts, lens, slots, arr = self._batch[slot]
+        verified, status, _, _ = self.wait(slot)
+        _check(_lib.cec_parts_reader_scatter(self._h, slot, arr))
+        return _parts_read_result(self.d, self.d + self.p, parts, lens, slots, verified, status,
+                                  self.data_only)
+
+    def query(self, slot: int) -> bool:
+        """True when the slot's batch is complete (never blocks)."""
+        r = _lib.cec_parts_reader_query(self._h, slot)
+        if r < 0 or r > 1:
+            raise Error(r)
+        return bool(r)
+
+    def drain(self) -> None:
+        _check(_lib.cec_parts_reader_drain(self._h))
+
+    def stats(self):
+        """(bytes_up, bytes_down, tail_copies) since the reader was made."""
+        up, down, tails = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _lib.cec_parts_reader_stats(self._h, ctypes.byref(up), ctypes.byref(down),
+                                    ctypes.byref(tails))
+        return up.value, down.value, tails.value
 
 
 class ReadPipeline:

@@ -45,6 +45,27 @@ int hip_fail(hipError_t e, const char* what);  // sets the last error; CEC_ERR_H
 
 int current_device(int* dev);
 
+// Makes `device` current for a scope and restores the caller's device on every exit path.
+class OnDevice {
+   public:
+    explicit OnDevice(int device) {
+        err_ = hipGetDevice(&prev_);
+        if (err_ == hipSuccess && prev_ != device) {
+            err_ = hipSetDevice(device);
+            switched_ = err_ == hipSuccess;
+        }
+    }
+    ~OnDevice() {
+        if (switched_) (void)hipSetDevice(prev_);
+    }
+    hipError_t status() const { return err_; }
+
+   private:
+    int prev_ = 0;
+    bool switched_ = false;
+    hipError_t err_ = hipSuccess;
+};
+
 constexpr size_t kChunkAlign = 256;
 inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline bool aligned16(const void* p, size_t a, size_t b) {
@@ -285,6 +306,25 @@ size_t ragged_words_bytes(size_t t, size_t n);
 int ragged_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, uint8_t* parity,
                   const size_t* poffs, const size_t* lens, size_t n, uint8_t* digests,
                   hipStream_t s, uint8_t* hwords = nullptr, uint8_t* dwords = nullptr);
+
+
+// ---- The ragged read (ragged.cpp), as the read pipeline (ragged_read_pipeline.cpp) shares it. ----
+
+// cec_ragged_layout behind its pointer checks.
+int ragged_layout(size_t t, const size_t* lens, size_t n, size_t* offs, size_t* total);
+// Whether a read fills slot i of a part when it is not among the verified chunks.
+inline bool fills_slot(size_t i, size_t d, bool data_only) { return i < d || !data_only; }
+// The worst case of a packed return (cec_read_ragged_packed_async's bound on rebuilt_cap): the sum
+// of rows * stride(L_k), rows = p, or min(p, d) under data_only.  Nonzero lengths.
+int packed_worst_case(size_t d, size_t p, bool data_only, const size_t* lens, size_t n,
+                      size_t* bytes);
+// Host-staged packing of n parts' loaded chunks into dst at offs, on up to 8 threads.
+void pack_loaded(uint8_t* dst, const size_t* offs, size_t t, const uint8_t* const* shards,
+                 const size_t* chunk_lens, size_t n, const uint8_t* present);
+// Copies of the byte ranges [first, second) (ascending, disjoint) between a pinned staging and a
+// device arena that share their offsets, neighbours merged across small gaps.
+using Spans = std::vector<std::pair<size_t, size_t>>;
+int copy_spans(uint8_t* stage, uint8_t* dbase, const Spans& spans, bool to_device, hipStream_t s);
 
 }  // namespace cec
 

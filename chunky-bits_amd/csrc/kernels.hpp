@@ -166,6 +166,33 @@ struct PlanParams {
 // launch): every compiled shape.
 bool decode_plan_covers(uint32_t d, uint32_t p);
 hipError_t launch_decode_plan(const PlanParams& a, hipStream_t s);
+
+// The packed return of a ragged read (plan_kernels.hip), queued behind the rebuild: everything
+// the rebuild wrote, gathered into `rebuilt` in part order.  records / slot_words / max_rows: the
+// planner's (PlanParams); units / parts / total_units: the whole batch's (RaggedParams), unit_bytes
+// = ragged_unit_bytes(); t = d + p.
+//   ret_off[k] = the sum over the parts before k of n_out * stride(L) bytes (return_plan.hpp),
+//                ret_off[n_parts] = the total;
+//   row r of part k (its chunk records[k][1 + d + r]) = L_k bytes at
+//                rebuilt + ret_off[k] + r * stride(L_k).
+// Bytes between L and the stride are unspecified; nothing at or behind ret_off[n_parts] is
+// written, and that is at most the sum of max_rows * stride(L_k), which the caller's region holds.
+struct ReturnParams {
+    const uint8_t* base;
+    const uint32_t* records;  // [n_parts][slot_words]
+    const uint32_t* units;    // [n_parts + 1]
+    const uint32_t* parts;    // [n_parts][4]
+    uint64_t* ret_off;        // [n_parts + 1]
+    uint8_t* rebuilt;
+    uint64_t unit_bytes;
+    uint32_t n_parts;
+    uint32_t total_units;
+    uint32_t d;
+    uint32_t t;
+    uint32_t slot_words;
+    uint32_t max_rows;
+};
+hipError_t launch_return_plan(const ReturnParams& a, hipStream_t s);
 bool fused_supported(uint32_t d, uint32_t p);
 bool fused_covers(uint32_t d, uint32_t p, uint64_t len);
 hipError_t launch_encode_hash(const FusedParams& a, bool vec16, hipStream_t s);

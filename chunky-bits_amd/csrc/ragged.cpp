@@ -1,12 +1,12 @@
 // ragged.cpp — the ragged half of include/chunky_ec.h: parts of different chunk lengths in one
 // launch sequence (cec_encode_hash_ragged, cec_encode_hash_split, cec_reconstruct_ragged,
 // cec_verify_ragged, cec_read_ragged, cec_resilver_ragged and their _async forms, which plan the
-// decode on the device and never wait) and the host-staged calls on top of
+// decode on the device and never wait, cec_read_ragged_packed_async among them) and the host-staged calls on top of
 // them (cec_parts_encode, cec_parts_read, cec_parts_verify).  Part k's chunk i lies at
 // base + off[k] + i * stride(L_k), stride = L rounded up to 16; the split layout keeps the parity
 // chunks in a region of their own.  Host work only; every step of the path has one home here
-// (the ragged write pipeline, ragged_pipeline.cpp, takes its steps from here through
-// capi_internal.hpp).
+// (the ragged write pipeline, ragged_pipeline.cpp, and the ragged read pipeline,
+// ragged_read_pipeline.cpp, take their steps from here through capi_internal.hpp).
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -29,10 +29,8 @@ size_t cec::ragged_stride(size_t L) {
     return L > SIZE_MAX - (kRaggedAlign - 1) ? 0 : round_up(L, kRaggedAlign);
 }
 
-namespace {
-
 // The packed layout: part k+1 directly behind part k.
-int ragged_layout(size_t t, const size_t* lens, size_t n, size_t* offs, size_t* total) {
+int cec::ragged_layout(size_t t, const size_t* lens, size_t n, size_t* offs, size_t* total) {
     size_t off = 0;
     for (size_t k = 0; k < n; ++k) {
         if (lens[k] == 0) return CEC_EMPTY_SHARD;
@@ -46,6 +44,8 @@ int ragged_layout(size_t t, const size_t* lens, size_t n, size_t* offs, size_t* 
     *total = off;
     return CEC_OK;
 }
+
+namespace {
 
 // Every argument check of a ragged layout of t chunks per part (no device use), the bound on the
 // launch's work units among them.
@@ -416,6 +416,14 @@ std::atomic<uint64_t> g_device_planned{0}, g_host_planned{0};
 // more than p of them in a part that decodes.
 inline size_t plan_rows(size_t d, size_t p, bool data_only) { return data_only ? std::min(p, d) : p; }
 
+// The packed return of read_ragged_async: a device region of `cap` bytes and the host array of
+// n + 1 byte offsets into it.
+struct PackedReturn {
+    uint8_t* rebuilt;
+    size_t cap;
+    size_t* offsets;
+};
+
 // Whether read_ragged_async covers a batch: the planner kernel's shape, and record offsets
 // (k * slot words) that fit the reconstruct launch's 32-bit part_pat.
 bool device_plan_covers(size_t d, size_t p, size_t n, bool data_only) {
@@ -423,6 +431,26 @@ bool device_plan_covers(size_t d, size_t p, size_t n, bool data_only) {
         return false;
     return n <= 0xFFFFFFFFull / pattern_words(d, plan_rows(d, p, data_only));
 }
+
+}  // namespace
+
+// The most a packed return of these (checked, nonzero) chunk lengths can hold: every part with
+// all its rows rebuilt.
+int cec::packed_worst_case(size_t d, size_t p, bool data_only, const size_t* lens, size_t n,
+                           size_t* bytes) {
+    const size_t rows = plan_rows(d, p, data_only);
+    size_t acc = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const size_t cs = ragged_stride(lens[k]);
+        size_t b = 0;
+        if (!cs || __builtin_mul_overflow(rows, cs, &b) || __builtin_add_overflow(acc, b, &acc))
+            return CEC_ERR_INVALID_ARGUMENT;
+    }
+    *bytes = acc;
+    return CEC_OK;
+}
+
+namespace {
 
 // cec_read_ragged_async / cec_resilver_ragged_async for a checked layout and a covered shape
 // (device_plan_covers): verification, decode plan and rebuild of every part queued on `s`, then
@@ -432,9 +460,14 @@ bool device_plan_covers(size_t d, size_t p, size_t n, bool data_only) {
 // whose record is empty (not decodable, or nothing to rebuild).
 // present, offs and lens are copied into the words' page-locked side before this returns.  Both
 // scratch buffers are released on `s` behind the last copy.
+// ret (null: none of this): the packed return.  Behind the rebuild, the scan of the records'
+// returns and the gather of every rebuilt chunk into ret->rebuilt (plan_kernels.hip
+// launch_return_plan), then the copy of the n + 1 offsets into ret->offsets (host).  The caller
+// checked the region against packed_worst_case.
 int read_ragged_async(cec_codec* c, uint8_t* base, const size_t* offs, const size_t* lens, size_t n,
                       const uint8_t* present, const uint8_t* expected, uint8_t* verified,
-                      int* part_status, bool data_only, hipStream_t s) {
+                      int* part_status, bool data_only, hipStream_t s,
+                      const PackedReturn* ret = nullptr) {
     const size_t d = c->d, t = c->d + c->p, items = n * t;
     const size_t rows = plan_rows(d, c->p, data_only), slot = pattern_words(d, rows);
     // what goes up, in one copy: [the SHA-256 list][units u32 x (n + 1)][parts u32 x 4n]
@@ -443,8 +476,10 @@ int read_ragged_async(cec_codec* c, uint8_t* base, const size_t* offs, const siz
                  o_pat = o_parts + n * 16, o_pres = o_pat + n * 4, up_bytes = o_pres + items;
     // what stays on the device: [records u32 x n * slot][status i32 x n][ok u8 x items]
     // [verified u8 x items]
+    // and, with a packed return, [ret_off u64 x (n + 1)] behind them
     const size_t o_st = n * slot * 4, o_ok = o_st + n * 4, o_ver = o_ok + items,
-                 dev_bytes = o_ver + items;
+                 o_ret = round_up(o_ver + items, 8),
+                 dev_bytes = ret ? o_ret + (n + 1) * 8 : o_ver + items;
     // every allocation before anything is queued
     Scratch up, dv;
     CEC_TRY(up.acquire(up_bytes, s));
@@ -489,8 +524,31 @@ int read_ragged_async(cec_codec* c, uint8_t* base, const size_t* offs, const siz
     a.n_rows = uint32_t(rows);
     e = launch_rs_reconstruct_ragged(a, s);
     if (e != hipSuccess) return hip_fail(e, "launch_rs_reconstruct_ragged (device plan)");
+    uint64_t* ret_off = ret ? reinterpret_cast<uint64_t*>(dv.dev() + o_ret) : nullptr;
+    if (ret) {
+        ReturnParams r{};
+        r.base = base;
+        r.records = pl.records;
+        r.units = a.units;
+        r.parts = a.parts;
+        r.ret_off = ret_off;
+        r.rebuilt = ret->rebuilt;
+        r.unit_bytes = ragged_unit_bytes();
+        r.n_parts = uint32_t(n);
+        r.total_units = total_units;
+        r.d = uint32_t(d);
+        r.t = uint32_t(t);
+        r.slot_words = uint32_t(slot);
+        r.max_rows = uint32_t(rows);
+        e = launch_return_plan(r, s);
+        if (e != hipSuccess) return hip_fail(e, "launch_return_plan");
+    }
     HIP_TRY(hipMemcpyAsync(verified, pl.verified, items, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(part_status, pl.part_status, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (ret) {
+        static_assert(sizeof(size_t) == sizeof(uint64_t), "the offsets are copied as they are");
+        HIP_TRY(hipMemcpyAsync(ret->offsets, ret_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    }
     return CEC_OK;
 }
 
@@ -500,12 +558,31 @@ int read_ragged_async(cec_codec* c, uint8_t* base, const size_t* offs, const siz
 int read_ragged_checked(const cec_codec* cc, uint8_t* base, const size_t* offs, const size_t* lens,
                         size_t n, const uint8_t* present, const uint8_t* expected,
                         uint8_t* verified, int* part_status, bool data_only, void* stream,
-                        bool async = false) {
+                        bool async = false, const PackedReturn* ret = nullptr) {
     if (!cc) return CEC_ERR_INVALID_ARGUMENT;
-    if (n == 0) return CEC_OK;
+    if (n == 0) {  // a batch of nothing returns nothing
+        if (ret && ret->offsets) ret->offsets[0] = 0;
+        return CEC_OK;
+    }
     if (!base || !offs || !lens || !present || !expected || !verified || !part_status)
         return CEC_ERR_INVALID_ARGUMENT;
+    if (ret && (!ret->rebuilt || !ret->offsets)) return CEC_ERR_INVALID_ARGUMENT;
     CEC_TRY(ragged_check(cc->d + cc->p, base, offs, lens, n));
+    if (ret) {  // the packed return's own checks, still before any device use
+        size_t worst = 0;
+        if (reinterpret_cast<uintptr_t>(ret->rebuilt) % kRaggedAlign) return CEC_ERR_INVALID_ARGUMENT;
+        if (!device_plan_covers(cc->d, cc->p, n, data_only)) {
+            set_last_error("cec_read_ragged_packed_async: the device planner covers d <= 32 and "
+                           "p <= 8; use cec_read_ragged_async for this shape");
+            return CEC_ERR_INVALID_ARGUMENT;
+        }
+        CEC_TRY(packed_worst_case(cc->d, cc->p, data_only, lens, n, &worst));
+        if (ret->cap < worst) {
+            set_last_error("cec_read_ragged_packed_async: rebuilt_cap is below the batch's worst "
+                           "case, the sum of rows * cec_ragged_stride(L_k)");
+            return CEC_ERR_INVALID_ARGUMENT;
+        }
+    }
     int dev = 0;
     CEC_TRY(current_device(&dev));
     cec_codec* c = const_cast<cec_codec*>(cc);
@@ -513,7 +590,7 @@ int read_ragged_checked(const cec_codec* cc, uint8_t* base, const size_t* offs, 
     if (async && device_plan_covers(c->d, c->p, n, data_only)) {
         g_device_planned.fetch_add(1, std::memory_order_relaxed);
         return read_ragged_async(c, base, offs, lens, n, present, expected, verified, part_status,
-                                 data_only, s);
+                                 data_only, s, ret);
     }
     if (async) g_host_planned.fetch_add(1, std::memory_order_relaxed);
     return read_ragged(c, base, offs, lens, n, present, expected, verified, part_status, data_only,
@@ -569,6 +646,20 @@ void cec::pack_parts(uint8_t* dst, const size_t* offs, size_t d, const uint8_t* 
     });
 }
 
+// The packing of a host-staged read: every loaded chunk (present[k * t + i] != 0) of part k, L_k
+// bytes at shards[k * t + i], to dst + offs[k] + i * stride(L_k).  Only those are read.
+void cec::pack_loaded(uint8_t* dst, const size_t* offs, size_t t, const uint8_t* const* shards,
+                      const size_t* chunk_lens, size_t n, const uint8_t* present) {
+    size_t in_bytes = 0;
+    for (size_t k = 0; k < n; ++k)
+        for (size_t i = 0; i < t; ++i) in_bytes += present[k * t + i] ? chunk_lens[k] : 0;
+    for_parts(n, in_bytes, [&](size_t k) {
+        const size_t L = chunk_lens[k], cs = ragged_stride(L);
+        for (size_t i = 0; i < t; ++i)
+            if (present[k * t + i]) std::memcpy(dst + offs[k] + i * cs, shards[k * t + i], L);
+    });
+}
+
 // The packed split layout: part k+1 directly behind part k in each region.
 int cec::split_layout(size_t d, size_t p, const size_t* lens, size_t n, size_t* doffs,
                       size_t* poffs, size_t* data_bytes, size_t* parity_bytes) {
@@ -576,15 +667,12 @@ int cec::split_layout(size_t d, size_t p, const size_t* lens, size_t n, size_t* 
     return ragged_layout(p, lens, n, poffs, parity_bytes);
 }
 
-namespace {
-
-using Spans = std::vector<std::pair<size_t, size_t>>;
-
 // Copies of the byte ranges [first, second) (ascending, disjoint) between the staging and the
 // device arena, which share their offsets.  Neighbouring ranges share one copy, with what lies
 // between them travelling along, until the gap is worth a copy call of its own (256 KiB: a few
 // microseconds of the link either way).
-int copy_spans(uint8_t* stage, uint8_t* dbase, const Spans& spans, bool to_device, hipStream_t s) {
+int cec::copy_spans(uint8_t* stage, uint8_t* dbase, const Spans& spans, bool to_device,
+                    hipStream_t s) {
     constexpr size_t kGap = size_t(256) << 10;
     for (size_t q = 0; q < spans.size();) {
         const size_t from = spans[q].first;
@@ -597,6 +685,8 @@ int copy_spans(uint8_t* stage, uint8_t* dbase, const Spans& spans, bool to_devic
     }
     return CEC_OK;
 }
+
+namespace {
 
 // One round's place in an arena: the packed layout of its n parts, `stage` (pinned) and `dbase`
 // (device) sharing those offsets, and `dside`, device room for the round's n * t digests, with
@@ -701,9 +791,6 @@ int parts_round(cec_codec* c, Arena& a, const uint8_t* const* bufs, const size_t
     std::memcpy(digests_out, a.out.ptr, n * t * 32);
     return CEC_OK;
 }
-
-// Whether the call fills slot i of a part when it is not among the verified chunks.
-inline bool fills_slot(size_t i, size_t d, bool data_only) { return i < d || !data_only; }
 
 // One round of cec_parts_read: parts [0, n) of these arrays.  The loaded chunks are packed into
 // the arena and moved up, verified and rebuilt as in cec_read_ragged, and only the rebuilt chunks
@@ -895,6 +982,16 @@ int cec_resilver_ragged(const cec_codec* c, uint8_t* base, const size_t* part_of
                         void* stream) {
     return read_ragged_checked(c, base, part_offsets, chunk_lens, n_parts, present, expected,
                                verified, part_status, false, stream);
+}
+
+int cec_read_ragged_packed_async(const cec_codec* c, uint8_t* base, const size_t* part_offsets,
+                                 const size_t* chunk_lens, size_t n_parts, const uint8_t* present,
+                                 const uint8_t* expected, int data_only, uint8_t* verified,
+                                 int* part_status, uint8_t* rebuilt, size_t rebuilt_cap,
+                                 size_t* rebuilt_offsets, void* stream) {
+    const PackedReturn ret{rebuilt, rebuilt_cap, rebuilt_offsets};
+    return read_ragged_checked(c, base, part_offsets, chunk_lens, n_parts, present, expected,
+                               verified, part_status, data_only != 0, stream, true, &ret);
 }
 
 int cec_read_ragged_async(const cec_codec* c, uint8_t* base, const size_t* part_offsets,

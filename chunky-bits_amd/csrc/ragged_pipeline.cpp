@@ -19,27 +19,6 @@ using namespace cec;
 
 namespace {
 
-// Makes `device` current for a scope and restores the caller's device on every exit path.
-class OnDevice {
-   public:
-    explicit OnDevice(int device) {
-        err_ = hipGetDevice(&prev_);
-        if (err_ == hipSuccess && prev_ != device) {
-            err_ = hipSetDevice(device);
-            switched_ = err_ == hipSuccess;
-        }
-    }
-    ~OnDevice() {
-        if (switched_) (void)hipSetDevice(prev_);
-    }
-    hipError_t status() const { return err_; }
-
-   private:
-    int prev_ = 0;
-    bool switched_ = false;
-    hipError_t err_ = hipSuccess;
-};
-
 struct PartsSlot {
     uint8_t *h_data = nullptr, *h_parity = nullptr, *h_dig = nullptr, *h_words = nullptr;  // pinned
     uint8_t *d_data = nullptr, *d_parity = nullptr, *d_dig = nullptr, *d_words = nullptr;

@@ -34,6 +34,11 @@ pub mod sys {
     }
 
     #[repr(C)]
+    pub struct cec_parts_reader {
+        _private: [u8; 0],
+    }
+
+    #[repr(C)]
     pub struct cec_multi {
         _private: [u8; 0],
     }
@@ -621,6 +626,85 @@ pub mod sys {
             ) -> c_int;
             pub fn cec_parts_pipeline_query(pipeline: *mut cec_parts_pipeline, slot: usize) -> c_int;
             pub fn cec_parts_pipeline_drain(pipeline: *mut cec_parts_pipeline) -> c_int;
+        }
+    }
+
+    /// include/chunky_ec_parts_read.h: the ragged read with a packed return and the ragged read
+    /// pipeline, function for function.
+    pub mod parts_read {
+        use super::*;
+
+        extern "C" {
+            pub fn cec_read_ragged_packed_async(
+                codec: *const cec_codec,
+                base: *mut u8,
+                part_offsets: *const usize,
+                chunk_lens: *const usize,
+                n_parts: usize,
+                present: *const u8,
+                expected: *const u8,
+                data_only: c_int,
+                verified: *mut u8,
+                part_status: *mut c_int,
+                rebuilt: *mut u8,
+                rebuilt_cap: usize,
+                rebuilt_offsets: *mut usize,
+                stream: *mut c_void,
+            ) -> c_int;
+            pub fn cec_parts_reader_new(
+                codec: *const cec_codec,
+                slot_bytes: usize,
+                max_parts: usize,
+                depth: usize,
+                data_only: c_int,
+                out: *mut *mut cec_parts_reader,
+            ) -> c_int;
+            pub fn cec_parts_reader_free(reader: *mut cec_parts_reader);
+            pub fn cec_parts_reader_depth(reader: *const cec_parts_reader) -> usize;
+            pub fn cec_parts_reader_acquire(
+                reader: *mut cec_parts_reader,
+                slot: *mut usize,
+                stage: *mut *mut u8,
+            ) -> c_int;
+            pub fn cec_parts_reader_submit(
+                reader: *mut cec_parts_reader,
+                slot: usize,
+                chunk_lens: *const usize,
+                n_parts: usize,
+                present: *const u8,
+                expected: *const u8,
+            ) -> c_int;
+            pub fn cec_parts_reader_submit_from(
+                reader: *mut cec_parts_reader,
+                slot: usize,
+                shards: *const *const u8,
+                chunk_lens: *const usize,
+                n_parts: usize,
+                present: *const u8,
+                expected: *const u8,
+            ) -> c_int;
+            pub fn cec_parts_reader_wait(
+                reader: *mut cec_parts_reader,
+                slot: usize,
+                verified: *mut *const u8,
+                part_status: *mut *const c_int,
+                rebuilt: *mut *const u8,
+                rebuilt_offsets: *mut *const usize,
+                n_parts: *mut usize,
+            ) -> c_int;
+            pub fn cec_parts_reader_scatter(
+                reader: *mut cec_parts_reader,
+                slot: usize,
+                shards: *const *mut u8,
+            ) -> c_int;
+            pub fn cec_parts_reader_query(reader: *mut cec_parts_reader, slot: usize) -> c_int;
+            pub fn cec_parts_reader_drain(reader: *mut cec_parts_reader) -> c_int;
+            pub fn cec_parts_reader_stats(
+                reader: *const cec_parts_reader,
+                bytes_up: *mut u64,
+                bytes_down: *mut u64,
+                tail_copies: *mut u64,
+            );
         }
     }
 }
@@ -1500,6 +1584,216 @@ impl PartsPipeline {
     /// Wait for every submitted batch.
     pub fn drain(&mut self) -> Result<(), CecError> {
         check(unsafe { sys::parts::cec_parts_pipeline_drain(self.raw) })
+    }
+}
+
+/// `cec_read_ragged_packed_async`: [`read_ragged_async`] (`data_only`) or its resilver form with
+/// a packed return.  Every chunk the rebuild wrote also lands in the device region `rebuilt`
+/// (`rebuilt_cap` bytes, 16-byte aligned), dense and in part order; a copy queued on `stream`
+/// fills `rebuilt_offsets` (`n + 1` byte offsets): the r-th rebuilt chunk of part k is `L_k` bytes
+/// at `rebuilt_offsets[k] + r * ragged_stride(L_k)`.
+///
+/// # Safety
+/// As [`read_ragged_async`]; `rebuilt` must be device memory of `rebuilt_cap` bytes and
+/// `rebuilt_offsets` host memory of `n + 1` `usize` that stays allocated, and is not read, until
+/// the work queued on `stream` is done.
+pub unsafe fn read_ragged_packed_async(
+    codec: &ReedSolomon,
+    base: *mut u8,
+    part_offsets: &[usize],
+    chunk_lens: &[usize],
+    present: &[u8],
+    expected: *const u8,
+    data_only: bool,
+    verified: *mut u8,
+    part_status: *mut c_int,
+    rebuilt: *mut u8,
+    rebuilt_cap: usize,
+    rebuilt_offsets: *mut usize,
+    stream: *mut c_void,
+) -> Result<(), CecError> {
+    let t = codec.data_shard_count() + codec.parity_shard_count();
+    let n = chunk_lens.len();
+    if part_offsets.len() != n || present.len() != n * t {
+        return Err(CecError::Engine(EngineError {
+            code: 101,
+            message: "part_offsets, chunk_lens and present differ in length".to_string(),
+        }));
+    }
+    check(sys::parts_read::cec_read_ragged_packed_async(
+        codec.raw,
+        base,
+        part_offsets.as_ptr(),
+        chunk_lens.as_ptr(),
+        n,
+        present.as_ptr(),
+        expected,
+        data_only as c_int,
+        verified,
+        part_status,
+        rebuilt,
+        rebuilt_cap,
+        rebuilt_offsets,
+        stream,
+    ))
+}
+
+/// [`parts_read`] with `depth` slots in flight and only the rebuilt chunks coming back, packed
+/// (`cec_parts_reader_*`).  One thread drives a reader (it is `Send`, not `Sync`).  Per slot:
+/// [`acquire`](Self::acquire) hands out the pinned staging region, [`submit`](Self::submit) queues
+/// a batch whose loaded chunks the caller placed there at the [`ragged_layout`] offsets,
+/// [`submit_from`](Self::submit_from) lets the engine pack the caller's chunk slots,
+/// [`wait`](Self::wait) borrows the flags, statuses and the packed return, and
+/// [`scatter`](Self::scatter) copies the rebuilt chunks into the caller's slots.
+pub struct PartsReader {
+    raw: *mut sys::cec_parts_reader,
+    t: usize,
+    slot_bytes: usize,
+}
+
+unsafe impl Send for PartsReader {}
+
+impl Drop for PartsReader {
+    fn drop(&mut self) {
+        unsafe { sys::parts_read::cec_parts_reader_free(self.raw) }
+    }
+}
+
+/// One completed ragged read batch: flags `[parts][d+p]`, statuses `[parts]`, the packed return
+/// and its `parts + 1` byte offsets, pinned host memory owned by the slot until it is acquired
+/// again.
+pub struct PartsReadResult<'a> {
+    pub verified: &'a [u8],
+    pub part_status: &'a [c_int],
+    pub rebuilt: &'a [u8],
+    pub rebuilt_offsets: &'a [usize],
+    pub n_parts: usize,
+}
+
+impl PartsReader {
+    pub fn new(
+        codec: &ReedSolomon,
+        slot_bytes: usize,
+        max_parts: usize,
+        depth: usize,
+        data_only: bool,
+    ) -> Result<PartsReader, CecError> {
+        let mut raw = std::ptr::null_mut();
+        check(unsafe {
+            sys::parts_read::cec_parts_reader_new(codec.raw, slot_bytes, max_parts, depth, data_only as c_int, &mut raw)
+        })?;
+        Ok(PartsReader {
+            raw,
+            t: codec.data_shard_count() + codec.parity_shard_count(),
+            slot_bytes,
+        })
+    }
+
+    pub fn depth(&self) -> usize {
+        unsafe { sys::parts_read::cec_parts_reader_depth(self.raw) }
+    }
+
+    /// Next slot (waits for its previous batch) and its pinned staging region.
+    pub fn acquire(&mut self) -> Result<(usize, &mut [u8]), CecError> {
+        let mut slot = 0usize;
+        let mut stage = std::ptr::null_mut();
+        check(unsafe { sys::parts_read::cec_parts_reader_acquire(self.raw, &mut slot, &mut stage) })?;
+        Ok((slot, unsafe { std::slice::from_raw_parts_mut(stage, self.slot_bytes) }))
+    }
+
+    fn lengths_agree(&self, n: usize, present: &[u8], expected: &[u8]) -> Result<(), CecError> {
+        if present.len() != n * self.t || expected.len() != n * self.t * 32 {
+            return Err(CecError::Engine(EngineError {
+                code: 101,
+                message: "present needs n * (d+p) flags and expected 32 bytes for each".to_string(),
+            }));
+        }
+        Ok(())
+    }
+
+    /// Queue the batch whose loaded chunks the caller wrote into `slot` (asynchronous).
+    pub fn submit(&mut self, slot: usize, chunk_lens: &[usize], present: &[u8], expected: &[u8]) -> Result<(), CecError> {
+        self.lengths_agree(chunk_lens.len(), present, expected)?;
+        check(unsafe {
+            sys::parts_read::cec_parts_reader_submit(self.raw, slot, chunk_lens.as_ptr(), chunk_lens.len(), present.as_ptr(), expected.as_ptr())
+        })
+    }
+
+    /// Pack the loaded chunks of `shards` (`[parts][d+p]` pointers, `cec_parts_read`'s form) into
+    /// `slot` and queue them.
+    ///
+    /// # Safety
+    /// Every loaded slot must point to `chunk_lens[k]` readable bytes.
+    pub unsafe fn submit_from(
+        &mut self,
+        slot: usize,
+        shards: &[*const u8],
+        chunk_lens: &[usize],
+        present: &[u8],
+        expected: &[u8],
+    ) -> Result<(), CecError> {
+        self.lengths_agree(chunk_lens.len(), present, expected)?;
+        if shards.len() != present.len() {
+            return Err(CecError::Engine(EngineError { code: 101, message: "shards needs n * (d+p) pointers".to_string() }));
+        }
+        check(sys::parts_read::cec_parts_reader_submit_from(
+            self.raw,
+            slot,
+            shards.as_ptr(),
+            chunk_lens.as_ptr(),
+            chunk_lens.len(),
+            present.as_ptr(),
+            expected.as_ptr(),
+        ))
+    }
+
+    /// Wait for `slot`'s batch and borrow its results.
+    pub fn wait(&mut self, slot: usize) -> Result<PartsReadResult<'_>, CecError> {
+        let mut verified = std::ptr::null();
+        let mut part_status = std::ptr::null();
+        let mut rebuilt = std::ptr::null();
+        let mut offsets = std::ptr::null();
+        let mut n_parts = 0usize;
+        check(unsafe {
+            sys::parts_read::cec_parts_reader_wait(self.raw, slot, &mut verified, &mut part_status, &mut rebuilt, &mut offsets, &mut n_parts)
+        })?;
+        let rebuilt_offsets = unsafe { std::slice::from_raw_parts(offsets, n_parts + 1) };
+        Ok(PartsReadResult {
+            verified: unsafe { std::slice::from_raw_parts(verified, n_parts * self.t) },
+            part_status: unsafe { std::slice::from_raw_parts(part_status, n_parts) },
+            rebuilt: unsafe { std::slice::from_raw_parts(rebuilt, rebuilt_offsets[n_parts]) },
+            rebuilt_offsets,
+            n_parts,
+        })
+    }
+
+    /// After [`wait`](Self::wait): copy every rebuilt chunk into the caller's slot.
+    ///
+    /// # Safety
+    /// Every slot the read fills must point to `chunk_lens[k]` writable bytes.
+    pub unsafe fn scatter(&mut self, slot: usize, shards: &[*mut u8]) -> Result<(), CecError> {
+        check(sys::parts_read::cec_parts_reader_scatter(self.raw, slot, shards.as_ptr()))
+    }
+
+    /// Whether `slot`'s batch is complete (never blocks).
+    pub fn query(&mut self, slot: usize) -> Result<bool, CecError> {
+        match unsafe { sys::parts_read::cec_parts_reader_query(self.raw, slot) } {
+            0 => Ok(false),
+            1 => Ok(true),
+            code => check(code).map(|_| true),
+        }
+    }
+
+    /// Wait for every submitted batch.
+    pub fn drain(&mut self) -> Result<(), CecError> {
+        check(unsafe { sys::parts_read::cec_parts_reader_drain(self.raw) })
+    }
+
+    /// (bytes queued to the device, bytes copied back, tail copies) since the reader was made.
+    pub fn stats(&self) -> (u64, u64, u64) {
+        let (mut up, mut down, mut tails) = (0u64, 0u64, 0u64);
+        unsafe { sys::parts_read::cec_parts_reader_stats(self.raw, &mut up, &mut down, &mut tails) };
+        (up, down, tails)
     }
 }
 

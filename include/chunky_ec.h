@@ -27,7 +27,8 @@
  *   and, for parts whose chunk lengths differ (whole small files, short last parts), the ragged
  *   forms of the four: cec_parts_encode / cec_encode_hash_ragged (write; with the data and the
  *   parity in regions of their own cec_encode_hash_split, and with slots in flight the ragged
- *   write pipeline cec_parts_pipeline_*, chunky_ec_parts.h), cec_parts_read / cec_read_ragged (read),
+ *   write pipeline cec_parts_pipeline_*, chunky_ec_parts.h), cec_parts_read / cec_read_ragged (read;
+ *   packed return and read pipeline cec_parts_reader_*, chunky_ec_parts_read.h),
  *   cec_parts_read / cec_resilver_ragged (resilver), cec_parts_verify / cec_verify_ragged
  *   (verify); cec_read_ragged_async / cec_resilver_ragged_async are the device-resident read
  *   and resilver with no wait inside the call.
@@ -104,7 +105,8 @@ int cec_device_numa_node(int device);
 const char* cec_build_info(void);
 /* Provenance: 16 hex digits, the hash of the sources the library was built from
  * (chunky-bits_amd/csrc/source_hash.py: every .cpp, .hip and .hpp file of csrc, its Makefile
- * and this header with chunky_ec_parts.h).  The Python binding refuses a library whose id differs from its shipped sources. */
+ * and this header with chunky_ec_parts.h and chunky_ec_parts_read.h).  The Python binding refuses a
+ * library whose id differs from its shipped sources. */
 const char* cec_build_id(void);
 /* Environment knobs (CEC_APPLY_*, CEC_FUSED*, CEC_SHA_VARIANT, CEC_COALESCE_*, ...;
  * DESIGN.md §6.3) are read ONCE, on the first call that needs one, into an immutable snapshot;
@@ -744,5 +746,8 @@ uint8_t cec_synth_byte(uint64_t seed, uint64_t part, uint64_t chunk, uint64_t of
 /* The ragged write pipeline (cec_parts_pipeline_*) has a header of its own, which this one
  * brings along. */
 #include "chunky_ec_parts.h"
+/* So have the ragged read with a packed return and the ragged read pipeline
+ * (cec_read_ragged_packed_async, cec_parts_reader_*). */
+#include "chunky_ec_parts_read.h"
 
 #endif /* CHUNKY_EC_H */

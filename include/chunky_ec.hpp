@@ -33,6 +33,7 @@
 #include <cstring>
 #include <deque>
 #include <exception>
+#include <functional>
 #include <future>
 #include <limits>
 #include <map>
@@ -396,6 +397,34 @@ inline cec_parts_pipeline* cached_parts_pipeline(size_t d, size_t p, size_t slot
         e.key = key;
     }
     return e.pipe.get();
+}
+
+// The calling thread's most recent ragged read pipeline (FileReference::read_many_stream), kept
+// the same way: per (d, p, slot bytes, parts per slot, depth) and device.
+struct CachedPartsReader {
+    std::vector<size_t> key;
+    std::shared_ptr<ReedSolomon> codec;
+    std::shared_ptr<cec_parts_reader> reader;
+};
+inline CachedPartsReader& cached_parts_reader_entry() {
+    thread_local CachedPartsReader e;
+    return e;
+}
+inline cec_parts_reader* cached_parts_reader(size_t d, size_t p, size_t slot_bytes,
+                                             size_t max_parts, size_t depth) {
+    CachedPartsReader& e = cached_parts_reader_entry();
+    int device = 0;
+    check(cec_current_device(&device));
+    const std::vector<size_t> key{d, p, slot_bytes, max_parts, depth, size_t(device)};
+    if (!e.reader || e.key != key) {
+        e.reader.reset();
+        e.codec = std::make_shared<ReedSolomon>(d, p);
+        cec_parts_reader* raw = nullptr;
+        check(cec_parts_reader_new(e.codec->raw(), slot_bytes, max_parts, depth, 1, &raw));
+        e.reader = std::shared_ptr<cec_parts_reader>(raw, cec_parts_reader_free);
+        e.key = key;
+    }
+    return e.reader.get();
 }
 }  // namespace detail
 
@@ -915,42 +944,107 @@ struct FileReference {
     static std::vector<Bytes> read_many(const std::vector<const FileReference*>& files,
                                         const ChunkStore& src, size_t parts_per_batch = 0,
                                         size_t depth = 4, const std::vector<int>& devices = {}) {
-        struct Pending {
-            const FilePart* part;
-            uint8_t* out;  // the part's d*L bytes in its file's result
-        };
-        std::vector<Bytes> out(files.size());
-        detail::ShapeWindows<Pending> windows;  // budget: data bytes
-        auto flush = [&](size_t d, size_t p, const std::vector<Pending>& parts) {
-            read_window(src, d, p, parts);
-        };
-        for (size_t f = 0; f < files.size(); ++f) {
-            const FileReference& file = *files[f];
-            out[f].resize(static_cast<size_t>(file.parts_bytes()));
-            std::vector<size_t> at(file.parts.size() + 1, 0);
-            for (size_t k = 0; k < file.parts.size(); ++k)
-                at[k + 1] = at[k] + file.parts[k].len_bytes();
-            file.for_runs(parts_per_batch, [&](size_t k0, size_t n) {
-                if (n >= 2) {
-                    size_t pos = at[k0];
-                    auto emit = [&](const uint8_t* b, size_t m) {
-                        detail::parallel_copy(out[f].data() + pos, b, m);
-                        pos += m;
-                    };
-                    file.read_run(src, k0, n, parts_per_batch, depth, devices, emit);
-                    return;
-                }
-                const FilePart& part = file.parts[k0];
-                windows.add(part.data.size(), part.parity.size(),
-                            Pending{&part, out[f].data() + at[k0]}, part.len_bytes(), flush);
+        detail::ShapeWindows<ReadPending> windows;  // budget: data bytes
+        return gather_reads(
+            files, src, parts_per_batch, depth, devices, windows,
+            [](const FilePart& part) { return part.len_bytes(); },
+            [&](size_t d, size_t p, const std::vector<ReadPending>& parts) {
+                read_window(src, d, p, parts);
             });
-        }
-        windows.flush(flush);
-        for (size_t f = 0; f < files.size(); ++f)
-            if (files[f]->length && *files[f]->length < out[f].size())
-                out[f].resize(static_cast<size_t>(*files[f]->length));
-        return out;
     }
+
+    // read_many with the gathered parts streamed through a ragged read pipeline
+    // (cec_parts_reader_*) instead of one cec_parts_read call per window and round: the same
+    // windows, but a window is a reader slot's batch (budget: its layout, (d + p) strides per
+    // part, within `slot_bytes`, and kStreamSlotParts parts) and `stream_depth` of them are in
+    // flight, so the loading and packing of one overlaps the copies and SHA-256 chains of the
+    // others, and only the rebuilt chunks come back from the device.  The retry rule is
+    // read_window's (ReadRounds): the parts a batch reports TooFewShardsPresent draw further
+    // chunks and go up again as a later batch of their own.  Same bytes and the same failures as
+    // read_many.  A shape the reader refuses (d > 32 or p > 8) and a part larger than a slot take
+    // read_many's path, window by window.  The reader is the calling thread's, kept between
+    // calls (see release_thread_buffers).
+    static constexpr size_t kStreamSlotParts = 4096;
+    static std::vector<Bytes> read_many_stream(const std::vector<const FileReference*>& files,
+                                               const ChunkStore& src, size_t parts_per_batch = 0,
+                                               size_t depth = 4,
+                                               const std::vector<int>& devices = {},
+                                               size_t stream_depth = 2,
+                                               size_t slot_bytes = size_t(64) << 20) {
+        if (stream_depth == 0) throw std::invalid_argument("read_many_stream: stream_depth must be > 0");
+        using Rounds = ReadRounds<ReadPending>;
+        struct Batch {
+            size_t slot;
+            std::shared_ptr<Rounds> rounds;
+            typename Rounds::Round round;
+        };
+        cec_parts_reader* rd = nullptr;  // the reader of the shape in flight
+        std::pair<size_t, size_t> shape{0, 0};
+        std::deque<Batch> flying;  // oldest first
+        std::function<void(std::shared_ptr<Rounds>, std::vector<size_t>)> launch;
+        auto collect = [&] {
+            Batch b = std::move(flying.front());
+            flying.pop_front();
+            const uint8_t* verified = nullptr;
+            const int* status = nullptr;
+            size_t got = 0;
+            detail::check(cec_parts_reader_wait(rd, b.slot, &verified, &status, nullptr, nullptr, &got));
+            if (got != b.round.active.size())
+                throw std::logic_error("read_many_stream: a slot lost its batch");
+            detail::check(cec_parts_reader_scatter(rd, b.slot, b.round.shards.data()));
+            std::vector<size_t> still = b.rounds->absorb(b.round, verified, status);
+            if (!still.empty()) launch(b.rounds, std::move(still));
+        };
+        launch = [&](std::shared_ptr<Rounds> rounds, std::vector<size_t> active) {
+            while (flying.size() >= stream_depth) collect();  // the slot that comes round next
+            Batch b{0, rounds, rounds->draw(std::move(active))};
+            uint8_t* stage = nullptr;
+            detail::check(cec_parts_reader_acquire(rd, &b.slot, &stage));
+            detail::check(cec_parts_reader_submit_from(rd, b.slot, b.round.shards.data(),
+                                                       b.round.lens.data(), b.round.lens.size(),
+                                                       b.round.present.data(), b.round.expected.data()));
+            flying.push_back(std::move(b));
+        };
+        auto settle = [&] {
+            while (!flying.empty()) collect();
+        };
+        auto flush = [&](size_t d, size_t p, const std::vector<ReadPending>& parts) {
+            size_t layout = 0;
+            for (const ReadPending& pd : parts)
+                layout += (d + p) * cec_ragged_stride(pd.part->chunksize);
+            if (d > kReaderMaxData || p > kReaderMaxParity || layout > slot_bytes) {
+                read_window(src, d, p, parts);  // outside the reader: read_many's path
+                return;
+            }
+            if (!rd || shape != std::make_pair(d, p)) {
+                settle();  // one reader at a time: the thread keeps one
+                rd = detail::cached_parts_reader(d, p, slot_bytes, kStreamSlotParts, stream_depth);
+                shape = {d, p};
+            }
+            auto rounds = std::make_shared<Rounds>(src, d, p, parts);
+            std::vector<size_t> all(parts.size());
+            for (size_t q = 0; q < all.size(); ++q) all[q] = q;
+            launch(std::move(rounds), std::move(all));
+        };
+        detail::ShapeWindows<ReadPending> windows;  // budget: the slot layout's bytes and parts
+        try {
+            std::vector<Bytes> out = gather_reads(
+                files, src, parts_per_batch, depth, devices, windows,
+                [&](const FilePart& part) {
+                    detail::ManyWindow<ReadPending>& w =
+                        windows.of[{part.data.size(), part.parity.size()}];
+                    w.cap = slot_bytes;
+                    w.max_items = kStreamSlotParts;
+                    return (part.data.size() + part.parity.size()) * cec_ragged_stride(part.chunksize);
+                },
+                flush, settle);
+            return out;
+        } catch (...) {
+            if (rd) (void)cec_parts_reader_drain(rd);  // nothing of this call stays in flight
+            throw;
+        }
+    }
+    static constexpr size_t kReaderMaxData = 32, kReaderMaxParity = 8;  // the device planner's scope
 
     // FileReadBuilder's reader (reader.rs:40-75) as a stream: the file's bytes in order (the
     // last part truncated to `length`, file_reference.rs:49-56) handed to sink(bytes, n) piece by
@@ -1313,56 +1407,134 @@ struct FileReference {
         }
     }
 
-    // One window of read_many: parts of one (d, p) and any chunk lengths, verified and rebuilt by
-    // one cec_parts_read call per retry round; part q's data lands at parts[q].out.
+    // A part the many-files reads gathered, and where its d*L bytes lie in its file's result.
+    struct ReadPending {
+        const FilePart* part;
+        uint8_t* out;
+    };
+
+    // The gather loop of read_many / read_many_stream.  Runs of two or more parts of one shape go
+    // through read_run when parts_per_batch is set; every other part goes into its shape's window
+    // with the budget size_of(part), which hands full windows to flush(d, p, parts).  settle()
+    // after the last window; then the results are cut to the files' lengths.
+    template <typename SizeOf, typename Flush, typename Settle>
+    static std::vector<Bytes> gather_reads(const std::vector<const FileReference*>& files,
+                                           const ChunkStore& src, size_t parts_per_batch,
+                                           size_t depth, const std::vector<int>& devices,
+                                           detail::ShapeWindows<ReadPending>& windows,
+                                           SizeOf&& size_of, Flush&& flush, Settle&& settle) {
+        std::vector<Bytes> out(files.size());
+        for (size_t f = 0; f < files.size(); ++f) {
+            const FileReference& file = *files[f];
+            out[f].resize(static_cast<size_t>(file.parts_bytes()));
+            std::vector<size_t> at(file.parts.size() + 1, 0);
+            for (size_t k = 0; k < file.parts.size(); ++k)
+                at[k + 1] = at[k] + file.parts[k].len_bytes();
+            file.for_runs(parts_per_batch, [&](size_t k0, size_t n) {
+                if (n >= 2) {
+                    size_t pos = at[k0];
+                    auto emit = [&](const uint8_t* b, size_t m) {
+                        detail::parallel_copy(out[f].data() + pos, b, m);
+                        pos += m;
+                    };
+                    file.read_run(src, k0, n, parts_per_batch, depth, devices, emit);
+                    return;
+                }
+                const FilePart& part = file.parts[k0];
+                const size_t size = size_of(part);
+                windows.add(part.data.size(), part.parity.size(),
+                            ReadPending{&part, out[f].data() + at[k0]}, size, flush);
+            });
+        }
+        windows.flush(flush);
+        settle();
+        for (size_t f = 0; f < files.size(); ++f)
+            if (files[f]->length && *files[f]->length < out[f].size())
+                out[f].resize(static_cast<size_t>(*files[f]->length));
+        return out;
+    }
+    template <typename SizeOf, typename Flush>
+    static std::vector<Bytes> gather_reads(const std::vector<const FileReference*>& files,
+                                           const ChunkStore& src, size_t parts_per_batch,
+                                           size_t depth, const std::vector<int>& devices,
+                                           detail::ShapeWindows<ReadPending>& windows,
+                                           SizeOf&& size_of, Flush&& flush) {
+        return gather_reads(files, src, parts_per_batch, depth, devices, windows, size_of, flush,
+                            [] {});
+    }
+
+    // The retry rounds of one window of read_many / read_many_stream: parts of one (d, p) and any
+    // chunk lengths, part q's data landing at parts[q].out.  Per part the bookkeeping of
+    // read_with_context (which chunks verified, which were tried, which have no copy left, the
+    // next copy of each) lives here across the rounds.
+    //   draw(active): for each listed part, the next round's chunks drawn (FilePart::draw) into
+    //     their slots, and the round's arguments in cec_parts_read's form; TooFewShardsPresent
+    //     when a part's copies have run out.
+    //   absorb(round, verified, status): the round's flags taken in; returns the parts reported
+    //     TooFewShardsPresent, which draw again.
     template <typename Pending>
-    static void read_window(const ChunkStore& src, size_t d, size_t p,
-                            const std::vector<Pending>& parts) {
-        const size_t t = d + p, n = parts.size();
-        const ReedSolomon codec(d, p);
-        std::vector<uint8_t> good(n * t), tried(n * t), exhausted(n * t);
-        std::vector<size_t> cursor(n * t), have(n);
-        std::vector<Bytes> parity(n * p);  // the loaded parity copies (never handed out)
-        std::vector<size_t> active(n);
-        for (size_t q = 0; q < n; ++q) active[q] = q;
-        auto slot = [&](size_t q, size_t i) {
+    struct ReadRounds {
+        struct Round {
+            std::vector<size_t> active;  // the window's parts of this round
+            std::vector<uint8_t*> shards;
+            std::vector<size_t> lens;
+            std::vector<uint8_t> present, expected;
+        };
+        const ChunkStore& src;
+        const size_t d, p, t;
+        const std::vector<Pending> parts;
+        std::vector<uint8_t> good, tried, exhausted;
+        std::vector<size_t> cursor, have;
+        std::vector<Bytes> parity;  // the loaded parity copies (never handed out)
+
+        ReadRounds(const ChunkStore& src_, size_t d_, size_t p_, const std::vector<Pending>& parts_)
+            : src(src_), d(d_), p(p_), t(d_ + p_), parts(parts_), good(parts_.size() * t),
+              tried(parts_.size() * t), exhausted(parts_.size() * t), cursor(parts_.size() * t),
+              have(parts_.size()), parity(parts_.size() * p_) {}
+
+        uint8_t* slot(size_t q, size_t i) {
             const size_t L = parts[q].part->chunksize;
             if (i < d) return parts[q].out + i * L;
             Bytes& b = parity[q * p + (i - d)];
             if (b.size() != L) b.resize(L);
             return b.data();
-        };
-        while (!active.empty()) {
+        }
+
+        Round draw(std::vector<size_t> active) {
+            Round r;
             const size_t m = active.size();
-            std::vector<uint8_t*> shards(m * t, nullptr);
-            std::vector<size_t> lens(m);
-            std::vector<uint8_t> present(m * t, 0), expected(m * t * 32), verified(m * t, 0);
-            std::vector<int> status(m, 0);
+            r.active = std::move(active);
+            r.shards.assign(m * t, nullptr);
+            r.lens.resize(m);
+            r.present.assign(m * t, 0);
+            r.expected.resize(m * t * 32);
             for (size_t a = 0; a < m; ++a) {
-                const size_t q = active[a];
+                const size_t q = r.active[a];
                 const FilePart& part = *parts[q].part;
                 const size_t L = part.chunksize;
-                lens[a] = L;
+                r.lens[a] = L;
                 uint8_t* gq = &good[q * t];
                 const size_t added =
                     part.draw(src, gq, &tried[q * t], &exhausted[q * t], &cursor[q * t], have[q],
                               [&](size_t i, const Bytes* b) {
                                   std::memcpy(slot(q, i), b->data(), L);
-                                  present[a * t + i] = 1;
+                                  r.present[a * t + i] = 1;
                               });
                 if (added == 0) throw ErasureError(Error::TooFewShardsPresent);
                 for (size_t i = 0; i < t; ++i) {
-                    if (gq[i]) present[a * t + i] = CEC_PRESENT_VERIFIED;
+                    if (gq[i]) r.present[a * t + i] = CEC_PRESENT_VERIFIED;
                     // data slots are the result's own bytes; parity is read only when loaded
-                    if (i < d || present[a * t + i]) shards[a * t + i] = slot(q, i);
-                    std::memcpy(&expected[(a * t + i) * 32], part.chunk(i).hash.digest().data(), 32);
+                    if (i < d || r.present[a * t + i]) r.shards[a * t + i] = slot(q, i);
+                    std::memcpy(&r.expected[(a * t + i) * 32], part.chunk(i).hash.digest().data(), 32);
                 }
             }
-            detail::check(cec_parts_read(codec.raw(), shards.data(), lens.data(), m, present.data(),
-                                         expected.data(), 1, verified.data(), status.data()));
+            return r;
+        }
+
+        std::vector<size_t> absorb(const Round& r, const uint8_t* verified, const int* status) {
             std::vector<size_t> still;
-            for (size_t a = 0; a < m; ++a) {
-                const size_t q = active[a];
+            for (size_t a = 0; a < r.active.size(); ++a) {
+                const size_t q = r.active[a];
                 for (size_t i = 0; i < t; ++i)
                     if (verified[a * t + i] && !good[q * t + i]) {
                         good[q * t + i] = 1;
@@ -1371,7 +1543,28 @@ struct FileReference {
                 if (status[a] == CEC_TOO_FEW_SHARDS_PRESENT) still.push_back(q);
                 else if (status[a] != CEC_OK) detail::check(status[a]);
             }
-            active.swap(still);
+            return still;
+        }
+    };
+
+    // One window of read_many: verified and rebuilt by one cec_parts_read call per retry round
+    // (ReadRounds).
+    template <typename Pending>
+    static void read_window(const ChunkStore& src, size_t d, size_t p,
+                            const std::vector<Pending>& parts) {
+        const ReedSolomon codec(d, p);
+        ReadRounds<Pending> rounds(src, d, p, parts);
+        std::vector<size_t> active(parts.size());
+        for (size_t q = 0; q < active.size(); ++q) active[q] = q;
+        while (!active.empty()) {
+            typename ReadRounds<Pending>::Round r = rounds.draw(std::move(active));
+            const size_t m = r.active.size();
+            std::vector<uint8_t> verified(m * (d + p), 0);
+            std::vector<int> status(m, 0);
+            detail::check(cec_parts_read(codec.raw(), r.shards.data(), r.lens.data(), m,
+                                         r.present.data(), r.expected.data(), 1, verified.data(),
+                                         status.data()));
+            active = rounds.absorb(r, verified.data(), status.data());
         }
     }
 
@@ -2302,6 +2495,7 @@ inline void release_thread_buffers() {
     }
     detail::cached_multi_entry() = detail::CachedMulti{};
     detail::cached_parts_pipeline_entry() = detail::CachedPartsPipeline{};
+    detail::cached_parts_reader_entry() = detail::CachedPartsReader{};
 }
 
 }  // namespace chunky_ec

@@ -36,8 +36,15 @@ the first parity chunk:
      the digests compared, then cec_reconstruct_data
   b  one cec_parts_read call over all parts
   c  the CPU oracle on 16 threads (SHA-256 of the d loaded chunks, reconstruct_data)
+  d  the parts reader: cec_parts_reader_submit_from per slot-sized batch of consecutive parts
+     (--slot-mib of ragged layout each), one arm per --depths entry; the oldest slot is waited
+     for and scattered into the same output slots while the later ones run
 
-All arms' rebuilt chunks must equal the erased ones (asserted).
+All arms' rebuilt chunks must equal the erased ones (asserted).  Beside the times, the bytes
+each of b and d brings back from the device per pass: d's from cec_parts_reader_stats, b's the
+copies its copy_spans step issues (rebuilt spans merged across gaps under 256 KiB, per round of
+CEC_COALESCE_MAX_MIB), counted here from the same layout.  d counts as faster than b only if its
+worst repeat is below b's best by more than the larger spread of the two.
 
 --device --read: 4096 x RS(10,4) x 64 KiB, two erasures per part, device resident:
 cec_reconstruct_ragged with uniform lengths against cec_reconstruct_batch on the same bytes.
@@ -63,7 +70,7 @@ Every arm must find every chunk good, and the one chunk that is flipped before t
     python tools/small_files_bench.py [--files 4096] [--repeats 3] [--shapes 3,2:10,4]
                                       [--slot-mib 64] [--depths 3,2] [--no-per-part]
     python tools/small_files_bench.py --device
-    python tools/small_files_bench.py --read
+    python tools/small_files_bench.py --read [--slot-mib 64] [--depths 3,2] [--no-per-part]
     python tools/small_files_bench.py --verify
     python tools/small_files_bench.py --device --read"""
 import argparse
@@ -403,6 +410,76 @@ class ReadWorkload:
         assert all(s == 0 for s in self.status[:n])
         assert np.array_equal(self.verified[:n], self.flags[:n])
 
+    def parts_read_d2h_bytes(self):
+        """What arm b's copy back moves: per round (at most CEC_COALESCE_MAX_MIB of padded data
+        chunks, ragged.cpp run_rounds) the rebuilt chunks' spans in the round's layout, neighbours
+        sharing a copy while the gap between them is under 256 KiB (copy_spans)."""
+        cap = int(os.environ.get("CEC_COALESCE_MAX_MIB", "1024")) << 20
+        d, t, gap = self.d, self.t, 256 << 10
+        total = copies = 0
+        off = acc = 0
+        last_to = None
+        for k, L in enumerate(self.L):
+            cs = (L + 15) // 16 * 16
+            b = d * cs
+            if acc and (b > cap or acc > cap - b):  # a new round: its own arena offsets
+                off, acc, last_to = 0, 0, None
+            acc += min(b, cap)
+            lo = off + self.erased[k] * cs
+            if last_to is not None and lo - last_to < gap:
+                total += lo + L - last_to
+            else:
+                total += L
+                copies += 1
+            last_to = lo + L
+            off += t * cs
+        return total, copies
+
+    def make_reader(self, slot_bytes, depth, max_parts=4096):
+        """(reader, [(k0, k1)], per batch (slot pointers, chunk lengths)): consecutive parts whose
+        ragged layout fits a slot, the tables made before any clock starts."""
+        t = self.t
+        need = [t * ((L + 15) // 16 * 16) for L in self.L]
+        slot_bytes = max(slot_bytes, max(need))
+        batches, k0, acc = [], 0, 0
+        for k, b in enumerate(need):
+            if k > k0 and (acc + b > slot_bytes or k - k0 >= max_parts):
+                batches.append((k0, k))
+                k0, acc = k, 0
+            acc += b
+        batches.append((k0, self.n))
+        rd = ce.PartsReader(self.rs, slot_bytes, max_parts, depth, True)
+        tables = [((U8P * ((k1 - k0) * t))(*self.all_ptrs[k0 * t:k1 * t]),
+                   (ctypes.c_size_t * (k1 - k0))(*self.L[k0:k1])) for k0, k1 in batches]
+        return rd, batches, tables
+
+    def arm_reader(self, reader):
+        rd, batches, tables = reader
+        lib, t = ce._lib, self.t
+        fb, eb = self.flags.ctypes.data, self.expected.ctypes.data
+        pending = []
+
+        def collect():
+            slot, (k0, k1), ptrs = pending.pop(0)
+            ver, st, n = U8P(), ctypes.POINTER(ctypes.c_int)(), ctypes.c_size_t(0)
+            ce._check(lib.cec_parts_reader_wait(rd._h, slot, ctypes.byref(ver), ctypes.byref(st),
+                                                None, None, ctypes.byref(n)))
+            ce._check(lib.cec_parts_reader_scatter(rd._h, slot, ptrs))
+            m = k1 - k0
+            assert n.value == m
+            assert not np.ctypeslib.as_array(st, shape=(m,)).any()
+            assert np.array_equal(np.ctypeslib.as_array(ver, shape=(m, t)), self.flags[k0:k1])
+        for (k0, k1), (ptrs, lens) in zip(batches, tables):
+            if len(pending) == rd.depth:
+                collect()
+            slot, _ = rd.acquire()
+            ce._check(lib.cec_parts_reader_submit_from(
+                rd._h, slot, ptrs, lens, k1 - k0, ctypes.cast(fb + k0 * t, U8P),
+                ctypes.cast(eb + k0 * t * 32, U8P)))
+            pending.append((slot, (k0, k1), ptrs))
+        while pending:
+            collect()
+
     def arm_cpu(self, threads=16, count=None):
         lib = oracle.lib()
         d, p, t = self.d, self.p, self.t
@@ -435,29 +512,66 @@ def host_read(args):
                  lambda c=None: w.arm_percall(256, c)),
                 ("b: one parts_read call", lambda c=None: w.arm_ragged(c)),
                 ("c: CPU oracle x 16 threads", lambda c=None: w.arm_cpu(16, c))]
+        if args.no_per_part:  # a quick look at b and d: the per-part arms take most of a run
+            arms = [arm for arm in arms if not arm[0].startswith("a")]
+        readers = {depth: w.make_reader(args.slot_mib << 20, depth) for depth in args.depths}
+        d_names = {depth: f"d: parts reader (submit_from) {args.slot_mib} MiB x {depth}"
+                   for depth in readers}
+        for depth, reader in readers.items():
+            arms.append((d_names[depth], lambda c=None, reader=reader: w.arm_reader(reader)))
         warm = min(w.n, 512)
-        for name, fn in arms:  # warm-up: b on the whole input (its staging is sized by it)
-            sec, _ = timed(lambda: fn(None if name.startswith("b") else warm))
+        for name, fn in arms:  # warm-up: b and d on the whole input (b's staging is sized by it)
+            sec, _ = timed(lambda: fn(None if name[0] in "bd" else warm))
             print(f"   warm-up {name}: {sec:.3f} s", flush=True)
+        print(f"   d: {len(readers[args.depths[0]][1])} batches", flush=True)
         secs = {name: [] for name, _ in arms}
+        down = {name: [] for name in d_names.values()}
+        by_name = {name: readers[depth][0] for depth, name in d_names.items()}
         for rep in range(args.repeats):
             for name, fn in arms:
                 w.out[:] = 0
+                before = by_name[name].stats() if name in by_name else None
                 sec, _ = timed(fn)
                 secs[name].append(sec)
                 assert np.array_equal(w.out, w.want), f"rebuilt chunks of '{name}' differ"
+                note = ""
+                if before is not None:
+                    after = by_name[name].stats()
+                    down[name].append(after[1] - before[1])
+                    note = f"  D2H {down[name][-1]} B, tail copies {after[2] - before[2]}"
                 print(f"   repeat {rep + 1} {name}: {sec:.3f} s  "
-                      f"{w.file_bytes / sec / 1e9:7.2f} GB/s  {w.n / sec:9.0f} parts/s", flush=True)
+                      f"{w.file_bytes / sec / 1e9:7.2f} GB/s  {w.n / sec:9.0f} parts/s{note}",
+                      flush=True)
         print("   every arm rebuilt the erased chunks exactly, in every repeat")
-        names = [name for name, _ in arms]
-        wins = [secs[names[2]][r] < min(secs[names[0]][r], secs[names[1]][r])
-                for r in range(args.repeats)]
-        print(f"   b faster than the better per-part arm in each repeat: {wins}", flush=True)
-        results.append({"d": d, "p": p, "files": len(files), "parts": w.n,
-                        "file_bytes": w.file_bytes, "seconds": secs,
-                        "gbps": {k: [w.file_bytes / s / 1e9 for s in v] for k, v in secs.items()},
-                        "b_faster_each_repeat": wins})
-        del w
+        row = {"d": d, "p": p, "files": len(files), "parts": w.n,
+               "file_bytes": w.file_bytes, "seconds": secs,
+               "gbps": {k: [w.file_bytes / s / 1e9 for s in v] for k, v in secs.items()}}
+        b = secs["b: one parts_read call"]
+        if not args.no_per_part:
+            names = [name for name, _ in arms]
+            wins = [b[r] < min(secs[names[0]][r], secs[names[1]][r]) for r in range(args.repeats)]
+            print(f"   b faster than the better per-part arm in each repeat: {wins}", flush=True)
+            row["b_faster_each_repeat"] = wins
+        b_down, b_copies = w.parts_read_d2h_bytes()
+        rebuilt = int(sum(w.L))
+        print(f"   D2H per pass: rebuilt chunks {rebuilt} B; b's copy_spans {b_down} B in "
+              f"{b_copies} copies ({b_down / rebuilt:.2f}x); d {sorted(set(sum(down.values(), [])))} B",
+              flush=True)
+        row["d2h_bytes"] = {"rebuilt": rebuilt, "b": b_down, "b_copies": b_copies, "d": down}
+        for depth, name in d_names.items():
+            dd = secs[name]
+            spread = max(max(dd) - min(dd), max(b) - min(b))
+            wins = max(dd) + spread < min(b)
+            row[f"d{depth}_vs_b"] = {"b_best_s": min(b), "d_worst_s": max(dd), "spread_s": spread,
+                                     "d_wins_by_more_than_spread": wins}
+            print(f"   d (depth {depth}) vs b: b {min(b):.3f}-{max(b):.3f} s "
+                  f"({w.file_bytes / max(b) / 1e9:.2f}-{w.file_bytes / min(b) / 1e9:.2f} GB/s), "
+                  f"d {min(dd):.3f}-{max(dd):.3f} s "
+                  f"({w.file_bytes / max(dd) / 1e9:.2f}-{w.file_bytes / min(dd) / 1e9:.2f} GB/s), "
+                  f"largest spread {spread:.3f} s -> d wins by more than the spread: {wins}",
+                  flush=True)
+        results.append(row)
+        del w, readers, by_name
     print(json.dumps({"tool": "small_files_bench", "mode": "host-read", "results": results}))
 
 
@@ -951,10 +1065,12 @@ def main():
     ap.add_argument("--files", type=int, default=4096)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--shapes", default="3,2:10,4")
-    ap.add_argument("--slot-mib", type=int, default=64, help="arm d: data bytes per slot")
+    ap.add_argument("--slot-mib", type=int, default=64,
+                    help="arm d: data bytes per slot (--read: bytes of ragged layout per slot)")
     ap.add_argument("--depths", type=lambda s: [int(x) for x in s.split(",")], default=[3, 2],
                     help="arm d: one arm per number of slots in flight")
-    ap.add_argument("--no-per-part", action="store_true", help="host mode: leave out the a arms")
+    ap.add_argument("--no-per-part", action="store_true",
+                    help="host mode and --read: leave out the a arms")
     ap.add_argument("--device", action="store_true")
     ap.add_argument("--read", action="store_true")
     ap.add_argument("--verify", action="store_true")
