@@ -177,6 +177,9 @@ _sig("cec_ragged_read_stats", [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(c
      None)
 _sig("cec_parts_read", [_vp, ctypes.POINTER(_u8p), _szp, ctypes.c_size_t, _u8p, _u8p, ctypes.c_int,
                         _u8p, ctypes.POINTER(ctypes.c_int)])
+_sig("cec_part_read", [_vp, ctypes.POINTER(_u8p), ctypes.c_size_t, _u8p, _u8p, ctypes.c_int, _u8p])
+_sig("cec_coalesce_detail", [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                             ctypes.POINTER(ctypes.c_uint64)], None)
 _sig("cec_verify_ragged", [ctypes.c_size_t, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp, _u8p, _vp])
 _sig("cec_parts_verify", [ctypes.POINTER(_u8p), _szp, ctypes.c_size_t, _u8p, _u8p])
 _sig("cec_coalesce_stats", [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
@@ -896,6 +899,36 @@ def parts_read(codec: ReedSolomon, parts: Sequence[Sequence], expected: Sequence
                                ctypes.cast(ctypes.c_char_p(exp), _u8p), 1 if data_only else 0,
                                verified, status))
     return _parts_read_result(d, t, parts, lens, slots, verified, status, data_only)
+
+
+def part_read(codec: ReedSolomon, shards: Sequence, expected: Sequence, data_only: bool = True):
+    """:func:`parts_read` for ONE part, coalesced (``cec_part_read``): the per-part call of the
+    read side, ``read_with_context``'s (``data_only``) or ``resilver``'s compute in one call per
+    FilePart task.  Concurrent calls with one codec and one mode share a launch whatever their
+    chunk lengths.  ``shards`` lists the part's d+p chunks and ``expected`` its d+p digests as
+    ``parts[k]`` / ``expected[k]`` of :func:`parts_read`.  Returns ``(chunks, verified, status)``
+    for the part: ``status`` is ``OK`` or ``TOO_FEW_SHARDS_PRESENT`` (``verified`` is filled in
+    both cases; nothing is rebuilt in the second)."""
+    d, t = codec.data_shard_count(), codec.total_shard_count()
+    lens, pres, exp, slots, ptrs = _parts_read_args(d, t, [shards], [expected], data_only)
+    verified = (ctypes.c_uint8 * t)()
+    code = _lib.cec_part_read(codec.handle, ptrs, lens[0],
+                              ctypes.cast(ctypes.c_char_p(pres), _u8p),
+                              ctypes.cast(ctypes.c_char_p(exp), _u8p), 1 if data_only else 0,
+                              verified)
+    if code not in (OK, TOO_FEW_SHARDS_PRESENT):
+        raise Error(code)
+    out, ver, _ = _parts_read_result(d, t, [shards], lens, slots, verified, [code], data_only)
+    return out[0], ver, code
+
+
+def coalesce_detail():
+    """(part_mixed_batches, read_calls, read_launches) of the per-call coalescing path
+    (cec_coalesce_detail): the ``part_encode`` batches of two or more chunk lengths, and the
+    ``part_read`` calls made and launches issued."""
+    mixed, calls, launches = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _lib.cec_coalesce_detail(ctypes.byref(mixed), ctypes.byref(calls), ctypes.byref(launches))
+    return mixed.value, calls.value, launches.value
 
 
 def _parts_read_args(d, t, parts, expected, data_only):

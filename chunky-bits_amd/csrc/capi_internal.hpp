@@ -21,6 +21,7 @@
 #include "gf256.hpp"
 #include "kernels.hpp"
 #include "knobs.hpp"
+#include "percall_plan.hpp"
 
 #pragma GCC visibility push(hidden)
 
@@ -312,8 +313,7 @@ int ragged_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, uint8_
 
 // cec_ragged_layout behind its pointer checks.
 int ragged_layout(size_t t, const size_t* lens, size_t n, size_t* offs, size_t* total);
-// Whether a read fills slot i of a part when it is not among the verified chunks.
-inline bool fills_slot(size_t i, size_t d, bool data_only) { return i < d || !data_only; }
+// (fills_slot, whether a read fills a slot that did not verify: percall_plan.hpp)
 // The worst case of a packed return (cec_read_ragged_packed_async's bound on rebuilt_cap): the sum
 // of rows * stride(L_k), rows = p, or min(p, d) under data_only.  Nonzero lengths.
 int packed_worst_case(size_t d, size_t p, bool data_only, const size_t* lens, size_t n,
@@ -323,8 +323,36 @@ void pack_loaded(uint8_t* dst, const size_t* offs, size_t t, const uint8_t* cons
                  const size_t* chunk_lens, size_t n, const uint8_t* present);
 // Copies of the byte ranges [first, second) (ascending, disjoint) between a pinned staging and a
 // device arena that share their offsets, neighbours merged across small gaps.
-using Spans = std::vector<std::pair<size_t, size_t>>;
+// (Spans: percall_plan.hpp)
 int copy_spans(uint8_t* stage, uint8_t* dbase, const Spans& spans, bool to_device, hipStream_t s);
+
+// ---- One round of a host-staged read, as cec_parts_read (ragged.cpp) and cec_part_read's
+// coalescer (percall.cpp) both run it: reserve, stage every part, launch, collect every part. ----
+
+// The arenas of the host-staged ragged calls: one per call or batch in flight.
+ArenaPool& ragged_arenas();
+
+// One round's place in an arena: the packed layout of its n parts, `stage` (pinned) and `dbase`
+// (device) sharing those offsets, and `dside`, device room for the round's n * t digests, with
+// the arena's `out` as its pinned side.
+struct Round {
+    std::vector<size_t> offs;
+    uint8_t *stage, *dside, *dbase;
+    hipStream_t s;
+};
+int reserve_round(Arena& a, size_t d, size_t t, const size_t* chunk_lens, size_t n, Round* r);
+// Stage: part k's loaded chunks (its t slots and flags, chunk length L) into the staging.
+void read_round_stage(const Round& r, size_t k, size_t t, size_t L, uint8_t* const* shards,
+                      const uint8_t* present);
+// Launch: the n * t expected digests (already in a.out.ptr) and the loaded chunks up, the
+// verification and the rebuild (the host-planned read, every (d, p)), the rebuilt chunks back into
+// the staging, and the wait.  verified and part_status (host) are written.
+int read_round_launch(cec_codec* c, Arena& a, const Round& r, const size_t* chunk_lens, size_t n,
+                      const uint8_t* present, bool data_only, uint8_t* verified, int* part_status);
+// Collect: part k's rebuilt chunks out of the staging into its slots.
+void read_round_collect(const Round& r, size_t k, size_t d, size_t t, size_t L,
+                        uint8_t* const* shards, const uint8_t* verified, int part_status,
+                        bool data_only);
 
 }  // namespace cec
 

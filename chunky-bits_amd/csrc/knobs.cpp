@@ -35,6 +35,8 @@ Knobs* parse() {
         k->fused = e[0] == '0' ? 0 : e[0] == '1' ? 1 : -1;
     if (const char* e = std::getenv("CEC_RAGGED_FUSED"))  // "0" or "1"; anything else: unset
         k->ragged_fused = (e[0] == '0' || e[0] == '1') && e[1] == '\0' ? e[0] - '0' : -1;
+    if (const char* e = std::getenv("CEC_COALESCE_MIXED"))  // "0" or "1"; anything else: unset
+        k->coalesce_mixed = (e[0] == '0' || e[0] == '1') && e[1] == '\0' ? e[0] - '0' : -1;
     k->coalesce_us = uint32_t(number("CEC_COALESCE_US", 200));
     k->coalesce_max_bytes = std::max<size_t>(size_t(number("CEC_COALESCE_MAX_MIB", 1024)), 1)
                             << 20;

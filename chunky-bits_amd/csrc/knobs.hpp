@@ -3,7 +3,7 @@
 // Every knob is parsed into one immutable snapshot on first use; the launch paths read the
 // snapshot, never the environment.  The knobs are capacities and diagnostics, plus the test
 // knobs that force one of the library's own paths at test sizes (CEC_APPLY_BS,
-// CEC_APPLY_MAX_BLOCKS, CEC_SHA_VARIANT 1/2, CEC_FUSED_MODE 3, CEC_FUSED, CEC_RAGGED_FUSED).
+// CEC_APPLY_MAX_BLOCKS, CEC_SHA_VARIANT 1/2, CEC_FUSED_MODE 3, CEC_FUSED, CEC_RAGGED_FUSED, CEC_COALESCE_MIXED).
 // The reference calls the hot path from tokio worker threads (writer.rs:200-210 spawns a task
 // per part; file_part.rs:161 runs the encode inside block_in_place), and getenv racing a setenv
 // elsewhere in the host process is undefined behaviour; a snapshot read is a plain load.
@@ -33,6 +33,7 @@ struct Knobs {
     size_t coalesce_max_bytes = size_t(1024) << 20;  // CEC_COALESCE_MAX_MIB
     bool coalesce_trace = false;    // CEC_COALESCE_TRACE
     uint32_t coalesce_inflight = 2;      // CEC_COALESCE_INFLIGHT (1..16)
+    int coalesce_mixed = -1;        // CEC_COALESCE_MIXED 0/1 (-1: percall.cpp's default)
     size_t idle_staging_bytes = size_t(1) << 30;  // CEC_IDLE_STAGING_MIB (per device)
     // multi.cpp
     unsigned multi_copy_threads = 4;     // CEC_MULTI_COPY_THREADS (1..32)

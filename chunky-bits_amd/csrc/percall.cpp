@@ -196,7 +196,8 @@ int reconstruct_host(const cec_codec* cc, uint8_t* const* shards, const size_t* 
 // launch.  cec_part_encode / cec_sha256(_many) therefore go through a leader/follower queue:
 // the first caller to find no batch in progress becomes the leader, waits up to
 // CEC_COALESCE_US microseconds (default 200; only when calls are concurrent) for more requests
-// with its key (codec, chunk length, device), and runs them as ONE batch:
+// with its key (the device; for cec_part_encode the codec too, and the chunk length while
+// CEC_COALESCE_MIXED is 0; for cec_part_read the codec and the mode), and runs them as ONE batch:
 //   1. copy-in   every caller copies its own (pageable) input into the queue's pinned staging,
 //                in parallel on its own thread;
 //   2. launch    the leader moves the whole batch with one H2D copy, runs the fused
@@ -205,15 +206,41 @@ int reconstruct_host(const cec_codec* cc, uint8_t* const* shards, const size_t* 
 //   3. copy-out  every caller copies its results out into its own buffers, in parallel.
 // Batches are capped at CEC_COALESCE_MAX_MIB of input (default 1024).  Results are
 // bit-identical to one call per launch (same kernels, same inputs).
+// cec_part_encode calls of different chunk lengths share a batch in the split layout of the ragged
+// encode (PartImpl below); cec_part_read, the read side's per-part call, has a queue of its own
+// whose batches are rounds of cec_parts_read (ReadImpl).
 // ------------------------------------------------------------------------------------------
-std::atomic<uint64_t> g_calls{0}, g_launches{0};
+// cec_coalesce_stats (cec_sha256(_many) and cec_part_encode) and cec_coalesce_detail (batches of
+// cec_part_encode calls of two or more chunk lengths; cec_part_read calls and their launches).
+struct Counters {
+    std::atomic<uint64_t> calls{0}, launches{0};
+};
+Counters g_write_counters, g_read_counters;
+std::atomic<uint64_t> g_mixed_batches{0};
 
+// What an unset CEC_COALESCE_MIXED selects.  The rule, fixed before the measurement: gathering
+// across chunk lengths becomes the default only if (1) on the small-file workload its worst repeat
+// beats the by-length arm's best at every shape and thread count, and (2) with uniform callers
+// (RS(10,4), 1 MiB chunks, 10 / 64 / 256 callers, where both values run the same batch code) no
+// arm's worst repeat lies outside the other's range by more than that arm's own spread.  (1) holds
+// everywhere, by 2.5-2.9 times at 10 threads and 20-27 times at 256
+// (profiles/small_files/percall_mixed.log).  (2) does not: 64 pageable callers gave 12.54-13.30
+// GB/s at 0 and 12.18-12.33 at 1 (profiles/small_files/percall_uniform.log), 0.36 below the
+// other's range with a spread of 0.15.  So unset = 0 and the path is reached through the knob.
+constexpr bool kCoalesceMixedDefault = false;
+inline bool gather_mixed() {
+    const int m = knobs().coalesce_mixed;
+    return m >= 0 ? m == 1 : kCoalesceMixedDefault;
+}
+
+// What the calls of one batch share.  `what`: the chunk length while cec_part_encode gathers by
+// length (CEC_COALESCE_MIXED=0), cec_part_read's mode, else 0.
 struct CoalesceKey {
     const void* codec;
-    size_t len;
+    size_t what;
     int device;
     bool operator==(const CoalesceKey& o) const {
-        return codec == o.codec && len == o.len && device == o.device;
+        return codec == o.codec && what == o.what && device == o.device;
     }
 };
 
@@ -232,8 +259,10 @@ struct ReqBase {
     std::condition_variable cv;     // this caller's wake-ups
 };
 
-// Impl: bytes(r) = input bytes; prepare(batch, arena) lays out + reserves; copy_in(r);
-// run(batch, arena) launches and waits; copy_out(r).
+// Impl: cap_bytes(r) = weight against the cap; prepare(batch, arena) lays out + reserves;
+// copy_in(r); run(batch, arena) launches and waits; copy_out(r); counters(), what its calls and
+// launches count into; arenas(), the pool its batches take their arena from (at most
+// knobs().coalesce_inflight in use per queue).
 // Wake-ups are targeted (one condition variable per request plus one for the leader) so a
 // batch of hundreds of callers costs O(batch) wake-ups, not O(batch^2).
 // One batch in flight: its size and copy counters, and the leader's wake-ups.
@@ -246,7 +275,7 @@ template <typename Req, typename Impl>
 class Coalescer {
    public:
     int submit(Req* r) {
-        g_calls.fetch_add(1, std::memory_order_relaxed);
+        Impl::counters().calls.fetch_add(1, std::memory_order_relaxed);
         std::unique_lock<std::mutex> lk(mu_);
         peak_ = std::max(peak_, ++callers_);
         queue_.push_back(r);
@@ -357,7 +386,7 @@ class Coalescer {
             peak_ = callers_;
             batches_since_peak_ = 0;
         }
-        Arena* arena = arenas_.take(key.device);
+        Arena* arena = Impl::arenas().take(key.device);
         gathering_ = false;
         if (trace)
             std::fprintf(stderr, "[cec coalesce] lead arena %p: %zu callers, %u active, %zu queued\n",
@@ -385,7 +414,7 @@ class Coalescer {
             lk.unlock();
             if (trace) std::fprintf(stderr, "[cec coalesce] arena %p: staged\n", (void*)arena);
             t2 = std::chrono::steady_clock::now();
-            g_launches.fetch_add(1, std::memory_order_relaxed);
+            Impl::counters().launches.fetch_add(1, std::memory_order_relaxed);
             st = Impl::run(batch, *arena);
             t3 = std::chrono::steady_clock::now();
         }
@@ -417,7 +446,7 @@ class Coalescer {
                          ms(t3, std::chrono::steady_clock::now()));
         }
         r->phase = Phase::Finished;
-        arenas_.give(key.device, arena);
+        Impl::arenas().give(key.device, arena);
         --active_;
         wake_next();
     }
@@ -433,7 +462,6 @@ class Coalescer {
     size_t peak_ = 0;                // most callers in progress at once, lately
     uint32_t batches_since_peak_ = 0;
     uint64_t last_run_us_ = 0;       // launch-to-results time of the last batch
-    ArenaPool arenas_;               // at most knobs().coalesce_inflight in use
 };
 
 // ---- cec_sha256(_many): one request = n buffers ----
@@ -445,7 +473,16 @@ struct ShaReq : ReqBase {
     CoalesceKey key() const { return {nullptr, 0, device}; }
 };
 
+// The arenas of the cec_sha256(_many) and the cec_part_encode queue: kept for the process.
+template <typename Tag>
+ArenaPool& own_arenas() {
+    static ArenaPool* pool = new ArenaPool();
+    return *pool;
+}
+
 struct ShaImpl {
+    static Counters& counters() { return g_write_counters; }
+    static ArenaPool& arenas() { return own_arenas<ShaImpl>(); }
     static size_t item_bytes(size_t len) { return round_up(std::max<size_t>(len, 1), kChunkAlign); }
     static size_t bytes(const ShaReq& r) {
         size_t b = 0;
@@ -522,20 +559,26 @@ struct PartReq : ReqBase {
     uint8_t* digests_out = nullptr;     // (d+p)*32 bytes
     // Page-locked caller buffers (cec_host_alloc): DMA'd directly, no copy-in / copy-out.
     bool in_pinned = false, out_pinned = false;
-    size_t out_off = 0;                 // parity offset in the pinned output staging
-    uint8_t* dev_dst = nullptr;         // this part's place in the device batch
+    plan::PartPlace at{};               // this part's places in the batch (percall_plan.hpp)
+    uint8_t* dbuf = nullptr;            // the batch's device buffer
     hipStream_t stream = nullptr;       // the batch's stream
-    CoalesceKey key() const { return {codec, L, device}; }
+    // Any lengths together, or (CEC_COALESCE_MIXED=0) one chunk length per batch.
+    CoalesceKey key() const { return {codec, gather_mixed() ? 0 : L, device}; }
 };
 
-// Pinned layout: input [part][d][cs] (staged parts only, at in_off), output [part][p][cs]
-// (staged parts only, at out_off) then digests [part][d+p][32]; device batch [part][d+p][cs]
-// (cs = L rounded up to 256 B).  A batch with no page-locked caller buffer moves with one
-// 2-D copy each way; otherwise every part is copied on its own (pinned ones straight from /
-// into the caller's memory).
+// The layout is plan::part_layout's (percall_plan.hpp).  A batch of one chunk length: pinned input
+// [part][d][cs] (staged parts only, at in_off), output [part][p][cs] (staged parts only, at
+// out_off) then digests [part][d+p][32]; device batch [part][d+p][cs] (cs = L rounded up to
+// 256 B), encoded by encode_hash_steps with the parity brought back early on a side stream.  A
+// batch of two or more lengths: the split layout, rows at L rounded up to 16, a data and a parity
+// region behind the digest block, encoded and hashed by ragged_launch (which has no hook for an
+// early parity download: it comes back behind the SHA-256 launch).  Either way a batch with no
+// page-locked caller buffer moves with one copy each way; otherwise every part is copied on its
+// own (pinned ones straight from / into the caller's memory).
 struct PartImpl {
-    static size_t cs_of(const PartReq& r) { return round_up(r.L, kChunkAlign); }
-    static size_t bytes(const PartReq& r) { return r.codec->d * cs_of(r); }
+    static Counters& counters() { return g_write_counters; }
+    static ArenaPool& arenas() { return own_arenas<PartImpl>(); }
+    static size_t bytes(const PartReq& r) { return r.codec->d * round_up(r.L, kChunkAlign); }
     // Weight against CEC_COALESCE_MAX_MIB: the cap bounds the pinned staging a batch needs; a
     // page-locked caller needs none, so its part counts a quarter (its batch is bounded by the
     // device buffer, 4x the staging cap).
@@ -547,28 +590,34 @@ struct PartImpl {
             if (r->in_pinned || r->out_pinned) return true;
         return false;
     }
+    static plan::PartTotals layout(const std::vector<PartReq*>& batch,
+                                   std::vector<plan::PartPlace>* at) {
+        const cec_codec* c = batch[0]->codec;
+        std::vector<plan::PartIn> in;
+        for (const PartReq* r : batch) in.push_back({r->L, r->in_pinned, r->out_pinned});
+        at->resize(batch.size());
+        plan::PartTotals tot{};
+        plan::part_layout(c->d, c->p, in.data(), in.size(), at->data(), &tot);
+        return tot;
+    }
     static int prepare(std::vector<PartReq*>& batch, Arena& a) {
         const cec_codec* c = batch[0]->codec;
-        const size_t d = c->d, p = c->p, t = d + p, B = batch.size(), cs = cs_of(*batch[0]);
-        size_t in_bytes = 0, out_bytes = 0;
-        for (size_t k = 0; k < B; ++k) {
+        const size_t d = c->d, p = c->p, t = d + p;
+        std::vector<plan::PartPlace> at;
+        const plan::PartTotals tot = layout(batch, &at);
+        const size_t cap = coalesce_max_bytes();
+        CEC_TRY(a.in.reserve(std::max<size_t>(tot.in_bytes, 1), cap));
+        CEC_TRY(a.out.reserve(tot.out_bytes + tot.dig_bytes,
+                              cap / d * p + (tot.mixed ? cap / 8 : cap / at[0].stride * t * 32)));
+        CEC_TRY(ctx_reserve(a.dev, tot.dev_bytes));
+        for (size_t k = 0; k < batch.size(); ++k) {
             PartReq* r = batch[k];
             r->arena = &a;
             r->slot = k;
-            r->in_off = in_bytes;
-            r->out_off = out_bytes;
-            if (!r->in_pinned) in_bytes += d * cs;
-            if (!r->out_pinned) out_bytes += p * cs;
-        }
-        const size_t dig0 = out_bytes;
-        for (PartReq* r : batch) r->item0 = dig0;  // locates the digest block
-        CEC_TRY(a.in.reserve(std::max<size_t>(in_bytes, 1), coalesce_max_bytes()));
-        CEC_TRY(a.out.reserve(out_bytes + B * t * 32,
-                              coalesce_max_bytes() / d * p + coalesce_max_bytes() / cs * t * 32));
-        CEC_TRY(ctx_reserve(a.dev, round_up(B * t * 32, kChunkAlign) + B * t * cs));
-        uint8_t* dbase = a.dev.dbuf + round_up(B * t * 32, kChunkAlign);
-        for (PartReq* r : batch) {
-            r->dev_dst = dbase + r->slot * t * cs;
+            r->at = at[k];
+            r->in_off = at[k].in_off;
+            r->item0 = tot.out_bytes;  // locates the digest block
+            r->dbuf = a.dev.dbuf;
             r->stream = a.dev.stream;
         }
         return CEC_OK;
@@ -576,26 +625,85 @@ struct PartImpl {
     // This part's upload into the device batch (from the caller's page-locked buffer or from its
     // copy in the pinned staging).
     static hipError_t upload(PartReq& r) {
-        const size_t d = r.codec->d, cs = cs_of(r);
+        const size_t d = r.codec->d, cs = r.at.stride;
+        uint8_t* dst = r.dbuf + r.at.dev_data;
         if (r.in_pinned && cs == r.L)
-            return hipMemcpyAsync(r.dev_dst, r.data_buf, d * r.L, hipMemcpyHostToDevice, r.stream);
+            return hipMemcpyAsync(dst, r.data_buf, d * r.L, hipMemcpyHostToDevice, r.stream);
         if (r.in_pinned)
-            return hipMemcpy2DAsync(r.dev_dst, cs, r.data_buf, r.L, r.L, d, hipMemcpyHostToDevice,
+            return hipMemcpy2DAsync(dst, cs, r.data_buf, r.L, r.L, d, hipMemcpyHostToDevice,
                                     r.stream);
-        return hipMemcpyAsync(r.dev_dst, r.arena->in.ptr + r.in_off, d * cs, hipMemcpyHostToDevice,
+        return hipMemcpyAsync(dst, r.arena->in.ptr + r.in_off, d * cs, hipMemcpyHostToDevice,
                               r.stream);
     }
+    // This part's parity back to its caller (or the staging) on stream `q`.
+    static hipError_t download(const PartReq& r, hipStream_t q) {
+        const size_t p = r.codec->p, cs = r.at.stride;
+        const uint8_t* src = r.dbuf + r.at.dev_parity;
+        if (r.out_pinned && cs == r.L)  // straight into the caller's parity buffer
+            return hipMemcpyAsync(r.parity_out, src, p * r.L, hipMemcpyDeviceToHost, q);
+        if (r.out_pinned)  // p rows of L bytes out of the padded chunk stride
+            return hipMemcpy2DAsync(r.parity_out, r.L, src, cs, r.L, p, hipMemcpyDeviceToHost, q);
+        return hipMemcpyAsync(r.arena->out.ptr + r.at.out_off, src, p * cs, hipMemcpyDeviceToHost,
+                              q);
+    }
+    // Each caller packs its own part: d rows of L bytes at the batch's row stride.  Nothing is
+    // zeroed: the kernels read exactly L bytes per chunk.
     static void copy_in(PartReq& r) {
         if (!r.in_pinned) {
-            const size_t d = r.codec->d, cs = cs_of(r);
+            const size_t d = r.codec->d, cs = r.at.stride;
             uint8_t* dst = r.arena->in.ptr + r.in_off;
             for (size_t j = 0; j < d; ++j) std::memcpy(dst + j * cs, r.data_buf + j * r.L, r.L);
         }
     }
     static int run(std::vector<PartReq*>& batch, Arena& a) {
+        std::vector<plan::PartPlace> at;
+        const plan::PartTotals tot = layout(batch, &at);
+        if (!tot.mixed) return run_uniform(batch, a);
+        g_mixed_batches.fetch_add(1, std::memory_order_relaxed);
+        const int st = run_mixed(batch, a, at, tot);
+        if (st != CEC_OK) {  // nothing of a failed batch stays in flight over the callers' buffers
+            (void)hipStreamSynchronize(a.dev.stream);
+            (void)hipGetLastError();
+        }
+        return st;
+    }
+    // Two or more chunk lengths: the split layout through ragged_launch.
+    static int run_mixed(std::vector<PartReq*>& batch, Arena& a,
+                         const std::vector<plan::PartPlace>& at, const plan::PartTotals& tot) {
+        cec_codec* c = batch[0]->codec;
+        const size_t B = batch.size();
+        const bool per_part = any_pinned(batch);
+        uint8_t* ddig = a.dev.dbuf;
+        uint8_t* ddata = a.dev.dbuf + tot.dev_data;
+        uint8_t* dpar = a.dev.dbuf + tot.dev_parity;
+        hipStream_t s = a.dev.stream;
+        std::vector<size_t> lens(B), doffs(B), poffs(B);
+        for (size_t k = 0; k < B; ++k) {
+            lens[k] = batch[k]->L;
+            doffs[k] = at[k].dev_data - tot.dev_data;
+            poffs[k] = at[k].dev_parity - tot.dev_parity;
+        }
+        CEC_TRY(split_check(c->d, c->p, ddata, doffs.data(), dpar, poffs.data(), lens.data(), B));
+        if (!per_part) {  // the staging's offsets are the data region's
+            HIP_TRY(hipMemcpyAsync(ddata, a.in.ptr, tot.in_bytes, hipMemcpyHostToDevice, s));
+        } else {
+            for (PartReq* r : batch) HIP_TRY(upload(*r));
+        }
+        CEC_TRY(ragged_launch(c, ddata, doffs.data(), dpar, poffs.data(), lens.data(), B, ddig, s));
+        if (!per_part) {
+            HIP_TRY(hipMemcpyAsync(a.out.ptr, dpar, tot.out_bytes, hipMemcpyDeviceToHost, s));
+        } else {
+            for (const PartReq* r : batch) HIP_TRY(download(*r, s));
+        }
+        HIP_TRY(hipMemcpyAsync(a.out.ptr + tot.out_bytes, ddig, tot.dig_bytes,
+                               hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return CEC_OK;
+    }
+    static int run_uniform(std::vector<PartReq*>& batch, Arena& a) {
         cec_codec* c = batch[0]->codec;
         const size_t d = c->d, p = c->p, t = d + p, B = batch.size();
-        const size_t L = batch[0]->L, cs = cs_of(*batch[0]);
+        const size_t L = batch[0]->L, cs = batch[0]->at.stride;
         const bool per_part = any_pinned(batch);
         uint32_t* drec = nullptr;
         CEC_TRY(c->encode_record(&drec));
@@ -615,17 +723,7 @@ struct PartImpl {
                                          hipMemcpyDeviceToHost, q));
                 return CEC_OK;
             }
-            for (const PartReq* r : batch) {
-                const uint8_t* src = dbase + r->slot * t * cs + d * cs;
-                if (r->out_pinned && cs == L)  // straight into the caller's parity buffer
-                    HIP_TRY(hipMemcpyAsync(r->parity_out, src, p * L, hipMemcpyDeviceToHost, q));
-                else if (r->out_pinned)  // p rows of L bytes out of the padded chunk stride
-                    HIP_TRY(hipMemcpy2DAsync(r->parity_out, r->L, src, cs, r->L, p,
-                                             hipMemcpyDeviceToHost, q));
-                else
-                    HIP_TRY(hipMemcpyAsync(a.out.ptr + r->out_off, src, p * cs,
-                                           hipMemcpyDeviceToHost, q));
-            }
+            for (const PartReq* r : batch) HIP_TRY(download(*r, q));
             return CEC_OK;
         };
         // an error return after the side-stream download was queued must not leave it writing
@@ -665,17 +763,93 @@ struct PartImpl {
         return CEC_OK;
     }
     static void copy_out(PartReq& r) {
-        const size_t d = r.codec->d, p = r.codec->p, t = d + p, cs = cs_of(r);
+        const size_t d = r.codec->d, p = r.codec->p, t = d + p, cs = r.at.stride;
         if (!r.out_pinned) {
-            const uint8_t* par = r.arena->out.ptr + r.out_off;
+            const uint8_t* par = r.arena->out.ptr + r.at.out_off;
             for (size_t i = 0; i < p; ++i) std::memcpy(r.parity_out + i * r.L, par + i * cs, r.L);
         }
-        std::memcpy(r.digests_out, r.arena->out.ptr + r.item0 + r.slot * t * 32, t * 32);
+        std::memcpy(r.digests_out, r.arena->out.ptr + r.item0 + r.at.dig_off, t * 32);
+    }
+};
+
+// ---- cec_part_read: one request = one part (its d+p slots, flags and expected digests) ----
+// What the calls of one batch share: the round's place in the arena and the batch's arrays in
+// cec_parts_read's form, filled by the callers (copy-in) and the launch.
+struct ReadShared {
+    Round round;
+    std::vector<size_t> lens;
+    std::vector<uint8_t> present, verified;
+    std::vector<int> status;
+};
+
+struct ReadReq : ReqBase {
+    cec_codec* codec = nullptr;
+    uint8_t* const* shards = nullptr;   // d+p slots of L bytes
+    size_t L = 0;
+    const uint8_t* present = nullptr;   // d+p flags
+    const uint8_t* expected = nullptr;  // (d+p)*32 bytes
+    bool data_only = true;
+    uint8_t* verified = nullptr;        // d+p flags, written
+    int part_status = CEC_OK;           // CEC_OK or CEC_TOO_FEW_SHARDS_PRESENT
+    std::shared_ptr<ReadShared> sh;
+    CoalesceKey key() const { return {codec, data_only ? 1u : 0u, device}; }
+};
+
+// The steps of cec_parts_read's round (ragged.cpp, through capi_internal.hpp) with the staging
+// and the collecting done by each caller for its own part.  Page-locked shard buffers are staged
+// like pageable ones.
+struct ReadImpl {
+    static Counters& counters() { return g_read_counters; }
+    static ArenaPool& arenas() { return ragged_arenas(); }
+    // As cec_parts_read's rounds: the cap counts the (padded) data chunks.
+    static size_t cap_bytes(const ReadReq& r) { return r.codec->d * ragged_stride(r.L); }
+    static int prepare(std::vector<ReadReq*>& batch, Arena& a) {
+        const cec_codec* c = batch[0]->codec;
+        const size_t t = c->d + c->p, B = batch.size();
+        auto sh = std::make_shared<ReadShared>();
+        for (const ReadReq* r : batch) sh->lens.push_back(r->L);
+        sh->present.resize(B * t);
+        sh->verified.resize(B * t);
+        sh->status.resize(B);
+        CEC_TRY(reserve_round(a, c->d, t, sh->lens.data(), B, &sh->round));
+        for (size_t k = 0; k < B; ++k) {
+            batch[k]->arena = &a;
+            batch[k]->slot = k;
+            batch[k]->sh = sh;
+        }
+        return CEC_OK;
+    }
+    static void copy_in(ReadReq& r) {
+        const size_t t = r.codec->d + r.codec->p;
+        std::memcpy(r.sh->present.data() + r.slot * t, r.present, t);
+        std::memcpy(r.arena->out.ptr + r.slot * t * 32, r.expected, t * 32);
+        read_round_stage(r.sh->round, r.slot, t, r.L, r.shards, r.present);
+    }
+    static int run(std::vector<ReadReq*>& batch, Arena& a) {
+        ReadReq& r = *batch[0];
+        ReadShared& sh = *r.sh;
+        const int st = read_round_launch(r.codec, a, sh.round, sh.lens.data(), batch.size(),
+                                         sh.present.data(), r.data_only, sh.verified.data(),
+                                         sh.status.data());
+        if (st != CEC_OK && a.dev.stream) {  // nothing of a failed round stays in flight
+            (void)hipStreamSynchronize(a.dev.stream);
+            (void)hipGetLastError();
+        }
+        return st;
+    }
+    static void copy_out(ReadReq& r) {
+        const size_t d = r.codec->d, t = d + r.codec->p;
+        const uint8_t* ver = r.sh->verified.data() + r.slot * t;
+        r.part_status = r.sh->status[r.slot];
+        read_round_collect(r.sh->round, r.slot, d, t, r.L, r.shards, ver, r.part_status,
+                           r.data_only);
+        std::memcpy(r.verified, ver, t);
     }
 };
 
 Coalescer<ShaReq, ShaImpl> g_sha_queue;
 Coalescer<PartReq, PartImpl> g_part_queue;
+Coalescer<ReadReq, ReadImpl> g_read_queue;
 
 int sha256_coalesced(const uint8_t* const* bufs, const size_t* lens, size_t n, uint8_t* out) {
     ShaReq r;
@@ -779,9 +953,48 @@ int cec_part_encode(const cec_codec* cc, const uint8_t* data_buf, size_t length,
     return CEC_OK;
 }
 
+int cec_part_read(const cec_codec* cc, uint8_t* const* shards, size_t chunk_len,
+                  const uint8_t* present, const uint8_t* expected, int data_only,
+                  uint8_t* verified) {
+    if (!cc || !shards || !present || !expected || !verified) return CEC_ERR_INVALID_ARGUMENT;
+    if (chunk_len == 0) return CEC_EMPTY_SHARD;
+    const size_t d = cc->d, t = cc->d + cc->p;
+    // cec_parts_read's rule: a loaded chunk needs its bytes; a part that can be decoded (d or more
+    // chunks loaded) needs memory behind every slot the mode fills.
+    size_t loaded = 0;
+    for (size_t i = 0; i < t; ++i) loaded += present[i] ? 1 : 0;
+    for (size_t i = 0; i < t; ++i) {
+        const bool need = present[i] || (loaded >= d && fills_slot(i, d, data_only != 0));
+        if (need && !shards[i]) {
+            set_last_error("cec_part_read: a chunk slot that is read or filled is NULL");
+            return CEC_ERR_INVALID_ARGUMENT;
+        }
+    }
+    if (!ragged_stride(chunk_len) || ragged_stride(chunk_len) > SIZE_MAX / t)
+        return CEC_ERR_INVALID_ARGUMENT;
+    ReadReq r;
+    CEC_TRY(current_device(&r.device));
+    r.codec = const_cast<cec_codec*>(cc);
+    r.shards = shards;
+    r.L = chunk_len;
+    r.present = present;
+    r.expected = expected;
+    r.data_only = data_only != 0;
+    r.verified = verified;
+    CEC_TRY(g_read_queue.submit(&r));
+    return r.part_status;
+}
+
 void cec_coalesce_stats(uint64_t* calls, uint64_t* launches) {
-    if (calls) *calls = g_calls.load();
-    if (launches) *launches = g_launches.load();
+    if (calls) *calls = g_write_counters.calls.load();
+    if (launches) *launches = g_write_counters.launches.load();
+}
+
+void cec_coalesce_detail(uint64_t* part_mixed_batches, uint64_t* read_calls,
+                         uint64_t* read_launches) {
+    if (part_mixed_batches) *part_mixed_batches = g_mixed_batches.load();
+    if (read_calls) *read_calls = g_read_counters.calls.load();
+    if (read_launches) *read_launches = g_read_counters.launches.load();
 }
 
 size_t cec_release_cached(int device) { return CtxPool::get().trim(device); }

@@ -19,30 +19,18 @@ using namespace cec;
 
 namespace {
 
-constexpr size_t kRaggedAlign = 16;
+constexpr size_t kRaggedAlign = plan::kRaggedAlign;
 
 }  // namespace
 
 // L rounded up to 16; 0 when that overflows (and for an empty chunk, which every caller refuses
 // before it asks).
-size_t cec::ragged_stride(size_t L) {
-    return L > SIZE_MAX - (kRaggedAlign - 1) ? 0 : round_up(L, kRaggedAlign);
-}
+size_t cec::ragged_stride(size_t L) { return plan::stride16(L); }
 
-// The packed layout: part k+1 directly behind part k.
+// The packed layout: part k+1 directly behind part k (the rule itself: percall_plan.hpp).
 int cec::ragged_layout(size_t t, const size_t* lens, size_t n, size_t* offs, size_t* total) {
-    size_t off = 0;
-    for (size_t k = 0; k < n; ++k) {
-        if (lens[k] == 0) return CEC_EMPTY_SHARD;
-        const size_t cs = ragged_stride(lens[k]);
-        size_t span = 0;
-        if (!cs || __builtin_mul_overflow(t, cs, &span) || span > SIZE_MAX - off)
-            return CEC_ERR_INVALID_ARGUMENT;
-        offs[k] = off;
-        off += span;
-    }
-    *total = off;
-    return CEC_OK;
+    const int st = plan::packed_layout(t, lens, n, offs, total);
+    return st == 0 ? CEC_OK : st == 1 ? CEC_EMPTY_SHARD : CEC_ERR_INVALID_ARGUMENT;
 }
 
 namespace {
@@ -601,11 +589,15 @@ int read_ragged_checked(const cec_codec* cc, uint8_t* base, const size_t* offs, 
 // arena's pinned staging in the cec_ragged_layout layout, moved up, worked on as above, results
 // copied out.
 
-// Their arenas: one per call in flight.
-ArenaPool& ragged_arenas() {
+}  // namespace
+
+// Their arenas: one per call in flight (and per batch of cec_part_read calls, percall.cpp).
+ArenaPool& cec::ragged_arenas() {
     static ArenaPool* pool = new ArenaPool();
     return *pool;
 }
+
+namespace {
 
 // fn(k) for k < n on up to 8 threads: one per 16 MiB of `bytes` moved, so a call of a few small
 // parts never starts one.
@@ -686,18 +678,8 @@ int cec::copy_spans(uint8_t* stage, uint8_t* dbase, const Spans& spans, bool to_
     return CEC_OK;
 }
 
-namespace {
-
-// One round's place in an arena: the packed layout of its n parts, `stage` (pinned) and `dbase`
-// (device) sharing those offsets, and `dside`, device room for the round's n * t digests, with
-// the arena's `out` as its pinned side.
-struct Round {
-    std::vector<size_t> offs;
-    uint8_t *stage, *dside, *dbase;
-    hipStream_t s;
-};
-
-int reserve_round(Arena& a, size_t d, size_t t, const size_t* chunk_lens, size_t n, Round* r) {
+// One round's place in an arena (Round, capi_internal.hpp).
+int cec::reserve_round(Arena& a, size_t d, size_t t, const size_t* chunk_lens, size_t n, Round* r) {
     r->offs.resize(n);
     size_t total = 0;
     CEC_TRY(ragged_layout(t, chunk_lens, n, r->offs.data(), &total));
@@ -712,6 +694,8 @@ int reserve_round(Arena& a, size_t d, size_t t, const size_t* chunk_lens, size_t
     r->s = a.dev.stream;
     return CEC_OK;
 }
+
+namespace {
 
 // The rounds of a host-staged call over parts of d data chunks among t, of these chunk lengths:
 // at most CEC_COALESCE_MAX_MIB of (padded) data chunks each, a larger part alone.  Every round is
@@ -792,55 +776,70 @@ int parts_round(cec_codec* c, Arena& a, const uint8_t* const* bufs, const size_t
     return CEC_OK;
 }
 
-// One round of cec_parts_read: parts [0, n) of these arrays.  The loaded chunks are packed into
-// the arena and moved up, verified and rebuilt as in cec_read_ragged, and only the rebuilt chunks
-// come back, into the caller's slots.
+}  // namespace
+
+// The steps of one round of a host-staged read (capi_internal.hpp).  The loaded chunks are packed
+// into the arena and moved up, verified and rebuilt as in cec_read_ragged, and only the rebuilt
+// chunks come back, into the caller's slots.
+void cec::read_round_stage(const Round& r, size_t k, size_t t, size_t L, uint8_t* const* shards,
+                           const uint8_t* present) {
+    const size_t cs = ragged_stride(L);
+    for (size_t i = 0; i < t; ++i)
+        if (present[i]) std::memcpy(r.stage + r.offs[k] + i * cs, shards[i], L);
+}
+
+int cec::read_round_launch(cec_codec* c, Arena& a, const Round& r, const size_t* chunk_lens,
+                           size_t n, const uint8_t* present, bool data_only, uint8_t* verified,
+                           int* part_status) {
+    const size_t d = c->d, t = c->d + c->p, items = n * t;
+    Spans spans;
+    plan::loaded_spans(t, chunk_lens, r.offs.data(), n, present, &spans);
+    HIP_TRY(hipMemcpyAsync(r.dside, a.out.ptr, items * 32, hipMemcpyHostToDevice, r.s));
+    CEC_TRY(copy_spans(r.stage, r.dbase, spans, true, r.s));
+    CEC_TRY(read_ragged(c, r.dbase, r.offs.data(), chunk_lens, n, present, r.dside, verified,
+                        part_status, data_only, r.s));
+    // what the rebuild wrote: in a decodable part, every slot of the mode that did not verify
+    spans.clear();
+    plan::rebuilt_spans(d, t, chunk_lens, r.offs.data(), n, verified, part_status, data_only,
+                        &spans);
+    CEC_TRY(copy_spans(r.stage, r.dbase, spans, false, r.s));
+    HIP_TRY(hipStreamSynchronize(r.s));
+    return CEC_OK;
+}
+
+void cec::read_round_collect(const Round& r, size_t k, size_t d, size_t t, size_t L,
+                             uint8_t* const* shards, const uint8_t* verified, int part_status,
+                             bool data_only) {
+    const size_t cs = ragged_stride(L);
+    for (size_t i = 0; i < t; ++i)
+        if (plan::rebuilt_slot(i, d, data_only, verified[i], part_status))
+            std::memcpy(shards[i], r.stage + r.offs[k] + i * cs, L);
+}
+
+namespace {
+
+// One round of cec_parts_read: parts [0, n) of these arrays, through the steps above.
 int parts_read_round(cec_codec* c, Arena& a, uint8_t* const* shards, const size_t* chunk_lens,
                      size_t n, const uint8_t* present, const uint8_t* expected, bool data_only,
                      uint8_t* verified, int* part_status) {
     const size_t d = c->d, t = c->d + c->p, items = n * t;
     Round r;
     CEC_TRY(reserve_round(a, d, t, chunk_lens, n, &r));
-    // fn(item, its offset in the arena, L) for every chunk slot i of part k that passes pick(k, i)
-    auto slots = [&](size_t k, auto pick, auto fn) {
-        const size_t L = chunk_lens[k], cs = ragged_stride(L);
-        for (size_t i = 0; i < t; ++i)
-            if (pick(k, i)) fn(k * t + i, r.offs[k] + i * cs, L);
-    };
-    auto spans_of = [&](auto pick, Spans* spans) {
-        size_t bytes = 0;
-        for (size_t k = 0; k < n; ++k)
-            slots(k, pick, [&](size_t, size_t off, size_t L) {
-                spans->emplace_back(off, off + L);
-                bytes += L;
-            });
-        return bytes;
-    };
-    auto loaded = [&](size_t k, size_t i) { return present[k * t + i] != 0; };
-    Spans spans;
-    const size_t in_bytes = spans_of(loaded, &spans);
+    size_t in_bytes = 0, out_bytes = 0;
+    for (size_t k = 0; k < n; ++k)
+        for (size_t i = 0; i < t; ++i) in_bytes += present[k * t + i] ? chunk_lens[k] : 0;
     for_parts(n, in_bytes, [&](size_t k) {
-        slots(k, loaded, [&](size_t item, size_t off, size_t L) {
-            std::memcpy(r.stage + off, shards[item], L);
-        });
+        read_round_stage(r, k, t, chunk_lens[k], shards + k * t, present + k * t);
     });
     std::memcpy(a.out.ptr, expected, items * 32);
-    HIP_TRY(hipMemcpyAsync(r.dside, a.out.ptr, items * 32, hipMemcpyHostToDevice, r.s));
-    CEC_TRY(copy_spans(r.stage, r.dbase, spans, true, r.s));
-    CEC_TRY(read_ragged(c, r.dbase, r.offs.data(), chunk_lens, n, present, r.dside, verified,
-                        part_status, data_only, r.s));
-    // what the rebuild wrote: in a decodable part, every slot of the mode that did not verify
-    auto rebuilt = [&](size_t k, size_t i) {
-        return part_status[k] == CEC_OK && !verified[k * t + i] && fills_slot(i, d, data_only);
-    };
-    spans.clear();
-    const size_t out_bytes = spans_of(rebuilt, &spans);
-    CEC_TRY(copy_spans(r.stage, r.dbase, spans, false, r.s));
-    HIP_TRY(hipStreamSynchronize(r.s));
+    CEC_TRY(read_round_launch(c, a, r, chunk_lens, n, present, data_only, verified, part_status));
+    for (size_t k = 0; k < n; ++k)
+        for (size_t i = 0; i < t; ++i)
+            if (plan::rebuilt_slot(i, d, data_only, verified[k * t + i], part_status[k]))
+                out_bytes += chunk_lens[k];
     for_parts(n, out_bytes, [&](size_t k) {
-        slots(k, rebuilt, [&](size_t item, size_t off, size_t L) {
-            std::memcpy(shards[item], r.stage + off, L);
-        });
+        read_round_collect(r, k, d, t, chunk_lens[k], shards + k * t, verified + k * t,
+                           part_status[k], data_only);
     });
     return CEC_OK;
 }

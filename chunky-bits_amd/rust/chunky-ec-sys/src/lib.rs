@@ -209,6 +209,15 @@ pub mod sys {
             verified: *mut u8,
             part_status: *mut c_int,
         ) -> c_int;
+        pub fn cec_part_read(
+            codec: *const cec_codec,
+            shards: *const *mut u8,
+            chunk_len: usize,
+            present: *const u8,
+            expected: *const u8,
+            data_only: c_int,
+            verified: *mut u8,
+        ) -> c_int;
         pub fn cec_parts_verify(
             bufs: *const *const u8,
             lens: *const usize,
@@ -414,6 +423,11 @@ pub mod sys {
             capacity: usize,
         ) -> c_int;
         pub fn cec_coalesce_stats(calls: *mut u64, launches: *mut u64);
+        pub fn cec_coalesce_detail(
+            part_mixed_batches: *mut u64,
+            read_calls: *mut u64,
+            read_launches: *mut u64,
+        );
         pub fn cec_ragged_stats(fused: *mut u64, two_pass: *mut u64);
         pub fn cec_build_info() -> *const std::os::raw::c_char;
         pub fn cec_build_id() -> *const std::os::raw::c_char;
@@ -1323,6 +1337,58 @@ pub fn parts_read(
         )
     })?;
     Ok((verified, status))
+}
+
+/// `cec_part_read`: [`parts_read`] for one part, coalesced: `FilePart::read_with_context`'s
+/// (`data_only`) or `FilePart::resilver`'s compute in one call per part task; concurrent calls
+/// with one codec and one mode share a launch whatever their chunk lengths.  `shards[i]` is a
+/// loaded chunk (`present[i]` nonzero) of `chunk_len` bytes, or a buffer of that size the engine
+/// fills when it rebuilds the chunk; `expected` is `[d+p][32]`.  Returns the verified flags and the
+/// part's status, 0 or 10 (`TooFewShardsPresent`: nothing was rebuilt, the flags are filled).
+pub fn part_read(
+    codec: &ReedSolomon,
+    shards: &mut [&mut [u8]],
+    chunk_len: usize,
+    present: &[u8],
+    expected: &[u8],
+    data_only: bool,
+) -> Result<(Vec<u8>, c_int), CecError> {
+    let t = codec.data_shard_count() + codec.parity_shard_count();
+    if shards.len() != t
+        || present.len() != t
+        || expected.len() != t * 32
+        || !shards.iter().all(|s| s.len() >= chunk_len)
+    {
+        return Err(CecError::Engine(EngineError {
+            code: 101,
+            message: "shards, present and expected differ in length".to_string(),
+        }));
+    }
+    let ptrs: Vec<*mut u8> = shards.iter_mut().map(|s| s.as_mut_ptr()).collect();
+    let mut verified = vec![0u8; t];
+    let code = unsafe {
+        sys::cec_part_read(
+            codec.raw,
+            ptrs.as_ptr(),
+            chunk_len,
+            present.as_ptr(),
+            expected.as_ptr(),
+            data_only as c_int,
+            verified.as_mut_ptr(),
+        )
+    };
+    if code != 0 && code != 10 {
+        check(code)?;
+    }
+    Ok((verified, code))
+}
+
+/// The per-call coalescing path's detail counters (`cec_coalesce_detail`): (`part_encode` batches
+/// of two or more chunk lengths, `part_read` calls, `part_read` launches).
+pub fn coalesce_detail() -> (u64, u64, u64) {
+    let (mut mixed, mut calls, mut launches) = (0u64, 0u64, 0u64);
+    unsafe { sys::cec_coalesce_detail(&mut mixed, &mut calls, &mut launches) };
+    (mixed, calls, launches)
 }
 
 /// `cec_verify_ragged`: the verification half of [`read_ragged`] alone (`FilePart::verify`'s

@@ -229,6 +229,29 @@ int cec_parts_read(const cec_codec* codec, uint8_t* const* shards, const size_t*
                    size_t n_parts, const uint8_t* present, const uint8_t* expected,
                    int data_only, uint8_t* verified, int* part_status);
 
+/* cec_parts_read for ONE part, coalesced: FilePart::read_with_context's compute (data_only = 1;
+ * file_part.rs:86-129: the drawn copies hashed and compared, reconstruct_data over the verified
+ * ones) or FilePart::resilver's (0; file_part.rs:266-308) in one call per FilePart task, the read
+ * counterpart of cec_part_encode.  shards, present, expected ([d+p][32], host) and verified
+ * ([d+p], host) are cec_parts_read's arrays for n_parts = 1 and chunk_len its chunk_lens[0]: the
+ * same bytes in the same slots, the same verified flags, the same treatment of
+ * CEC_PRESENT_VERIFIED; a loaded chunk that failed in a decodable part is rebuilt into its own
+ * slot if the mode fills it, and nothing is written for a part short of d verified chunks.
+ * Returns the part's status, CEC_OK or CEC_TOO_FEW_SHARDS_PRESENT, with verified filled in both
+ * cases (the retry round needs it); any other code leaves verified and every slot untouched.
+ * Checks, in this order and all before any queueing or device use: a null pointer ->
+ * CEC_ERR_INVALID_ARGUMENT; chunk_len == 0 -> CEC_EMPTY_SHARD; a NULL slot that is read or filled
+ * (cec_parts_read's rule) -> CEC_ERR_INVALID_ARGUMENT; then CEC_ERR_NO_DEVICE.
+ * Concurrent calls with one codec and one mode on one device, whatever their chunk lengths, are
+ * gathered into one round of cec_parts_read's own steps (see "Per-call coalescing" below): each
+ * caller packs its loaded chunks into the round's staging, one caller moves them up, runs the
+ * verification and the rebuild (the host-planned read: every (d, p)) and brings the rebuilt chunks
+ * back, and each caller copies its own out.  The staging is cec_parts_read's (no further pinned
+ * memory).  Page-locked shard buffers are staged like pageable ones in this version. */
+int cec_part_read(const cec_codec* codec, uint8_t* const* shards, size_t chunk_len,
+                  const uint8_t* present, const uint8_t* expected, int data_only,
+                  uint8_t* verified);
+
 /* FilePart::verify's compute (file_part.rs:228-251: every location's copy of every chunk hashed
  * and compared) for a flat list of n chunk copies of unrelated lengths in one call:
  * ok[i] = 1 iff SHA-256(bufs[i][0..lens[i])) == expected[i*32 .. +32].  expected is a HOST array
@@ -245,13 +268,24 @@ int cec_parts_verify(const uint8_t* const* bufs, const size_t* lens, size_t n,
                      const uint8_t* expected, uint8_t* ok);
 
 /* Per-call coalescing.  Concurrent cec_part_encode calls with the same codec and chunk length
- * (and concurrent cec_sha256 / cec_sha256_many calls) on the same device are gathered into one
- * launch: the first caller waits up to CEC_COALESCE_US microseconds (environment, default 200,
- * 0 = off) for others, runs the whole batch and wakes them with their results.  A lone GPU
- * SHA-256 lane hashes ~25 MB/s (a serial chain), so the reference's per-part calls only pay off
- * when their concurrency becomes batch width.  Results are identical either way.
- * cec_coalesce_stats: calls made and launches issued through this path since load. */
+ * (any chunk lengths under CEC_COALESCE_MIXED=1, below; and concurrent cec_sha256 /
+ * cec_sha256_many calls, and concurrent cec_part_read calls with the same codec and mode,
+ * whatever their chunk lengths) on the same device are gathered into one launch: the first caller waits up to
+ * CEC_COALESCE_US microseconds (environment, default 200, 0 = off) for others, runs the whole
+ * batch and wakes them with their results.  A lone GPU SHA-256 lane hashes ~25 MB/s (a serial
+ * chain), so the reference's per-part calls only pay off when their concurrency becomes batch
+ * width.  Results are identical either way.
+ * cec_part_encode calls of different chunk lengths: with CEC_COALESCE_MIXED=1 (environment, a
+ * test and A/B knob; 0 or unset: one chunk length per batch) they share a batch, laid out in the
+ * cec_split_layout layout and run by the launches of cec_encode_hash_split; a batch whose calls
+ * all have one chunk length runs as without the knob.
+ * cec_coalesce_stats: cec_part_encode and cec_sha256(_many) calls made and launches issued
+ * through this path since load.  cec_coalesce_detail: the cec_part_encode batches of two or more
+ * chunk lengths among those launches, and the cec_part_read calls made and launches issued
+ * (process-wide; any pointer may be null). */
 void cec_coalesce_stats(uint64_t* calls, uint64_t* launches);
+void cec_coalesce_detail(uint64_t* part_mixed_batches, uint64_t* read_calls,
+                         uint64_t* read_launches);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Device-resident batch API (inputs already in HBM; asynchronous on `stream`)              */

@@ -426,6 +426,18 @@ inline cec_parts_reader* cached_parts_reader(size_t d, size_t p, size_t slot_byt
     }
     return e.reader.get();
 }
+
+// One codec per shape for the whole process (FilePart::read_coalesced): concurrent per-part
+// calls share a launch only when they pass the same codec.  Kept for the life of the process.
+inline const ReedSolomon& shared_codec(size_t d, size_t p) {
+    static std::mutex mu;
+    static std::map<std::pair<size_t, size_t>, std::unique_ptr<ReedSolomon>>* codecs =
+        new std::map<std::pair<size_t, size_t>, std::unique_ptr<ReedSolomon>>();
+    std::lock_guard<std::mutex> lk(mu);
+    std::unique_ptr<ReedSolomon>& c = (*codecs)[{d, p}];
+    if (!c) c = std::make_unique<ReedSolomon>(d, p);
+    return *c;
+}
 }  // namespace detail
 
 // file::hash::Sha256Hash.
@@ -709,6 +721,55 @@ struct FilePart {
         out.reserve(len_bytes());
         for (size_t i = 0; i < d; ++i) out.insert(out.end(), all[i]->begin(), all[i]->end());
         return out;
+    }
+
+    // read_with_context with each round's compute in ONE engine call (cec_part_read: the drawn
+    // copies hashed, compared and, once d verify, the missing data rebuilt), which concurrent
+    // readers of one shape share whatever their chunk sizes: the same draw loop (FilePart::draw),
+    // the freshly drawn copies flagged 1 and the copies verified in earlier rounds
+    // CEC_PRESENT_VERIFIED, the data chunks loaded and rebuilt in place in the result.  The same
+    // bytes and the same failure (TooFewShardsPresent when the copies run out).
+    Bytes read_coalesced(const ChunkStore& src) const {
+        const size_t d = data.size(), p = parity.size(), t = d + p, L = chunksize;
+        if (L == 0) return read_with_context(src);  // nothing to hash or rebuild in one call
+        const ReedSolomon& codec = detail::shared_codec(d, p);
+        std::vector<uint8_t> good(t), tried(t), exhausted(t), present(t), verified(t);
+        std::vector<uint8_t> expected(t * 32);
+        std::vector<size_t> cursor(t);
+        Bytes out(d * L);
+        std::vector<Bytes> par(p);  // a parity chunk's bytes once it was drawn
+        auto slot = [&](size_t i) {
+            if (i < d) return out.data() + i * L;
+            if (par[i - d].size() != L) par[i - d].resize(L);
+            return par[i - d].data();
+        };
+        for (size_t i = 0; i < t; ++i)
+            std::memcpy(&expected[i * 32], chunk(i).hash.digest().data(), 32);
+        size_t have = 0;
+        for (;;) {
+            std::fill(present.begin(), present.end(), uint8_t(0));
+            const size_t added = draw(src, good.data(), tried.data(), exhausted.data(),
+                                      cursor.data(), have, [&](size_t i, const Bytes* b) {
+                                          std::memcpy(slot(i), b->data(), L);
+                                          present[i] = 1;
+                                      });
+            if (added == 0) throw ErasureError(Error::TooFewShardsPresent);
+            std::vector<uint8_t*> shards(t, nullptr);
+            for (size_t i = 0; i < t; ++i) {
+                if (good[i]) present[i] = CEC_PRESENT_VERIFIED;
+                // data slots are the result's own bytes; parity is read only when loaded
+                if (i < d || present[i]) shards[i] = slot(i);
+            }
+            const int st = cec_part_read(codec.raw(), shards.data(), L, present.data(),
+                                         expected.data(), 1, verified.data());
+            if (st != CEC_OK && st != CEC_TOO_FEW_SHARDS_PRESENT) detail::check(st);
+            for (size_t i = 0; i < t; ++i)
+                if (verified[i] && !good[i]) {
+                    good[i] = 1;
+                    ++have;
+                }
+            if (st == CEC_OK) return out;
+        }
     }
 
     // verify (file_part.rs:228-251): every location of every chunk read and its copy checked

@@ -5,7 +5,9 @@ them (about 2 GiB), cut into parts of d x 1 MiB as FileWriteBuilder does, for RS
 RS(10,4).  Three arms produce the same parts:
 
   a  the per-part way: cec_part_encode per part from 10 and from 256 threads (the padded copy of
-     each part that call needs is made before the clock starts)
+     each part that call needs is made before the clock starts), each with CEC_COALESCE_MIXED 0
+     (one chunk length per coalesced batch) and 1 (any lengths together); --per-part-only runs
+     these arms alone
   b  one cec_parts_encode call over all parts, straight from the files' bytes
   c  the CPU oracle (the crate's path restated in C) on 16 threads
   d  the parts pipeline: cec_parts_pipeline_submit_from per slot-sized batch of consecutive
@@ -33,7 +35,8 @@ encodes it and its data chunk k % d is erased, so every part is decoded from d -
 the first parity chunk:
 
   a  the per-part way from 10 and from 256 threads: cec_sha256_many over the d loaded chunks,
-     the digests compared, then cec_reconstruct_data
+     the digests compared, then cec_reconstruct_data; and the same in one call per part,
+     cec_part_read
   b  one cec_parts_read call over all parts
   c  the CPU oracle on 16 threads (SHA-256 of the d loaded chunks, reconstruct_data)
   d  the parts reader: cec_parts_reader_submit_from per slot-sized batch of consecutive parts
@@ -237,6 +240,42 @@ class Workload:
         return dig
 
 
+def set_env_knob(name, value):
+    """CEC_* knob `name` = value (None: unset) from the next call on."""
+    if value is None:
+        os.environ.pop(name, None)
+    else:
+        os.environ[name] = value
+    ce.reload_knobs()
+
+
+MIXED = "CEC_COALESCE_MIXED"
+
+
+def with_mixed(value, fn):
+    """fn() with CEC_COALESCE_MIXED = value, the knob restored behind it."""
+    before = os.environ.get(MIXED)
+    set_env_knob(MIXED, value)
+    try:
+        return fn()
+    finally:
+        set_env_knob(MIXED, before)
+
+
+def mixed_verdict(secs, threads, row):
+    """The rule of DESIGN.md 4.6 for one thread count: mixed gathering's worst repeat against the
+    by-length arm's best."""
+    by_len = secs[f"a: part_encode x {threads} threads, by length"]
+    mixed = secs[f"a: part_encode x {threads} threads, mixed"]
+    wins = max(mixed) < min(by_len)
+    row[f"mixed_vs_by_length_{threads}"] = {"by_length_best_s": min(by_len),
+                                            "mixed_worst_s": max(mixed), "mixed_wins": wins}
+    print(f"   mixed vs by length, {threads} threads: by length {min(by_len):.3f}-{max(by_len):.3f} s, "
+          f"mixed {min(mixed):.3f}-{max(mixed):.3f} s -> mixed's worst beats by-length's best: {wins}",
+          flush=True)
+    return wins
+
+
 def timed(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -253,13 +292,18 @@ def host_staged(args):
         w = Workload(pool, files, d, p)
         print(f"== RS({d},{p}) chunk 1 MiB: {len(files)} files, {w.file_bytes / 2**30:.2f} GiB, "
               f"{w.n} parts, {len(set(w.L))} distinct chunk lengths", flush=True)
-        arms = [("a: part_encode x 10 threads", lambda c=None: w.arm_percall(10, c)),
-                ("a: part_encode x 256 threads", lambda c=None: w.arm_percall(256, c)),
-                ("b: one parts_encode call", lambda c=None: w.arm_ragged(c)),
-                ("c: CPU oracle x 16 threads", lambda c=None: w.arm_cpu(16, c))]
+        # the per-part arms under both values of CEC_COALESCE_MIXED, alternating
+        arms = [(f"a: part_encode x {th} threads, {how}",
+                 lambda c=None, th=th, knob=knob: with_mixed(knob, lambda: w.arm_percall(th, c)))
+                for th in (10, 256) for knob, how in (("0", "by length"), ("1", "mixed"))]
+        arms += [("b: one parts_encode call", lambda c=None: w.arm_ragged(c)),
+                 ("c: CPU oracle x 16 threads", lambda c=None: w.arm_cpu(16, c))]
         slot = args.slot_mib << 20
         if args.no_per_part:  # a quick look at arm d: the per-part arms take most of a run
             arms = [arm for arm in arms if not arm[0].startswith("a")]
+        if args.per_part_only:  # the A/B of the per-part arms alone
+            arms = [arm for arm in arms if arm[0].startswith("a")]
+            args.depths = []
         pipes = {depth: w.make_pipeline(slot, depth) for depth in args.depths}
         d_names = {depth: f"d: parts pipeline (submit_from) {args.slot_mib} MiB x {depth}"
                    for depth in pipes}
@@ -271,8 +315,9 @@ def host_staged(args):
             print(f"   warm-up {name}: {sec:.3f} s", flush=True)
         for depth, pipe in pipes.items():  # d's parity, left in the slots, against b's (untimed)
             w.arm_pipeline(pipe, check_parity=True)
-        print(f"   d: {len(pipes[args.depths[0]][1])} batches; parity in the slots equals b's",
-              flush=True)
+        if pipes:
+            print(f"   d: {len(pipes[args.depths[0]][1])} batches; parity in the slots equals "
+                  f"b's", flush=True)
         secs = {name: [] for name, _ in arms}
         ref = None
         for rep in range(args.repeats):
@@ -290,9 +335,12 @@ def host_staged(args):
         row = {"d": d, "p": p, "files": len(files), "parts": w.n, "file_bytes": w.file_bytes,
                "seconds": secs,
                "gbps": {k: [w.file_bytes / s / 1e9 for s in v] for k, v in secs.items()}}
-        b = secs["b: one parts_encode call"]
         if not args.no_per_part:
-            a = secs["a: part_encode x 256 threads"]
+            row["mixed_wins"] = [mixed_verdict(secs, th, row) for th in (10, 256)]
+        b = secs.get("b: one parts_encode call")
+        if not args.no_per_part and b:
+            a = min(secs["a: part_encode x 256 threads, by length"],
+                    secs["a: part_encode x 256 threads, mixed"], key=min)
             spread = max(max(a) - min(a), max(b) - min(b))
             row["b_vs_a256"] = {"a_best_s": min(a), "b_worst_s": max(b), "spread_s": spread,
                                 "b_wins_by_more_than_spread": max(b) + spread < min(a)}
@@ -402,6 +450,23 @@ class ReadWorkload:
         with ThreadPoolExecutor(threads) as ex:
             list(ex.map(one, range(count or self.n)))
 
+    def arm_part_read(self, threads, count=None):
+        """The per-part way in one call per part: cec_part_read (coalesced)."""
+        h, t = self.rs.handle, self.t
+        fb, eb, vb = (x.ctypes.data for x in (self.flags, self.expected, self.verified))
+
+        def one(k):
+            st = ce._lib.cec_part_read(h, self.part_ptrs[k], self.L[k],
+                                       ctypes.cast(fb + k * t, U8P),
+                                       ctypes.cast(eb + k * t * 32, U8P), 1,
+                                       ctypes.cast(vb + k * t, U8P))
+            assert st == 0, (st, k)
+        n = count or self.n
+        self.verified[:n] = 0
+        with ThreadPoolExecutor(threads) as ex:
+            list(ex.map(one, range(n)))
+        assert np.array_equal(self.verified[:n], self.flags[:n])
+
     def arm_ragged(self, count=None):
         n = count or self.n
         ce._check(ce._lib.cec_parts_read(
@@ -510,10 +575,15 @@ def host_read(args):
         arms = [("a: sha256_many + reconstruct_data x 10 threads", lambda c=None: w.arm_percall(10, c)),
                 ("a: sha256_many + reconstruct_data x 256 threads",
                  lambda c=None: w.arm_percall(256, c)),
+                ("a: part_read x 10 threads", lambda c=None: w.arm_part_read(10, c)),
+                ("a: part_read x 256 threads", lambda c=None: w.arm_part_read(256, c)),
                 ("b: one parts_read call", lambda c=None: w.arm_ragged(c)),
                 ("c: CPU oracle x 16 threads", lambda c=None: w.arm_cpu(16, c))]
         if args.no_per_part:  # a quick look at b and d: the per-part arms take most of a run
             arms = [arm for arm in arms if not arm[0].startswith("a")]
+        if args.per_part_only:  # the per-part arms alone
+            arms = [arm for arm in arms if arm[0].startswith("a")]
+            args.depths = []
         readers = {depth: w.make_reader(args.slot_mib << 20, depth) for depth in args.depths}
         d_names = {depth: f"d: parts reader (submit_from) {args.slot_mib} MiB x {depth}"
                    for depth in readers}
@@ -523,7 +593,8 @@ def host_read(args):
         for name, fn in arms:  # warm-up: b and d on the whole input (b's staging is sized by it)
             sec, _ = timed(lambda: fn(None if name[0] in "bd" else warm))
             print(f"   warm-up {name}: {sec:.3f} s", flush=True)
-        print(f"   d: {len(readers[args.depths[0]][1])} batches", flush=True)
+        if readers:
+            print(f"   d: {len(readers[args.depths[0]][1])} batches", flush=True)
         secs = {name: [] for name, _ in arms}
         down = {name: [] for name in d_names.values()}
         by_name = {name: readers[depth][0] for depth, name in d_names.items()}
@@ -546,11 +617,23 @@ def host_read(args):
         row = {"d": d, "p": p, "files": len(files), "parts": w.n,
                "file_bytes": w.file_bytes, "seconds": secs,
                "gbps": {k: [w.file_bytes / s / 1e9 for s in v] for k, v in secs.items()}}
+        if not args.no_per_part:
+            for th in (10, 256):
+                two = secs[f"a: sha256_many + reconstruct_data x {th} threads"]
+                one = secs[f"a: part_read x {th} threads"]
+                print(f"   per part, {th} threads: two calls {min(two):.3f}-{max(two):.3f} s, "
+                      f"part_read {min(one):.3f}-{max(one):.3f} s "
+                      f"({w.file_bytes / max(one) / 1e9:.2f}-{w.file_bytes / min(one) / 1e9:.2f} "
+                      f"GB/s)", flush=True)
+        if args.per_part_only:
+            results.append(row)
+            del w, readers, by_name
+            continue
         b = secs["b: one parts_read call"]
         if not args.no_per_part:
-            names = [name for name, _ in arms]
-            wins = [b[r] < min(secs[names[0]][r], secs[names[1]][r]) for r in range(args.repeats)]
-            print(f"   b faster than the better per-part arm in each repeat: {wins}", flush=True)
+            names = [name for name, _ in arms if name.startswith("a")]
+            wins = [b[r] < min(secs[name][r] for name in names) for r in range(args.repeats)]
+            print(f"   b faster than the best per-part arm in each repeat: {wins}", flush=True)
             row["b_faster_each_repeat"] = wins
         b_down, b_copies = w.parts_read_d2h_bytes()
         rebuilt = int(sum(w.L))
@@ -897,11 +980,7 @@ KNOB = "CEC_RAGGED_FUSED"
 
 def set_knob(value):
     """CEC_RAGGED_FUSED = value (None: unset) from the next call on."""
-    if value is None:
-        os.environ.pop(KNOB, None)
-    else:
-        os.environ[KNOB] = value
-    ce.reload_knobs()
+    set_env_knob(KNOB, value)
 
 
 def event_ms(fn, knob=None):
@@ -1071,6 +1150,8 @@ def main():
                     help="arm d: one arm per number of slots in flight")
     ap.add_argument("--no-per-part", action="store_true",
                     help="host mode and --read: leave out the a arms")
+    ap.add_argument("--per-part-only", action="store_true",
+                    help="host mode and --read: the a arms alone (the CEC_COALESCE_MIXED A/B)")
     ap.add_argument("--device", action="store_true")
     ap.add_argument("--read", action="store_true")
     ap.add_argument("--verify", action="store_true")
