@@ -160,6 +160,22 @@ hipError_t launch_hash(const cec_part_batch& b, size_t first_chunk, size_t n_chu
     return launch_sha256(h, aligned16(b), s);
 }
 
+ShaParams sha_list_params(const uint64_t* ptrs, const uint64_t* lens, size_t items,
+                          const uint32_t* order, size_t listed, uint8_t* digests,
+                          const uint8_t* expected, uint8_t* ok) {
+    ShaParams h{};
+    h.ptrs = ptrs;
+    h.lens = lens;
+    h.n_parts = uint32_t(items);
+    h.n_chunks = 1;
+    h.digests = digests;
+    h.expected = expected;
+    h.ok = ok;
+    h.items = order;
+    h.n_items = uint32_t(listed);
+    return h;
+}
+
 hipError_t launch_decode(const cec_part_batch& b, size_t d, const uint32_t* words,
                          const DecodePlan::Launch* l, uint32_t n_rows, uint32_t lds_reserve,
                          hipStream_t s) {
@@ -291,6 +307,19 @@ int check_present(size_t d, size_t t, const uint8_t* present, size_t n_parts) {
         size_t n_present = 0;
         for (size_t i = 0; i < t; ++i) n_present += present[k * t + i] ? 1 : 0;
         if (n_present != t && n_present < d) return CEC_TOO_FEW_SHARDS_PRESENT;
+    }
+    return CEC_OK;
+}
+
+int null_slot_rule(const char* who, const uint8_t* const* shards, const uint8_t* present, size_t n,
+                   size_t d, size_t t, bool data_only) {
+    for (size_t k = 0; k < n; ++k) {
+        const size_t loaded = plan::loaded_count(present + k * t, t);
+        for (size_t i = 0; i < t; ++i)
+            if ((present[k * t + i] || plan::may_fill(i, d, loaded, data_only)) && !shards[k * t + i]) {
+                set_last_error(std::string(who) + ": a chunk slot that is read or filled is NULL");
+                return CEC_ERR_INVALID_ARGUMENT;
+            }
     }
     return CEC_OK;
 }

@@ -7,12 +7,14 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <array>
 #include <functional>
 #include <list>
 #include <map>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <unordered_map>
 #include <utility>
@@ -24,6 +26,8 @@
 #include "percall_plan.hpp"
 
 #pragma GCC visibility push(hidden)
+
+#include "ragged_words.hpp"  // hidden like everything here: its templates export nothing
 
 namespace cec {
 
@@ -264,6 +268,11 @@ struct HashVerify {
 // SHA-256 of chunks [first_chunk, first_chunk + n_chunks) of every part: digests and/or verify.
 hipError_t launch_hash(const cec_part_batch& b, size_t first_chunk, size_t n_chunks,
                        uint8_t* digests, const HashVerify& v, hipStream_t s);
+// The list-mode ShaParams (device pointers): item i hashes lens[i] bytes at ptrs[i], i < items;
+// order (null: every item) lists the `listed` items a launch hashes; digests and / or expected + ok.
+ShaParams sha_list_params(const uint64_t* ptrs, const uint64_t* lens, size_t items,
+                          const uint32_t* order, size_t listed, uint8_t* digests,
+                          const uint8_t* expected = nullptr, uint8_t* ok = nullptr);
 
 // One decode launch.  l: the listed parts of b, each with its own record in `words` (the shared
 // launch when l->n_out == 0, n_rows its row class); null: every part of b through the n_rows
@@ -298,22 +307,24 @@ int split_check(size_t d, size_t p, const uint8_t* data, const size_t* doffs,
 // Host-staged packing of n parts' data chunks into dst at offs (zero-padded), on up to 8 threads.
 void pack_parts(uint8_t* dst, const size_t* offs, size_t d, const uint8_t* const* bufs,
                 const size_t* lengths, const size_t* chunk_lens, size_t n);
-// Bytes of per-part words the launches of a ragged encode of n parts of t chunks upload.
-size_t ragged_words_bytes(size_t t, size_t n);
 // The launches of a ragged encode + SHA-256 of checked arguments on s.  poffs null: parity behind
 // each part's data (cec_encode_hash_ragged, `parity` unused); else the split layout.  hwords /
-// dwords: page-locked and device room of ragged_words_bytes for the words, which a caller that
+// dwords: page-locked and device room of plan::ragged_words_bytes for the words, which a caller that
 // owns them must not reuse before the launches are done (null: a buffer of the scratch pool).
 int ragged_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, uint8_t* parity,
                   const size_t* poffs, const size_t* lens, size_t n, uint8_t* digests,
                   hipStream_t s, uint8_t* hwords = nullptr, uint8_t* dwords = nullptr);
-
 
 // ---- The ragged read (ragged.cpp), as the read pipeline (ragged_read_pipeline.cpp) shares it. ----
 
 // cec_ragged_layout behind its pointer checks.
 int ragged_layout(size_t t, const size_t* lens, size_t n, size_t* offs, size_t* total);
 // (fills_slot, whether a read fills a slot that did not verify: percall_plan.hpp)
+// The rule of cec_parts_read, cec_part_read and the parts reader for n parts' t slots each: a
+// loaded chunk needs its bytes; a part that can be decoded (d or more chunks loaded) needs memory
+// behind every slot the mode fills.  `who` opens the error text.
+int null_slot_rule(const char* who, const uint8_t* const* shards, const uint8_t* present, size_t n,
+                   size_t d, size_t t, bool data_only);
 // The worst case of a packed return (cec_read_ragged_packed_async's bound on rebuilt_cap): the sum
 // of rows * stride(L_k), rows = p, or min(p, d) under data_only.  Nonzero lengths.
 int packed_worst_case(size_t d, size_t p, bool data_only, const size_t* lens, size_t n,

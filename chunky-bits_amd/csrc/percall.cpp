@@ -534,12 +534,8 @@ struct ShaImpl {
         HIP_TRY(hipMemcpyAsync(ddata, a.in.ptr, total, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(dptrs, hmeta.data(), hmeta.size() * sizeof(uint64_t),
                                hipMemcpyHostToDevice, s));
-        ShaParams h{};  // list mode: not a cec_part_batch layout
-        h.ptrs = dptrs;
-        h.lens = dptrs + items;
-        h.n_parts = uint32_t(items);
-        h.n_chunks = 1;
-        h.digests = ddig;
+        // list mode: not a cec_part_batch layout
+        const ShaParams h = sha_list_params(dptrs, dptrs + items, items, nullptr, 0, ddig);
         HIP_TRY(launch_sha256(h, true, s));
         HIP_TRY(hipMemcpyAsync(a.out.ptr, ddig, items * 32, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -959,17 +955,7 @@ int cec_part_read(const cec_codec* cc, uint8_t* const* shards, size_t chunk_len,
     if (!cc || !shards || !present || !expected || !verified) return CEC_ERR_INVALID_ARGUMENT;
     if (chunk_len == 0) return CEC_EMPTY_SHARD;
     const size_t d = cc->d, t = cc->d + cc->p;
-    // cec_parts_read's rule: a loaded chunk needs its bytes; a part that can be decoded (d or more
-    // chunks loaded) needs memory behind every slot the mode fills.
-    size_t loaded = 0;
-    for (size_t i = 0; i < t; ++i) loaded += present[i] ? 1 : 0;
-    for (size_t i = 0; i < t; ++i) {
-        const bool need = present[i] || (loaded >= d && fills_slot(i, d, data_only != 0));
-        if (need && !shards[i]) {
-            set_last_error("cec_part_read: a chunk slot that is read or filled is NULL");
-            return CEC_ERR_INVALID_ARGUMENT;
-        }
-    }
+    CEC_TRY(null_slot_rule("cec_part_read", shards, present, 1, d, t, data_only != 0));
     if (!ragged_stride(chunk_len) || ragged_stride(chunk_len) > SIZE_MAX / t)
         return CEC_ERR_INVALID_ARGUMENT;
     ReadReq r;

@@ -146,6 +146,31 @@ inline size_t loaded_spans(size_t t, const size_t* lens, const size_t* offs, siz
                        [&](size_t k, size_t i) { return present[k * t + i] != 0; }, spans);
 }
 
+// What a decodable part can return.  A part decodes once d of its chunks verify, so one with
+// `loaded` chunks loaded can have slot i filled when the slot is not loaded itself, d or more are,
+// and the mode fills the slot.
+inline size_t loaded_count(const uint8_t* present, size_t t) {
+    size_t loaded = 0;
+    for (size_t i = 0; i < t; ++i) loaded += present[i] ? 1 : 0;
+    return loaded;
+}
+inline bool may_fill(size_t i, size_t d, size_t loaded, bool data_only) {
+    return loaded >= d && fills_slot(i, d, data_only);
+}
+
+// The bytes of a packed return (a stride per rebuilt chunk) if every loaded chunk verifies: what a
+// reader fetches before it knows the flags.
+inline size_t return_guess(size_t d, size_t t, const size_t* lens, size_t n,
+                           const uint8_t* present, bool data_only) {
+    size_t bytes = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const size_t loaded = loaded_count(present + k * t, t);
+        for (size_t i = 0; i < t; ++i)
+            if (!present[k * t + i] && may_fill(i, d, loaded, data_only)) bytes += stride16(lens[k]);
+    }
+    return bytes;
+}
+
 // Whether the rebuild wrote slot i of a part: the part decoded (status 0), the chunk did not
 // verify, and the mode fills the slot.
 inline bool rebuilt_slot(size_t i, size_t d, bool data_only, uint8_t verified, int part_status) {

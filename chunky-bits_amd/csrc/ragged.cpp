@@ -10,18 +10,13 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
-#include <numeric>
 #include <thread>
 
 #include "capi_internal.hpp"
 
 using namespace cec;
 
-namespace {
-
-constexpr size_t kRaggedAlign = plan::kRaggedAlign;
-
-}  // namespace
+using plan::kRaggedAlign;
 
 // L rounded up to 16; 0 when that overflows (and for an empty chunk, which every caller refuses
 // before it asks).
@@ -90,74 +85,6 @@ int cec::split_check(size_t d, size_t p, const uint8_t* data, const size_t* doff
 
 namespace {
 
-// The per-part device records of the parts ids[0 .. count) (null: parts 0 .. count - 1):
-// units[count + 1] = the prefix array of their work units (null: not wanted), parts[4 * count] =
-// {off lo, off hi, L lo, L hi}.  Returns the unit total, at most the whole batch's, which
-// ragged_check bounded.
-// With `disp` (the split layout, kernels.hpp RaggedParams::split) a record has two more words,
-// {disp lo, disp hi}: parts[6 * count].
-uint32_t part_records(const size_t* offs, const size_t* lens, const uint32_t* ids, size_t count,
-                      uint32_t* units, uint32_t* parts, const uint64_t* disp = nullptr) {
-    const uint64_t unit = ragged_unit_bytes();
-    const size_t w = disp ? 6 : 4;
-    uint64_t acc = 0;
-    for (size_t q = 0; q < count; ++q) {
-        const size_t k = ids ? ids[q] : q;
-        const uint64_t off = offs[k], L = lens[k];
-        if (units) units[q] = uint32_t(acc);
-        acc += (L - 1) / unit + 1;
-        parts[w * q + 0] = uint32_t(off);
-        parts[w * q + 1] = uint32_t(off >> 32);
-        parts[w * q + 2] = uint32_t(L);
-        parts[w * q + 3] = uint32_t(L >> 32);
-        if (disp) {
-            parts[w * q + 4] = uint32_t(disp[k]);
-            parts[w * q + 5] = uint32_t(disp[k] >> 32);
-        }
-    }
-    if (units) units[count] = uint32_t(acc);
-    return uint32_t(acc);
-}
-
-// order[n] = the parts stably sorted by chunk length, longest first.
-void length_order(const size_t* lens, size_t n, uint32_t* order) {
-    std::iota(order, order + n, 0u);
-    std::stable_sort(order, order + n, [&](uint32_t x, uint32_t y) { return lens[x] > lens[y]; });
-}
-
-// The SHA-256 list of a ragged batch: ptrs / h_len of the items k * t + i that pass `pick` (the
-// others are never looked at) and, in `order`, those items stably sorted by their part's length,
-// longest first: a SHA-256 wave runs as long as its longest lane, so the 64 chains of a wave get
-// similar lengths.  Digests and flags land at their item's place whatever the order.  An item's
-// key is its part's, so the parts are sorted and each expanded in place.  Returns the items listed.
-// at(k, i, stride) is where part k's chunk i lies.
-template <typename Pick, typename At>
-size_t sha_list(const size_t* lens, size_t n, size_t t, Pick pick, At at, uint64_t* ptrs,
-                uint64_t* h_len, uint32_t* order) {
-    std::vector<uint32_t> by_len(n);
-    length_order(lens, n, by_len.data());
-    size_t count = 0;
-    for (const size_t k : by_len) {
-        const size_t cs = ragged_stride(lens[k]);
-        for (size_t i = 0; i < t; ++i) {
-            const size_t item = k * t + i;
-            if (!pick(item)) continue;
-            ptrs[item] = reinterpret_cast<uint64_t>(at(k, i, cs));
-            h_len[item] = lens[k];
-            order[count++] = uint32_t(item);
-        }
-    }
-    return count;
-}
-
-}  // namespace
-
-// Two-pass: [ptrs u64 x items][lens u64 x items][order u32 x items][units u32 x n+1]
-// [parts u32 x 4n or 6n]; fused: [order u32 x n][parts u32 x 4n or 6n], which is less.
-size_t cec::ragged_words_bytes(size_t t, size_t n) { return n * t * 20 + (n + 1) * 4 + n * 24; }
-
-namespace {
-
 // Ragged encode launch sequences since load, by path (cec_ragged_stats).
 std::atomic<uint64_t> g_fused_seqs{0}, g_two_pass_seqs{0};
 
@@ -186,6 +113,15 @@ bool ragged_prefers_fused(size_t d, size_t p, const size_t* lens, size_t n) {
     return f >= 0 ? f == 1 : !use_split(n * (d + p)) && kRaggedFusedDefault;
 }
 
+// The RaggedParams of a launch over n_parts listed parts, in the order of its fields (kernels.hpp):
+// device pointers; part_pat null: every part uses the record at pat.
+RaggedParams ragged_params(uint8_t* base, const uint32_t* pat, const uint32_t* units,
+                           const uint32_t* parts, const uint32_t* part_pat, size_t n_parts,
+                           uint32_t total_units, size_t d, size_t n_rows, bool split = false) {
+    return {base, pat, units, parts, part_pat, uint32_t(n_parts), total_units, uint32_t(d),
+            uint32_t(n_rows), split ? 1u : 0u};
+}
+
 }  // namespace
 
 // The launches of a checked ragged encode on `s`: one upload of the per-part words, then the
@@ -201,42 +137,39 @@ int cec::ragged_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, u
     uint32_t* drec = nullptr;
     CEC_TRY(c->encode_record(&drec));
     const bool fused = ragged_prefers_fused(d, c->p, lens, n);
-    // fused: the part order where the SHA-256 list and the unit prefix would be
-    const size_t o_len = items * 8, o_ord = o_len + items * 8, o_units = o_ord + items * 4,
-                 o_parts = fused ? n * 4 : o_units + (n + 1) * 4,
-                 bytes = o_parts + n * (poffs ? 24 : 16);
+    const plan::EncodeWords w = plan::encode_words(t, n, fused, poffs != nullptr);
     Scratch sc;  // the words of a caller that has none: released on s behind the launches below
     if (!hwords) {
-        CEC_TRY(sc.acquire(bytes, s));
+        CEC_TRY(sc.acquire(w.bytes, s));
         hwords = sc.host();
         dwords = sc.dev();
     }
+    const plan::View v{hwords, dwords};
     // where part k's parity chunk 0 lies, less where today's layout has it
     std::vector<uint64_t> disp(poffs ? n : 0);
     for (size_t k = 0; k < disp.size(); ++k)
         disp[k] = (reinterpret_cast<uint64_t>(parity) + poffs[k]) -
                   (reinterpret_cast<uint64_t>(data) + doffs[k] + d * ragged_stride(lens[k]));
     if (fused)
-        length_order(lens, n, reinterpret_cast<uint32_t*>(hwords));
+        plan::length_order(lens, n, v.host(w.list.order));
     else
-        sha_list(
+        plan::sha_list(
             lens, n, t, [](size_t) { return true; },
             [&](size_t k, size_t i, size_t cs) {
                 return i < d || !poffs ? data + doffs[k] + i * cs
                                        : parity + poffs[k] + (i - d) * cs;
             },
-            reinterpret_cast<uint64_t*>(hwords), reinterpret_cast<uint64_t*>(hwords + o_len),
-            reinterpret_cast<uint32_t*>(hwords + o_ord));
-    const uint32_t total_units = part_records(
-        doffs, lens, nullptr, n, fused ? nullptr : reinterpret_cast<uint32_t*>(hwords + o_units),
-        reinterpret_cast<uint32_t*>(hwords + o_parts), poffs ? disp.data() : nullptr);
-    HIP_TRY(hipMemcpyAsync(dwords, hwords, bytes, hipMemcpyHostToDevice, s));
+            v.host(w.list.ptrs), v.host(w.list.lens), v.host(w.list.order));
+    const uint32_t total_units = plan::part_records(
+        ragged_unit_bytes(), doffs, lens, nullptr, n, fused ? nullptr : v.host(w.units),
+        v.host(w.parts), poffs ? disp.data() : nullptr);
+    HIP_TRY(hipMemcpyAsync(dwords, hwords, w.bytes, hipMemcpyHostToDevice, s));
     if (fused) {
         FusedRaggedParams f{};
         f.base = const_cast<uint8_t*>(data);  // split: only read
         f.pat = drec;
-        f.order = reinterpret_cast<const uint32_t*>(dwords);
-        f.parts = reinterpret_cast<const uint32_t*>(dwords + o_parts);
+        f.order = v.dev(w.list.order);
+        f.parts = v.dev(w.parts);
         f.digests = digests;
         f.n_parts = uint32_t(n);
         f.d = uint32_t(d);
@@ -246,25 +179,12 @@ int cec::ragged_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, u
         g_fused_seqs.fetch_add(1, std::memory_order_relaxed);
         return CEC_OK;
     }
-    RaggedParams a{};
-    a.total_units = total_units;
-    a.base = const_cast<uint8_t*>(data);  // split: only read
-    a.pat = drec;
-    a.units = reinterpret_cast<const uint32_t*>(dwords + o_units);
-    a.parts = reinterpret_cast<const uint32_t*>(dwords + o_parts);
-    a.n_parts = uint32_t(n);
-    a.d = uint32_t(d);
-    a.n_rows = uint32_t(c->p);
-    a.split = poffs ? 1u : 0u;
+    const RaggedParams a =
+        ragged_params(const_cast<uint8_t*>(data) /* split: only read */, drec, v.dev(w.units),
+                      v.dev(w.parts), nullptr, n, total_units, d, c->p, poffs != nullptr);
     HIP_TRY(launch_rs_encode_ragged(a, s));
-    ShaParams h{};
-    h.ptrs = reinterpret_cast<const uint64_t*>(dwords);
-    h.lens = reinterpret_cast<const uint64_t*>(dwords + o_len);
-    h.n_parts = uint32_t(items);
-    h.n_chunks = 1;
-    h.digests = digests;
-    h.items = reinterpret_cast<const uint32_t*>(dwords + o_ord);
-    h.n_items = uint32_t(items);
+    const ShaParams h = sha_list_params(v.dev(w.list.ptrs), v.dev(w.list.lens), items,
+                                        v.dev(w.list.order), items, digests);
     HIP_TRY(launch_sha256(h, true, s));
     g_two_pass_seqs.fetch_add(1, std::memory_order_relaxed);
     return CEC_OK;
@@ -281,36 +201,25 @@ int reconstruct_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const si
     DecodePlan plan;
     plan_decode(c, present, n, data_only, &plan);
     if (plan.launches.empty()) return CEC_OK;
-    size_t listed = 0;
-    for (const auto& l : plan.launches) {
+    for (const auto& l : plan.launches)
         if (!l.n_out) CEC_TRY(check_row_class(plan, l, plan.var_rows, "reconstruct_ragged"));
-        listed += l.count;
-    }
-    // [plan words][per launch: units u32 x (count + 1), parts u32 x 4 count]
-    const size_t n_words = plan.words.size() + listed * 5 + plan.launches.size();
+    const plan::ReconWords w = plan::recon_words(plan.words.size(), plan.launches);
     Scratch sc;  // released on s behind the launches below
-    CEC_TRY(sc.acquire(n_words * sizeof(uint32_t), s));
-    uint32_t* h = reinterpret_cast<uint32_t*>(sc.host());
-    uint32_t* dwords = reinterpret_cast<uint32_t*>(sc.dev());
-    std::memcpy(h, plan.words.data(), plan.words.size() * sizeof(uint32_t));
+    CEC_TRY(sc.acquire(w.bytes, s));
+    const plan::View v{sc.host(), sc.dev()};
+    std::memcpy(v.host(w.plan), plan.words.data(), plan.words.size() * sizeof(uint32_t));
+    const uint32_t* dplan = v.dev(w.plan);
     std::vector<RaggedParams> params;
-    size_t at = plan.words.size();
-    for (const auto& l : plan.launches) {
-        RaggedParams a{};
-        a.total_units = part_records(offs, lens, plan.words.data() + l.ids, l.count, h + at,
-                                     h + at + l.count + 1);
-        a.base = base;
-        a.pat = dwords;
-        a.units = dwords + at;
-        a.parts = dwords + at + l.count + 1;
-        a.part_pat = dwords + l.ids + l.count;
-        a.n_parts = uint32_t(l.count);
-        a.d = uint32_t(c->d);
-        a.n_rows = l.n_out ? l.n_out : plan.var_rows;
-        params.push_back(a);
-        at += l.count * 5 + 1;
+    for (size_t i = 0; i < plan.launches.size(); ++i) {
+        const auto& l = plan.launches[i];
+        const uint32_t total_units =
+            plan::part_records(ragged_unit_bytes(), offs, lens, plan.words.data() + l.ids, l.count,
+                               v.host(w.units[i]), v.host(w.parts[i]));
+        params.push_back(ragged_params(base, dplan, v.dev(w.units[i]), v.dev(w.parts[i]),
+                                       dplan + l.ids + l.count, l.count, total_units, c->d,
+                                       l.n_out ? l.n_out : plan.var_rows));
     }
-    HIP_TRY(hipMemcpyAsync(dwords, h, n_words * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(sc.dev(), sc.host(), w.bytes, hipMemcpyHostToDevice, s));
     for (size_t i = 0; i < params.size(); ++i) {
         const hipError_t e = plan.launches[i].n_out ? launch_rs_encode_ragged(params[i], s)
                                                     : launch_rs_reconstruct_ragged(params[i], s);
@@ -319,39 +228,27 @@ int reconstruct_ragged(cec_codec* c, uint8_t* base, const size_t* offs, const si
     return CEC_OK;
 }
 
-// Bytes of the SHA-256 list of a ragged verification: [ptrs u64 x items][lens u64 x items]
-// [order u32 x items].
-inline size_t verify_list_bytes(size_t items) { return items * 20; }
-
 // The queued half of a ragged verification for a checked layout of t chunks per part: on `s` one
 // upload, the memset of ok[items] (device) and the SHA-256 list launch in verify mode over the
 // chunks that need hashing (present null: all of them; ok and expected indexed by k*t+i).
-// hwords / dwords: page-locked and device room for the list (verify_list_bytes) and, directly
-// behind it, `tail` bytes of the caller's own words, filled on the page-locked side before the
-// call, which go up in the same copy.  tail == 0: only the listed part of the list goes up, and
-// nothing when nothing is hashed.  No wait; nothing of `base` is written.
+// v: page-locked and device room for the list `w` (of n * t items, at the start of both) and,
+// directly behind it, `tail` bytes of the caller's own words, filled on the page-locked side
+// before the call, which go up in the same copy.  tail == 0: only the listed part of the list goes
+// up, and nothing when nothing is hashed.  No wait; nothing of `base` is written.
 int verify_launch(const uint8_t* base, const size_t* offs, const size_t* lens, size_t n, size_t t,
-                  const uint8_t* present, const uint8_t* expected, uint8_t* hwords,
-                  uint8_t* dwords, size_t tail, uint8_t* ok, hipStream_t s) {
-    const size_t items = n * t, o_len = items * 8, o_ord = o_len + items * 8;
-    const size_t hashed = sha_list(
+                  const uint8_t* present, const uint8_t* expected, const plan::ShaListWords& w,
+                  const plan::View& v, size_t tail, uint8_t* ok, hipStream_t s) {
+    const size_t items = n * t;
+    const size_t hashed = plan::sha_list(
         lens, n, t, [&](size_t item) { return !present || needs_hash(present[item]); },
-        [&](size_t k, size_t i, size_t cs) { return base + offs[k] + i * cs; },
-        reinterpret_cast<uint64_t*>(hwords), reinterpret_cast<uint64_t*>(hwords + o_len),
-        reinterpret_cast<uint32_t*>(hwords + o_ord));
-    const size_t up = tail ? verify_list_bytes(items) + tail : hashed ? o_ord + hashed * 4 : 0;
-    if (up) HIP_TRY(hipMemcpyAsync(dwords, hwords, up, hipMemcpyHostToDevice, s));
+        [&](size_t k, size_t i, size_t cs) { return base + offs[k] + i * cs; }, v.host(w.ptrs),
+        v.host(w.lens), v.host(w.order));
+    const size_t up = tail ? w.bytes + tail : w.up_bytes(hashed);
+    if (up) HIP_TRY(hipMemcpyAsync(v.d, v.h, up, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(ok, 0, items, s));
     if (hashed) {
-        ShaParams h{};
-        h.ptrs = reinterpret_cast<const uint64_t*>(dwords);
-        h.lens = reinterpret_cast<const uint64_t*>(dwords + o_len);
-        h.n_parts = uint32_t(items);
-        h.n_chunks = 1;
-        h.expected = expected;
-        h.ok = ok;
-        h.items = reinterpret_cast<const uint32_t*>(dwords + o_ord);
-        h.n_items = uint32_t(hashed);
+        const ShaParams h = sha_list_params(v.dev(w.ptrs), v.dev(w.lens), items, v.dev(w.order),
+                                            hashed, nullptr, expected, ok);
         const hipError_t e = launch_sha256(h, true, s);
         if (e != hipSuccess) return hip_fail(e, "launch_sha256 (ragged verify)");
     }
@@ -366,16 +263,15 @@ int verify_ragged(const uint8_t* base, const size_t* offs, const size_t* lens, s
                   const uint8_t* present, const uint8_t* expected, uint8_t* verified,
                   hipStream_t s) {
     const size_t items = n * t;
-    // [the SHA-256 list][ok u8 x items]
-    const size_t o_ok = verify_list_bytes(items), bytes = o_ok + items;
+    const plan::VerifyWords w = plan::verify_words(items);
     Scratch sc;  // released on s behind the readback
-    CEC_TRY(sc.acquire(bytes, s));
-    uint8_t* ok = sc.dev() + o_ok;
-    CEC_TRY(verify_launch(base, offs, lens, n, t, present, expected, sc.host(), sc.dev(), 0, ok, s));
+    CEC_TRY(sc.acquire(w.bytes, s));
+    const plan::View v{sc.host(), sc.dev()};
+    CEC_TRY(verify_launch(base, offs, lens, n, t, present, expected, w.list, v, 0, v.dev(w.ok), s));
     // the flags come back through the mirror, behind the words that went up
-    HIP_TRY(hipMemcpyAsync(sc.host() + o_ok, ok, items, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(v.host(w.ok), v.dev(w.ok), items, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    std::memcpy(verified, sc.host() + o_ok, items);
+    std::memcpy(verified, v.host(w.ok), items);
     for (size_t i = 0; present && i < items; ++i)  // trusted, not hashed
         if (present[i] == CEC_PRESENT_VERIFIED) verified[i] = 1;
     return CEC_OK;
@@ -458,40 +354,32 @@ int read_ragged_async(cec_codec* c, uint8_t* base, const size_t* offs, const siz
                       const PackedReturn* ret = nullptr) {
     const size_t d = c->d, t = c->d + c->p, items = n * t;
     const size_t rows = plan_rows(d, c->p, data_only), slot = pattern_words(d, rows);
-    // what goes up, in one copy: [the SHA-256 list][units u32 x (n + 1)][parts u32 x 4n]
-    // [part_pat u32 x n][present u8 x items]
-    const size_t o_units = verify_list_bytes(items), o_parts = o_units + (n + 1) * 4,
-                 o_pat = o_parts + n * 16, o_pres = o_pat + n * 4, up_bytes = o_pres + items;
-    // what stays on the device: [records u32 x n * slot][status i32 x n][ok u8 x items]
-    // [verified u8 x items]
-    // and, with a packed return, [ret_off u64 x (n + 1)] behind them
-    const size_t o_st = n * slot * 4, o_ok = o_st + n * 4, o_ver = o_ok + items,
-                 o_ret = round_up(o_ver + items, 8),
-                 dev_bytes = ret ? o_ret + (n + 1) * 8 : o_ver + items;
+    // what goes up, in one copy, and what stays on the device
+    const plan::ReadUpWords wu = plan::read_up_words(t, n);
+    const plan::ReadDevWords wd = plan::read_dev_words(t, n, slot, ret != nullptr);
     // every allocation before anything is queued
     Scratch up, dv;
-    CEC_TRY(up.acquire(up_bytes, s));
-    CEC_TRY(dv.acquire(dev_bytes, s, false));
+    CEC_TRY(up.acquire(wu.bytes, s));
+    CEC_TRY(dv.acquire(wd.bytes, s, false));
     uint8_t* dmat = nullptr;
     CEC_TRY(c->matrix_device(&dmat));
 
-    uint8_t *h = up.host(), *dw = up.dev();
-    const uint32_t total_units =
-        part_records(offs, lens, nullptr, n, reinterpret_cast<uint32_t*>(h + o_units),
-                     reinterpret_cast<uint32_t*>(h + o_parts));
-    uint32_t* part_pat = reinterpret_cast<uint32_t*>(h + o_pat);
+    const plan::View vu{up.host(), up.dev()}, vd{nullptr, dv.dev()};
+    const uint32_t total_units = plan::part_records(ragged_unit_bytes(), offs, lens, nullptr, n,
+                                                    vu.host(wu.units), vu.host(wu.parts));
+    uint32_t* part_pat = vu.host(wu.part_pat);
     for (size_t k = 0; k < n; ++k) part_pat[k] = uint32_t(k * slot);
-    std::memcpy(h + o_pres, present, items);
-    uint8_t* ok = dv.dev() + o_ok;
-    CEC_TRY(verify_launch(base, offs, lens, n, t, present, expected, h, dw, up_bytes - o_units, ok,
-                          s));
+    std::memcpy(vu.host(wu.present), present, items);
+    uint8_t* ok = vd.dev(wd.ok);
+    CEC_TRY(verify_launch(base, offs, lens, n, t, present, expected, wu.list, vu,
+                          wu.bytes - wu.list.bytes, ok, s));
     PlanParams pl{};
-    pl.present = dw + o_pres;
+    pl.present = vu.dev(wu.present);
     pl.ok = ok;
     pl.matrix = dmat;
-    pl.verified = dv.dev() + o_ver;
-    pl.part_status = reinterpret_cast<int32_t*>(dv.dev() + o_st);
-    pl.records = reinterpret_cast<uint32_t*>(dv.dev());
+    pl.verified = vd.dev(wd.verified);
+    pl.part_status = vd.dev(wd.status);
+    pl.records = vd.dev(wd.records);
     pl.n_parts = uint32_t(n);
     pl.d = uint32_t(d);
     pl.p = uint32_t(c->p);
@@ -500,19 +388,11 @@ int read_ragged_async(cec_codec* c, uint8_t* base, const size_t* offs, const siz
     pl.data_only = data_only ? 1u : 0u;
     hipError_t e = launch_decode_plan(pl, s);
     if (e != hipSuccess) return hip_fail(e, "launch_decode_plan");
-    RaggedParams a{};
-    a.base = base;
-    a.pat = pl.records;
-    a.units = reinterpret_cast<const uint32_t*>(dw + o_units);
-    a.parts = reinterpret_cast<const uint32_t*>(dw + o_parts);
-    a.part_pat = reinterpret_cast<const uint32_t*>(dw + o_pat);
-    a.n_parts = uint32_t(n);
-    a.total_units = total_units;
-    a.d = uint32_t(d);
-    a.n_rows = uint32_t(rows);
+    const RaggedParams a = ragged_params(base, pl.records, vu.dev(wu.units), vu.dev(wu.parts),
+                                         vu.dev(wu.part_pat), n, total_units, d, rows);
     e = launch_rs_reconstruct_ragged(a, s);
     if (e != hipSuccess) return hip_fail(e, "launch_rs_reconstruct_ragged (device plan)");
-    uint64_t* ret_off = ret ? reinterpret_cast<uint64_t*>(dv.dev() + o_ret) : nullptr;
+    uint64_t* ret_off = ret ? vd.dev(wd.ret_off) : nullptr;
     if (ret) {
         ReturnParams r{};
         r.base = base;
@@ -825,12 +705,8 @@ int parts_read_round(cec_codec* c, Arena& a, uint8_t* const* shards, const size_
     const size_t d = c->d, t = c->d + c->p, items = n * t;
     Round r;
     CEC_TRY(reserve_round(a, d, t, chunk_lens, n, &r));
-    size_t in_bytes = 0, out_bytes = 0;
-    for (size_t k = 0; k < n; ++k)
-        for (size_t i = 0; i < t; ++i) in_bytes += present[k * t + i] ? chunk_lens[k] : 0;
-    for_parts(n, in_bytes, [&](size_t k) {
-        read_round_stage(r, k, t, chunk_lens[k], shards + k * t, present + k * t);
-    });
+    size_t out_bytes = 0;
+    pack_loaded(r.stage, r.offs.data(), t, shards, chunk_lens, n, present);
     std::memcpy(a.out.ptr, expected, items * 32);
     CEC_TRY(read_round_launch(c, a, r, chunk_lens, n, present, data_only, verified, part_status));
     for (size_t k = 0; k < n; ++k)
@@ -1028,19 +904,7 @@ int cec_parts_read(const cec_codec* cc, uint8_t* const* shards, const size_t* ch
     size_t items = 0;
     if (__builtin_mul_overflow(n_parts, t, &items) || items > 0xFFFFFFFFull)
         return CEC_ERR_INVALID_ARGUMENT;
-    // A loaded chunk needs its bytes; a part that can be decoded (d or more chunks loaded) needs
-    // memory behind every slot the mode fills.
-    for (size_t k = 0; k < n_parts; ++k) {
-        size_t loaded = 0;
-        for (size_t i = 0; i < t; ++i) loaded += present[k * t + i] ? 1 : 0;
-        for (size_t i = 0; i < t; ++i) {
-            const bool need = present[k * t + i] || (loaded >= d && fills_slot(i, d, data_only != 0));
-            if (need && !shards[k * t + i]) {
-                set_last_error("cec_parts_read: a chunk slot that is read or filled is NULL");
-                return CEC_ERR_INVALID_ARGUMENT;
-            }
-        }
-    }
+    CEC_TRY(null_slot_rule("cec_parts_read", shards, present, n_parts, d, t, data_only != 0));
     return run_rounds(d, t, chunk_lens, n_parts, [&](Arena& a, size_t k0, size_t k1) {
         return parts_read_round(c, a, shards + k0 * t, chunk_lens + k0, k1 - k0, present + k0 * t,
                                 expected + k0 * t * 32, data_only != 0, verified + k0 * t,

@@ -139,7 +139,7 @@ int cec_parts_pipeline_new(const cec_codec* codec, size_t slot_data_bytes, size_
     // last chunk's stride whatever the rounding
     pl->parity_cap = slot_data_bytes / d * p + p * 16;
     pl->max_parts = max_parts;
-    const size_t words = ragged_words_bytes(t, max_parts);
+    const size_t words = plan::ragged_words_bytes(t, max_parts);
     hipError_t e = hipGetDevice(&pl->device);
     uint32_t* rec = nullptr;  // the codec's encode record on this device: made now, not mid-stream
     int st = e == hipSuccess ? pl->codec->encode_record(&rec) : CEC_OK;

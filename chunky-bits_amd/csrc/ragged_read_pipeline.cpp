@@ -84,24 +84,6 @@ struct cec_parts_reader {
         return CEC_OK;
     }
 
-    // cec_parts_read's rule: a loaded slot, and in a part that can be decoded every slot the mode
-    // fills, needs memory.
-    int null_rule(const uint8_t* const* shards, const uint8_t* present, size_t n,
-                  const char* who) const {
-        for (size_t k = 0; k < n; ++k) {
-            size_t loaded = 0;
-            for (size_t i = 0; i < t; ++i) loaded += present[k * t + i] ? 1 : 0;
-            for (size_t i = 0; i < t; ++i) {
-                const bool need = present[k * t + i] || (loaded >= d && fills_slot(i, d, data_only));
-                if (need && !shards[k * t + i]) {
-                    set_last_error(std::string(who) + ": a chunk slot that is read or filled is NULL");
-                    return CEC_ERR_INVALID_ARGUMENT;
-                }
-            }
-        }
-        return CEC_OK;
-    }
-
     // The layout of a batch of these (nonzero) chunk lengths in the slot (no device use).
     int place(const size_t* lens, size_t n, std::vector<size_t>* offs) const {
         offs->resize(n);
@@ -126,21 +108,9 @@ struct cec_parts_reader {
         s.present.assign(present, present + n * t);
         std::memcpy(s.h_exp, expected, n * t * 32);
         Spans spans;
-        size_t guess = 0, up = n * t * 32;
-        for (size_t k = 0; k < n; ++k) {
-            const size_t L = lens[k], cs = ragged_stride(L);
-            size_t loaded = 0, fill = 0;
-            for (size_t i = 0; i < t; ++i) {
-                if (present[k * t + i]) {
-                    spans.emplace_back(s.offs[k] + i * cs, s.offs[k] + i * cs + L);
-                    up += L;
-                    ++loaded;
-                } else if (fills_slot(i, d, data_only)) {
-                    ++fill;
-                }
-            }
-            if (loaded >= d) guess += fill * cs;
-        }
+        const size_t up =
+            n * t * 32 + plan::loaded_spans(t, lens, s.offs.data(), n, present, &spans);
+        const size_t guess = plan::return_guess(d, t, lens, n, present, data_only);
         HIP_TRY(hipMemcpyAsync(s.d_exp, s.h_exp, n * t * 32, hipMemcpyHostToDevice, s.stream));
         CEC_TRY(copy_spans(s.h_stage, s.d_base, spans, true, s.stream));
         CEC_TRY(cec_read_ragged_packed_async(codec, s.d_base, s.offs.data(), s.lens.data(), n,
@@ -317,7 +287,8 @@ int cec_parts_reader_submit_from(cec_parts_reader* rd, size_t slot, const uint8_
                                  const uint8_t* expected) {
     if (!rd || (n_parts && !shards)) return CEC_ERR_INVALID_ARGUMENT;
     CEC_TRY(rd->check(slot, chunk_lens, n_parts, present, expected));
-    CEC_TRY(rd->null_rule(shards, present, n_parts, "cec_parts_reader_submit_from"));
+    CEC_TRY(null_slot_rule("cec_parts_reader_submit_from", shards, present, n_parts, rd->d, rd->t,
+                           rd->data_only));
     ReadSlot& s = rd->slots[slot];
     std::vector<size_t> offs;
     CEC_TRY(rd->place(chunk_lens, n_parts, &offs));
@@ -350,7 +321,8 @@ int cec_parts_reader_scatter(cec_parts_reader* rd, size_t slot, uint8_t* const* 
     ReadSlot& s = rd->slots[slot];
     if (s.n_parts == 0) return CEC_OK;
     if (!shards) return CEC_ERR_INVALID_ARGUMENT;
-    CEC_TRY(rd->null_rule(shards, s.present.data(), s.n_parts, "cec_parts_reader_scatter"));
+    CEC_TRY(null_slot_rule("cec_parts_reader_scatter", shards, s.present.data(), s.n_parts, rd->d,
+                           rd->t, rd->data_only));
     CEC_TRY(rd->finish(s));
     CEC_TRY(rd->fetch_tail(s));
     rd->rebuilt_chunks(s, [&](size_t item, size_t at, size_t L) {
