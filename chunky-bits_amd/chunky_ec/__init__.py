@@ -144,6 +144,23 @@ _sig("cec_parts_pipeline_wait", [_vp, ctypes.c_size_t, ctypes.POINTER(_u8p), cty
                                  _szp])
 _sig("cec_parts_pipeline_query", [_vp, ctypes.c_size_t])
 _sig("cec_parts_pipeline_drain", [_vp])
+_u32p = ctypes.POINTER(ctypes.c_uint32)
+_sig("cec_sha_midstate_bytes", [], ctypes.c_size_t)
+_sig("cec_encode_hash_segments", [_vp, _vp, _szp, _vp, _szp, _szp, ctypes.c_size_t, _u32p, _u8p,
+                                  _vp, ctypes.c_size_t, _vp, _vp])
+_sig("cec_segment_pipeline_new", [_vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                  ctypes.c_size_t, ctypes.POINTER(_vp)])
+_sig("cec_segment_pipeline_free", [_vp], None)
+_sig("cec_segment_pipeline_depth", [_vp], ctypes.c_size_t)
+_sig("cec_segment_pipeline_acquire", [_vp, _szp])
+_sig("cec_segment_pipeline_submit_from", [_vp, ctypes.c_size_t, ctypes.POINTER(_u8p), _szp, _szp,
+                                          _szp, _u32p, ctypes.c_size_t, _szp])
+_sig("cec_segment_pipeline_wait", [_vp, ctypes.c_size_t, ctypes.POINTER(_u8p),
+                                   ctypes.POINTER(_u8p), _szp])
+_sig("cec_segment_pipeline_query", [_vp, ctypes.c_size_t])
+_sig("cec_segment_pipeline_drain", [_vp])
+_sig("cec_segment_pipeline_open_count", [_vp], ctypes.c_size_t)
+_sig("cec_segment_pipeline_abandon", [_vp, ctypes.c_uint32])
 _sig("cec_reconstruct_ragged", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, ctypes.c_int, _vp])
 _sig("cec_read_ragged", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp, _u8p,
                          ctypes.POINTER(ctypes.c_int), _vp])
@@ -699,6 +716,29 @@ def encode_hash_split(codec: ReedSolomon, data_ptr: int, data_offsets: Sequence[
                                       digests_ptr, _stream_ptr(stream)))
 
 
+SEG_FIRST, SEG_LAST = 1, 2
+MIDSTATE_BYTES = _lib.cec_sha_midstate_bytes()
+
+
+def encode_hash_segments(codec: ReedSolomon, data_ptr: int, data_offsets: Sequence[int],
+                         parity_ptr: int, parity_offsets: Sequence[int], seg_lens: Sequence[int],
+                         state_slots: Sequence[int], flags: Sequence[int], midstates_ptr: int,
+                         n_state_slots: int, digests_ptr: int, stream=None) -> None:
+    """:func:`encode_hash_split` over column segments (``cec_encode_hash_segments``): entry k is
+    ``seg_lens[k]`` columns of one part in the split layout over ``seg_lens``.  Its parity pieces
+    are written, and the SHA-256 chain of each of its d + p chunks starts (``SEG_FIRST``), resumes
+    from the records of state slot ``state_slots[k]`` in the device pool at ``midstates_ptr``
+    (``n_state_slots * (d + p)`` records of ``MIDSTATE_BYTES``), and with ``SEG_LAST`` ends: only
+    then is the entry's digest row written.  Successive segments of a part go in order on one
+    stream."""
+    n = len(seg_lens)
+    arr = lambda v: (ctypes.c_size_t * max(n, 1))(*v)  # noqa: E731
+    _check(_lib.cec_encode_hash_segments(
+        codec.handle, data_ptr, arr(data_offsets), parity_ptr, arr(parity_offsets), arr(seg_lens),
+        n, (ctypes.c_uint32 * max(n, 1))(*state_slots), (ctypes.c_uint8 * max(n, 1))(*flags),
+        midstates_ptr, n_state_slots, digests_ptr, _stream_ptr(stream)))
+
+
 def sha256_batch(batch: PartBatch, first_chunk: int, n_chunks: int, digests_ptr: int,
                  stream=None) -> None:
     s = batch.struct()
@@ -1201,6 +1241,91 @@ class PartsPipeline:
 
     def drain(self) -> None:
         _check(_lib.cec_parts_pipeline_drain(self._h))
+
+
+class SegmentPipeline:
+    """cec_segment_pipeline: :class:`PartsPipeline` whose batches carry column segments of parts,
+    so that a part with long chunks passes through in pieces and no batch waits for a long SHA-256
+    chain.  The midstates of the parts under way ("open", each holding an id below `max_open`
+    from its first to its last segment) stay on the device between batches.
+
+    Per batch: ``slot = pl.acquire()``, ``pl.submit_from(slot, entries)`` with entries
+    ``(buf, seg_offset, seg_len, open_id)`` (columns ``[seg_offset, seg_offset + seg_len)`` of each
+    of the part's chunks; the id of a whole part is ignored), later ``parity, digests =
+    pl.wait(slot)``: the parity pieces in the split layout of the batch's segment lengths and
+    ``[n][d+p][32]`` digests, whose rows are valid for the entries that ended their part.
+    """
+
+    def __init__(self, codec: ReedSolomon, slot_data_bytes: int, max_parts: int, depth: int = 3,
+                 max_open: int = 0):
+        h = _vp()
+        _check(_lib.cec_segment_pipeline_new(codec.handle, slot_data_bytes, max_parts, depth,
+                                             max_open, ctypes.byref(h)))
+        self._h = h
+        self.codec = codec  # keep the codec alive
+        self.d, self.p = codec.data_shard_count(), codec.parity_shard_count()
+        self.slot_data_bytes = slot_data_bytes
+        self.max_parts = max_parts
+        self.depth = depth
+        self.max_open = max_open
+        self._parity_bytes = [0] * depth
+
+    def __del__(self, _free=_lib.cec_segment_pipeline_free):
+        h = getattr(self, "_h", None)
+        if h:
+            _free(h)
+            self._h = None
+
+    def acquire(self) -> int:
+        slot = ctypes.c_size_t(0)
+        _check(_lib.cec_segment_pipeline_acquire(self._h, ctypes.byref(slot)))
+        return slot.value
+
+    def submit_from(self, slot: int, entries: Sequence) -> List[int]:
+        """``entries[k] = (buf, seg_offset, seg_len, open_id)``; returns the parts' chunk sizes."""
+        n = len(entries)
+        keep: list = []
+        m = max(n, 1)
+        ptrs = (_u8p * m)(*[_buf_ptr(e[0], keep) for e in entries])
+        lens = (ctypes.c_size_t * m)(*[_nbytes(e[0]) for e in entries])
+        offs = (ctypes.c_size_t * m)(*[e[1] for e in entries])
+        segs = (ctypes.c_size_t * m)(*[e[2] for e in entries])
+        ids = (ctypes.c_uint32 * m)(*[e[3] for e in entries])
+        cs = (ctypes.c_size_t * m)()
+        _check(_lib.cec_segment_pipeline_submit_from(self._h, slot, ptrs, lens, offs, segs, ids, n,
+                                                     cs))
+        self._parity_bytes[slot] = sum(self.p * ragged_stride(e[2]) for e in entries)
+        return list(cs[:n])
+
+    def wait(self, slot: int):
+        import numpy as np
+        par, dig = _u8p(), _u8p()
+        n = ctypes.c_size_t(0)
+        _check(_lib.cec_segment_pipeline_wait(self._h, slot, ctypes.byref(par), ctypes.byref(dig),
+                                              ctypes.byref(n)))
+        k, t = n.value, self.d + self.p
+        nb = self._parity_bytes[slot] if k else 0
+        parity = np.ctypeslib.as_array(par, shape=(max(nb, 1),))[:nb]
+        digests = np.ctypeslib.as_array(dig, shape=(max(k * t * 32, 1),))[: k * t * 32].reshape(
+            k, t, 32)
+        return parity, digests
+
+    def query(self, slot: int) -> bool:
+        """True when the slot's batch is complete (never blocks)."""
+        r = _lib.cec_segment_pipeline_query(self._h, slot)
+        if r < 0 or r > 1:
+            raise Error(r)
+        return bool(r)
+
+    def drain(self) -> None:
+        _check(_lib.cec_segment_pipeline_drain(self._h))
+
+    def open_count(self) -> int:
+        return _lib.cec_segment_pipeline_open_count(self._h)
+
+    def abandon(self, open_id: int) -> None:
+        """Closes an open id whose part will not be finished."""
+        _check(_lib.cec_segment_pipeline_abandon(self._h, open_id))
 
 
 class PartsReader:

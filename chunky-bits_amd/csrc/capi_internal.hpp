@@ -28,6 +28,7 @@
 #pragma GCC visibility push(hidden)
 
 #include "ragged_words.hpp"  // hidden like everything here: its templates export nothing
+#include "segment_words.hpp"
 
 namespace cec {
 
@@ -305,8 +306,11 @@ int split_layout(size_t d, size_t p, const size_t* lens, size_t n, size_t* doffs
 int split_check(size_t d, size_t p, const uint8_t* data, const size_t* doffs,
                 const uint8_t* parity, const size_t* poffs, const size_t* lens, size_t n);
 // Host-staged packing of n parts' data chunks into dst at offs (zero-padded), on up to 8 threads.
+// seg_offs / seg_lens (null: whole chunks): only those columns of every chunk, as pieces of
+// seg_lens[k] bytes.
 void pack_parts(uint8_t* dst, const size_t* offs, size_t d, const uint8_t* const* bufs,
-                const size_t* lengths, const size_t* chunk_lens, size_t n);
+                const size_t* lengths, const size_t* chunk_lens, size_t n,
+                const size_t* seg_offs = nullptr, const size_t* seg_lens = nullptr);
 // The launches of a ragged encode + SHA-256 of checked arguments on s.  poffs null: parity behind
 // each part's data (cec_encode_hash_ragged, `parity` unused); else the split layout.  hwords /
 // dwords: page-locked and device room of plan::ragged_words_bytes for the words, which a caller that
@@ -314,6 +318,23 @@ void pack_parts(uint8_t* dst, const size_t* offs, size_t d, const uint8_t* const
 int ragged_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, uint8_t* parity,
                   const size_t* poffs, const size_t* lens, size_t n, uint8_t* digests,
                   hipStream_t s, uint8_t* hwords = nullptr, uint8_t* dwords = nullptr);
+
+// ---- The segmented encode (ragged.cpp), as the segment pipeline (segment_pipeline.cpp) shares it. ----
+
+// Every check of cec_encode_hash_segments behind its null-pointer and zero-length checks; no
+// device use.
+int segments_check(size_t d, size_t p, const uint8_t* data, const size_t* doffs,
+                   const uint8_t* parity, const size_t* poffs, const size_t* seg_lens, size_t n,
+                   const uint32_t* slots, const uint8_t* flags, size_t n_slots);
+// The launches of a checked segmented encode on s: the GF(2^8) kernel over the entries, then the
+// resume launch.  hwords / dwords: page-locked and device room of plan::segment_words(t, n).bytes
+// (null: a buffer of the scratch pool).  The resume launch waits for before_hash and after_hash is
+// recorded behind it (either may be null).
+int segments_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, uint8_t* parity,
+                    const size_t* poffs, const size_t* seg_lens, size_t n, const uint32_t* slots,
+                    const uint8_t* flags, uint8_t* midstates, uint8_t* digests, hipStream_t s,
+                    uint8_t* hwords = nullptr, uint8_t* dwords = nullptr,
+                    hipEvent_t before_hash = nullptr, hipEvent_t after_hash = nullptr);
 
 // ---- The ragged read (ragged.cpp), as the read pipeline (ragged_read_pipeline.cpp) shares it. ----
 

@@ -225,6 +225,32 @@ hipError_t launch_sha256(const ShaParams& a, bool vec16, hipStream_t s);
 // when it does.
 bool use_split(uint64_t chunks);
 int device_cus();  // CUs of the current device
+// The SHA-256 lane kernel's occupancy rule (sha256_kernels.hip launch_lane): the dynamic LDS a
+// 256-thread workgroup reserves so that one wave runs per SIMD (two when the grid exceeds the
+// CUs), and the largest such reservation.
+size_t sha_lane_reservation(uint32_t grid_x);
+size_t sha_lane_reservation_max();
+
+// Resumable SHA-256 over a list of chunk segments (sha256_resume_kernels.hip), one lane per item:
+// item i hashes lens[i] bytes at ptrs[i] (16-byte aligned) onto the chain kept in the midstate
+// record midstates + record[i] * 48 (segment_words.hpp ShaMidstate).  flags[i] & 1 (FIRST): the
+// chain starts here, from the initial hash value and 0 prior bytes, and the record is not read.
+// flags[i] & 2 (LAST): the chain ends here, with the padding of a message of prior + lens[i]
+// bytes; the digest goes to digests + i * 32 and the record is not written.  Not LAST: lens[i]
+// is a multiple of 64, and the eight state words and prior + lens[i] are written to the record;
+// no digest byte is touched.  An item that is FIRST and LAST touches no record (midstates may be
+// null when every item is).  `order` lists the n_items items the launch hashes, longest first.
+struct ShaResumeParams {
+    const uint64_t* ptrs;
+    const uint64_t* lens;
+    const uint32_t* order;
+    const uint32_t* record;
+    const uint8_t* flags;
+    uint8_t* midstates;
+    uint8_t* digests;
+    uint32_t n_items;
+};
+hipError_t launch_sha256_resume(const ShaResumeParams& a, hipStream_t s);
 hipError_t launch_fill(const FillParams& a, hipStream_t s);
 
 // Packed <-> batch chunk moves (move_kernels.hip): packed chunk j (len bytes at packed + j*len)

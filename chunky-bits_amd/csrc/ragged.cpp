@@ -1,5 +1,6 @@
 // ragged.cpp — the ragged half of include/chunky_ec.h: parts of different chunk lengths in one
-// launch sequence (cec_encode_hash_ragged, cec_encode_hash_split, cec_reconstruct_ragged,
+// launch sequence (cec_encode_hash_ragged, cec_encode_hash_split, cec_encode_hash_segments, which
+// takes parts as column segments and resumes their SHA-256 chains, cec_reconstruct_ragged,
 // cec_verify_ragged, cec_read_ragged, cec_resilver_ragged and their _async forms, which plan the
 // decode on the device and never wait, cec_read_ragged_packed_async among them) and the host-staged calls on top of
 // them (cec_parts_encode, cec_parts_read, cec_parts_verify).  Part k's chunk i lies at
@@ -187,6 +188,82 @@ int cec::ragged_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, u
                                         v.dev(w.list.order), items, digests);
     HIP_TRY(launch_sha256(h, true, s));
     g_two_pass_seqs.fetch_add(1, std::memory_order_relaxed);
+    return CEC_OK;
+}
+
+// The checks of cec_encode_hash_segments behind its null-pointer and zero-length checks (no
+// device use): the split layout's rules over the segment lengths, then the segment rules.
+int cec::segments_check(size_t d, size_t p, const uint8_t* data, const size_t* doffs,
+                        const uint8_t* parity, const size_t* poffs, const size_t* seg_lens,
+                        size_t n, const uint32_t* slots, const uint8_t* flags, size_t n_slots) {
+    CEC_TRY(split_check(d, p, data, doffs, parity, poffs, seg_lens, n));
+    switch (plan::segment_rules(seg_lens, slots, flags, n, n_slots)) {
+        case 0: break;
+        case 1:
+            set_last_error("segments: an entry that is not CEC_SEG_LAST has a length that is no "
+                           "multiple of 64");
+            return CEC_ERR_INVALID_ARGUMENT;
+        case 2:
+            set_last_error("segments: a state slot is not below n_state_slots");
+            return CEC_ERR_INVALID_ARGUMENT;
+        default:
+            set_last_error("segments: two entries of one call name the same state slot");
+            return CEC_ERR_INVALID_ARGUMENT;
+    }
+    for (size_t k = 0; k < n; ++k)  // the kernel's record index is 32-bit
+        if (plan::touches_record(flags[k]) && (uint64_t(slots[k]) + 1) * (d + p) > 0xFFFFFFFFull)
+            return CEC_ERR_INVALID_ARGUMENT;
+    return CEC_OK;
+}
+
+// The launches of a checked segmented encode on `s`: one upload of the words, the GF(2^8) kernel
+// over the entries (to it a segment is a part of chunk length seg_lens[k] in the split layout) and
+// the resume launch over the n * (d + p) chunk segments (sha256_resume_kernels.hip).  Always two
+// passes.  The host arrays are copied into the words' page-locked side before this returns.
+// before_hash (null: none): an event the resume launch waits for; after_hash (null: none): an
+// event recorded behind it, for a caller that orders the chains of successive calls across streams.
+int cec::segments_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, uint8_t* parity,
+                         const size_t* poffs, const size_t* seg_lens, size_t n,
+                         const uint32_t* slots, const uint8_t* flags, uint8_t* midstates,
+                         uint8_t* digests, hipStream_t s, uint8_t* hwords, uint8_t* dwords,
+                         hipEvent_t before_hash, hipEvent_t after_hash) {
+    const size_t d = c->d, t = c->d + c->p, items = n * t;
+    uint32_t* drec = nullptr;
+    CEC_TRY(c->encode_record(&drec));
+    const plan::SegmentWords w = plan::segment_words(t, n);
+    Scratch sc;  // the words of a caller that has none: released on s behind the launches below
+    if (!hwords) {
+        CEC_TRY(sc.acquire(w.bytes, s));
+        hwords = sc.host();
+        dwords = sc.dev();
+    }
+    const plan::View v{hwords, dwords};
+    std::vector<uint64_t> disp(n);  // where entry k's parity piece 0 lies, behind its data pieces
+    for (size_t k = 0; k < n; ++k)
+        disp[k] = (reinterpret_cast<uint64_t>(parity) + poffs[k]) -
+                  (reinterpret_cast<uint64_t>(data) + doffs[k] + d * ragged_stride(seg_lens[k]));
+    const plan::ShaListWords& l = w.resume.list;
+    plan::sha_list(
+        seg_lens, n, t, [](size_t) { return true; },
+        [&](size_t k, size_t i, size_t cs) {
+            return i < d ? data + doffs[k] + i * cs : parity + poffs[k] + (i - d) * cs;
+        },
+        v.host(l.ptrs), v.host(l.lens), v.host(l.order));
+    plan::resume_items(slots, flags, n, t, v.host(w.resume.record), v.host(w.resume.flags));
+    const uint32_t total_units =
+        plan::part_records(ragged_unit_bytes(), doffs, seg_lens, nullptr, n, v.host(w.units),
+                           v.host(w.parts), disp.data());
+    HIP_TRY(hipMemcpyAsync(dwords, hwords, w.bytes, hipMemcpyHostToDevice, s));
+    const RaggedParams a = ragged_params(const_cast<uint8_t*>(data) /* split: only read */, drec,
+                                         v.dev(w.units), v.dev(w.parts), nullptr, n, total_units,
+                                         d, c->p, true);
+    HIP_TRY(launch_rs_encode_ragged(a, s));
+    if (before_hash) HIP_TRY(hipStreamWaitEvent(s, before_hash, 0));
+    const ShaResumeParams h{v.dev(l.ptrs),         v.dev(l.lens),         v.dev(l.order),
+                            v.dev(w.resume.record), v.dev(w.resume.flags), midstates,
+                            digests,               uint32_t(items)};
+    HIP_TRY(launch_sha256_resume(h, s));
+    if (after_hash) HIP_TRY(hipEventRecord(after_hash, s));
     return CEC_OK;
 }
 
@@ -503,17 +580,23 @@ void for_parts(size_t n, size_t bytes, Fn fn) {
 // The packing of a host-staged encode: data chunk j of part k (L_k bytes at
 // dst + offs[k] + j * stride(L_k)) = bytes [j*L, (j+1)*L) of the caller's lengths[k] bytes, zeros
 // behind.  Only those bytes are read.
+// With seg_offs / seg_lens (the segment pipeline): piece j of entry k is the columns
+// [seg_offs[k], + seg_lens[k]) of that chunk, seg_lens[k] bytes at dst + offs[k] + j *
+// stride(seg_lens[k]).
 void cec::pack_parts(uint8_t* dst, const size_t* offs, size_t d, const uint8_t* const* bufs,
-                     const size_t* lengths, const size_t* chunk_lens, size_t n) {
+                     const size_t* lengths, const size_t* chunk_lens, size_t n,
+                     const size_t* seg_offs, const size_t* seg_lens) {
     size_t in_bytes = 0;
-    for (size_t k = 0; k < n; ++k) in_bytes += lengths[k];
+    for (size_t k = 0; k < n; ++k) in_bytes += seg_lens ? d * seg_lens[k] : lengths[k];
     for_parts(n, in_bytes, [&](size_t k) {
-        const size_t L = chunk_lens[k], cs = ragged_stride(L), len = lengths[k];
+        const size_t L = chunk_lens[k], len = lengths[k];
+        const size_t piece = seg_lens ? seg_lens[k] : L, cs = ragged_stride(piece);
         for (size_t j = 0; j < d; ++j) {
             uint8_t* to = dst + offs[k] + j * cs;
-            const size_t b0 = j * L, have = b0 < len ? std::min(L, len - b0) : 0;
+            const size_t b0 = j * L + (seg_offs ? seg_offs[k] : 0);
+            const size_t have = b0 < len ? std::min(piece, len - b0) : 0;
             if (have) std::memcpy(to, bufs[k] + b0, have);
-            if (have < L) std::memset(to + have, 0, L - have);
+            if (have < piece) std::memset(to + have, 0, piece - have);
         }
     });
 }
@@ -791,6 +874,35 @@ int cec_encode_hash_split(const cec_codec* cc, const uint8_t* data_base,
     return ragged_launch(const_cast<cec_codec*>(cc), data_base, data_offsets, parity_base,
                          parity_offsets, chunk_lens, n_parts, digests,
                          static_cast<hipStream_t>(stream));
+}
+
+size_t cec_sha_midstate_bytes(void) { return plan::kMidstateBytes; }
+
+int cec_encode_hash_segments(const cec_codec* cc, const uint8_t* data_base,
+                             const size_t* data_offsets, uint8_t* parity_base,
+                             const size_t* parity_offsets, const size_t* seg_lens, size_t n_segs,
+                             const uint32_t* state_slots, const uint8_t* flags, uint8_t* midstates,
+                             size_t n_state_slots, uint8_t* digests, void* stream) {
+    if (!cc) return CEC_ERR_INVALID_ARGUMENT;
+    if (n_segs == 0) return CEC_OK;
+    if (!data_base || !data_offsets || !parity_base || !parity_offsets || !seg_lens ||
+        !state_slots || !flags || !digests)
+        return CEC_ERR_INVALID_ARGUMENT;
+    size_t items = 0;  // SHA-256 items are 32-bit (checked before the arrays are walked)
+    if (__builtin_mul_overflow(n_segs, cc->d + cc->p, &items) || items > 0xFFFFFFFFull)
+        return CEC_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; !midstates && k < n_segs; ++k)
+        if (plan::touches_record(flags[k])) return CEC_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < n_segs; ++k)
+        if (seg_lens[k] == 0) return CEC_EMPTY_SHARD;
+    if (reinterpret_cast<uintptr_t>(midstates) % kRaggedAlign) return CEC_ERR_INVALID_ARGUMENT;
+    CEC_TRY(segments_check(cc->d, cc->p, data_base, data_offsets, parity_base, parity_offsets,
+                           seg_lens, n_segs, state_slots, flags, n_state_slots));
+    int dev = 0;
+    CEC_TRY(current_device(&dev));
+    return segments_launch(const_cast<cec_codec*>(cc), data_base, data_offsets, parity_base,
+                           parity_offsets, seg_lens, n_segs, state_slots, flags, midstates, digests,
+                           static_cast<hipStream_t>(stream));
 }
 
 int cec_parts_encode(const cec_codec* cc, const uint8_t* const* data_bufs, const size_t* lengths,

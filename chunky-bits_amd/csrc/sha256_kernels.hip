@@ -284,6 +284,14 @@ hipError_t launch_split(const ShaParams& a, bool vec16, hipStream_t s) {
 
 }  // namespace
 
+// The lane kernel's one-wave-per-SIMD reservation (launch_lane's rule), for the other lane-per-item
+// kernels (sha256_resume_kernels.hip): the dynamic LDS a 256-thread workgroup of a grid of
+// `grid_x` workgroups asks for, and the most it ever asks for (the kernel's attribute).
+size_t sha_lane_reservation(uint32_t grid_x) {
+    return grid_x > uint32_t(device_cus()) ? kCuReservation2 : kCuReservation;
+}
+size_t sha_lane_reservation_max() { return kCuReservation; }
+
 // CUs of the current device (cached per device ordinal); 256 when unknown.
 int device_cus() {
     static std::atomic<uint32_t> cache[kMaxDevices];

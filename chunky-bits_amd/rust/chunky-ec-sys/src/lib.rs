@@ -39,6 +39,11 @@ pub mod sys {
     }
 
     #[repr(C)]
+    pub struct cec_segment_pipeline {
+        _private: [u8; 0],
+    }
+
+    #[repr(C)]
     pub struct cec_multi {
         _private: [u8; 0],
     }
@@ -719,6 +724,77 @@ pub mod sys {
                 bytes_down: *mut u64,
                 tail_copies: *mut u64,
             );
+        }
+    }
+
+    /// include/chunky_ec_segments.h: segmented ragged writes (resumable SHA-256 over column
+    /// segments of parts) and the segment pipeline, function for function.  Declarations only:
+    /// the crate has no loop on top of them.
+    pub mod segments {
+        use super::*;
+
+        pub const CEC_SEG_FIRST: std::os::raw::c_uint = 1;
+        pub const CEC_SEG_LAST: std::os::raw::c_uint = 2;
+
+        extern "C" {
+            pub fn cec_sha_midstate_bytes() -> usize;
+            pub fn cec_encode_hash_segments(
+                codec: *const cec_codec,
+                data_base: *const u8,
+                data_offsets: *const usize,
+                parity_base: *mut u8,
+                parity_offsets: *const usize,
+                seg_lens: *const usize,
+                n_segs: usize,
+                state_slots: *const u32,
+                flags: *const u8,
+                midstates: *mut u8,
+                n_state_slots: usize,
+                digests: *mut u8,
+                stream: *mut c_void,
+            ) -> c_int;
+            pub fn cec_segment_pipeline_new(
+                codec: *const cec_codec,
+                slot_data_bytes: usize,
+                max_parts: usize,
+                depth: usize,
+                max_open: usize,
+                out: *mut *mut cec_segment_pipeline,
+            ) -> c_int;
+            pub fn cec_segment_pipeline_free(pipeline: *mut cec_segment_pipeline);
+            pub fn cec_segment_pipeline_depth(pipeline: *const cec_segment_pipeline) -> usize;
+            pub fn cec_segment_pipeline_acquire(
+                pipeline: *mut cec_segment_pipeline,
+                slot: *mut usize,
+            ) -> c_int;
+            pub fn cec_segment_pipeline_submit_from(
+                pipeline: *mut cec_segment_pipeline,
+                slot: usize,
+                data_bufs: *const *const u8,
+                lengths: *const usize,
+                seg_offsets: *const usize,
+                seg_lens: *const usize,
+                open_ids: *const u32,
+                n_parts: usize,
+                chunksizes: *mut usize,
+            ) -> c_int;
+            pub fn cec_segment_pipeline_wait(
+                pipeline: *mut cec_segment_pipeline,
+                slot: usize,
+                parity: *mut *const u8,
+                digests: *mut *const u8,
+                n_parts: *mut usize,
+            ) -> c_int;
+            pub fn cec_segment_pipeline_query(
+                pipeline: *mut cec_segment_pipeline,
+                slot: usize,
+            ) -> c_int;
+            pub fn cec_segment_pipeline_drain(pipeline: *mut cec_segment_pipeline) -> c_int;
+            pub fn cec_segment_pipeline_open_count(pipeline: *const cec_segment_pipeline) -> usize;
+            pub fn cec_segment_pipeline_abandon(
+                pipeline: *mut cec_segment_pipeline,
+                id: u32,
+            ) -> c_int;
         }
     }
 }

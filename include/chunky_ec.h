@@ -783,5 +783,7 @@ uint8_t cec_synth_byte(uint64_t seed, uint64_t part, uint64_t chunk, uint64_t of
 /* So have the ragged read with a packed return and the ragged read pipeline
  * (cec_read_ragged_packed_async, cec_parts_reader_*). */
 #include "chunky_ec_parts_read.h"
+/* And the segmented ragged writes (cec_encode_hash_segments, cec_segment_pipeline_*). */
+#include "chunky_ec_segments.h"
 
 #endif /* CHUNKY_EC_H */

@@ -47,6 +47,7 @@
 #include <vector>
 
 #include "chunky_ec.h"
+#include "chunky_ec_segment_plan.hpp"
 
 namespace chunky_ec {
 
@@ -394,6 +395,36 @@ inline cec_parts_pipeline* cached_parts_pipeline(size_t d, size_t p, size_t slot
         cec_parts_pipeline* raw = nullptr;
         check(cec_parts_pipeline_new(e.codec->raw(), slot_bytes, max_parts, depth, &raw));
         e.pipe = std::shared_ptr<cec_parts_pipeline>(raw, cec_parts_pipeline_free);
+        e.key = key;
+    }
+    return e.pipe.get();
+}
+
+// The calling thread's most recent segment pipeline (write_many_stream under many_segment), kept
+// the same way: per (d, p, slot bytes, parts per slot, depth, open parts) and device.
+struct CachedSegmentPipeline {
+    std::vector<size_t> key;
+    std::shared_ptr<ReedSolomon> codec;
+    std::shared_ptr<cec_segment_pipeline> pipe;
+};
+inline CachedSegmentPipeline& cached_segment_pipeline_entry() {
+    thread_local CachedSegmentPipeline e;
+    return e;
+}
+inline cec_segment_pipeline* cached_segment_pipeline(size_t d, size_t p, size_t slot_bytes,
+                                                     size_t max_parts, size_t depth,
+                                                     size_t max_open) {
+    CachedSegmentPipeline& e = cached_segment_pipeline_entry();
+    int device = 0;
+    check(cec_current_device(&device));
+    const std::vector<size_t> key{d, p, slot_bytes, max_parts, depth, max_open, size_t(device)};
+    if (!e.pipe || e.key != key) {
+        e.pipe.reset();
+        e.codec = std::make_shared<ReedSolomon>(d, p);
+        cec_segment_pipeline* raw = nullptr;
+        check(cec_segment_pipeline_new(e.codec->raw(), slot_bytes, max_parts, depth, max_open,
+                                       &raw));
+        e.pipe = std::shared_ptr<cec_segment_pipeline>(raw, cec_segment_pipeline_free);
         e.key = key;
     }
     return e.pipe.get();
@@ -2330,6 +2361,7 @@ class FileWriteBuilder {
     std::vector<FileReference> write_many_stream(
         const std::vector<std::pair<const uint8_t*, size_t>>& files, ChunkStore& dest) const {
         if (concurrency_ <= 1) throw std::invalid_argument("concurrency must be > 1");  // :128
+        if (many_segment_) return write_many_segments(files, dest);
         const size_t d = data_, p = parity_, t = d + p;
         // never smaller than one part, so every part fits a slot
         const size_t slot_bytes = std::max(many_slot_bytes_, d * cec_ragged_stride(chunk_size_));
@@ -2403,6 +2435,20 @@ class FileWriteBuilder {
     }
     static constexpr size_t kManySlotParts = 4096;  // parts a slot's batch holds at most
 
+    // Segmented write_many_stream: a gathered part whose chunks are longer than `bytes` goes
+    // through a segment pipeline (cec_segment_pipeline_*) as column segments of `bytes`, one per
+    // batch, so that no batch waits for a long chunk's SHA-256 chain; up to max_open such parts
+    // are under way at once.  Same FileReferences, stored chunks and order towards dest.
+    // 0 (the default) is off: write_many_stream does exactly what it does without this option.
+    // max_open == 0: as many as a slot holds segments (a batch's SHA-256 launch takes as long
+    // as one segment's chain however many chains it holds, so wide batches are the cheap ones).
+    FileWriteBuilder& many_segment(size_t bytes, size_t max_open = 0) {
+        if (bytes % 64) throw std::invalid_argument("many_segment: a multiple of 64");
+        many_segment_ = bytes;
+        many_open_ = max_open;
+        return *this;
+    }
+
    public:
     // The page-locked windows of the calling thread's batched writes (see release_thread_buffers).
     struct WriteWindow {
@@ -2426,6 +2472,8 @@ class FileWriteBuilder {
     std::vector<int> devices_;
     size_t many_slot_bytes_ = size_t(64) << 20;  // write_many_stream's slots (many_slots)
     size_t many_depth_ = 3;
+    size_t many_segment_ = 0;  // columns per segment of write_many_stream (many_segment); 0: off
+    size_t many_open_ = 0;     // parts under way at most; 0: as many as a slot holds segments
 
     // A part the many-files calls gathered: `length` bytes of file `file`.
     struct ManyPart {
@@ -2433,6 +2481,124 @@ class FileWriteBuilder {
         const uint8_t* bytes;
         size_t length;
     };
+
+    // write_many_stream under many_segment.  The gathered parts between two scheduler runs (all
+    // of them without batch()) are planned as one list (detail::SegmentPlanner).
+    std::vector<FileReference> write_many_segments(
+        const std::vector<std::pair<const uint8_t*, size_t>>& files, ChunkStore& dest) const {
+        const size_t d = data_, p = parity_;
+        const size_t slot_bytes = std::max(many_slot_bytes_, d * cec_ragged_stride(chunk_size_));
+        const size_t max_open = many_open_ ? many_open_
+            : std::max<size_t>(1, std::min(kManySlotParts,
+                                           slot_bytes / (d * cec_ragged_stride(many_segment_))));
+        cec_segment_pipeline* pl = detail::cached_segment_pipeline(
+            d, p, slot_bytes, kManySlotParts, many_depth_, max_open);
+        std::vector<FileReference> out(files.size());
+        detail::ManyWindow<ManyPart> window;  // no budget: the planner has the slots'
+        window.cap = SIZE_MAX;
+        try {
+            gather_many(
+                files, dest, out, window,
+                [&](const std::vector<ManyPart>& pend) {
+                    segmented_parts(pl, slot_bytes, max_open, pend, dest, out);
+                },
+                [] {}, [](size_t) { return size_t(0); });
+        } catch (...) {  // nothing of this call stays in flight or open
+            (void)cec_segment_pipeline_drain(pl);
+            for (size_t id = 0; id < max_open; ++id)
+                (void)cec_segment_pipeline_abandon(pl, uint32_t(id));
+            throw;
+        }
+        return out;
+    }
+
+    // The parts `pend` through the segment pipeline, their FileParts appended to their files in
+    // the order of `pend`.  A batch is what the planner says; while later batches are packed and
+    // encoded the oldest is collected: the parity pieces of a part that spans batches are put
+    // together in a buffer of its own, and a part that is complete while an earlier one is still
+    // open is held, its parity and digests copied out of the slot, until its turn.  A whole part
+    // whose turn it is goes to dest straight from the slot's page-locked region.
+    void segmented_parts(cec_segment_pipeline* pl, size_t slot_bytes, size_t max_open,
+                         const std::vector<ManyPart>& pend, ChunkStore& dest,
+                         std::vector<FileReference>& out) const {
+        const size_t d = data_, p = parity_, t = d + p, n = pend.size();
+        std::vector<size_t> L(n);
+        for (size_t k = 0; k < n; ++k) L[k] = (pend[k].length + d - 1) / d;
+        detail::SegmentPlanner plan(d, many_segment_, slot_bytes, kManySlotParts, max_open, L);
+        struct Held {
+            Bytes parity, digests;  // [p][L] and [t][32]
+        };
+        std::vector<Held> held(n);
+        struct Batch {
+            size_t slot;
+            std::vector<detail::SegmentEntry> entries;
+        };
+        std::deque<Batch> flying;  // oldest first
+        auto emit = [&](size_t k, const uint8_t* digests, auto&& parity_of) {
+            out[pend[k].file].parts.push_back(many_part(dest, pend[k], L[k], digests, parity_of));
+        };
+        auto collect = [&] {
+            Batch b = std::move(flying.front());
+            flying.pop_front();
+            const size_t m = b.entries.size();
+            const uint8_t *parity = nullptr, *digests = nullptr;
+            size_t got = 0;
+            detail::check(cec_segment_pipeline_wait(pl, b.slot, &parity, &digests, &got));
+            if (got != m) throw std::logic_error("write_many_stream: a slot lost its batch");
+            std::vector<size_t> lens(m), doffs(m), poffs(m);
+            for (size_t q = 0; q < m; ++q) lens[q] = b.entries[q].len;
+            size_t data_bytes = 0, parity_bytes = 0;
+            detail::check(cec_split_layout(d, p, lens.data(), m, doffs.data(), poffs.data(),
+                                           &data_bytes, &parity_bytes));
+            for (size_t q = 0; q < m; ++q) {
+                const detail::SegmentEntry& e = b.entries[q];
+                const size_t cs = cec_ragged_stride(e.len);
+                const uint8_t* piece = parity + poffs[q];
+                if (e.first && e.last && plan.released() == e.part) {  // its turn: no copy
+                    emit(e.part, digests + q * t * 32, [&](size_t i) { return piece + i * cs; });
+                    plan.complete(e.part);
+                    plan.release();
+                } else {
+                    Held& h = held[e.part];
+                    h.parity.resize(p * L[e.part]);
+                    for (size_t i = 0; i < p; ++i)
+                        std::memcpy(&h.parity[i * L[e.part] + e.off], piece + i * cs, e.len);
+                    if (e.last) {
+                        h.digests.assign(digests + q * t * 32, digests + (q + 1) * t * 32);
+                        plan.complete(e.part);
+                    }
+                }
+                for (size_t k; (k = plan.releasable()) != detail::SegmentPlanner::npos;) {
+                    emit(k, held[k].digests.data(),
+                         [&](size_t i) { return &held[k].parity[i * L[k]]; });
+                    held[k] = Held{};
+                    plan.release();
+                }
+            }
+        };
+        while (!plan.planned()) {
+            if (flying.size() == many_depth_) collect();  // the slot that comes round next
+            Batch b{0, plan.next_batch()};
+            const size_t m = b.entries.size();
+            std::vector<const uint8_t*> bufs(m);
+            std::vector<size_t> lengths(m), offs(m), lens(m), chunksizes(m);
+            std::vector<uint32_t> ids(m);
+            for (size_t q = 0; q < m; ++q) {
+                const detail::SegmentEntry& e = b.entries[q];
+                bufs[q] = pend[e.part].bytes;
+                lengths[q] = pend[e.part].length;
+                offs[q] = e.off;
+                lens[q] = e.len;
+                ids[q] = e.id;
+            }
+            detail::check(cec_segment_pipeline_acquire(pl, &b.slot));
+            detail::check(cec_segment_pipeline_submit_from(pl, b.slot, bufs.data(), lengths.data(),
+                                                           offs.data(), lens.data(), ids.data(), m,
+                                                           chunksizes.data()));
+            flying.push_back(std::move(b));
+        }
+        while (!flying.empty()) collect();
+    }
 
     // The gather loop of write_many / write_many_stream.  The full parts of a file with at least
     // two of them go through write_full_parts when batch() is set, after flush and settle() have
@@ -2556,6 +2722,7 @@ inline void release_thread_buffers() {
     }
     detail::cached_multi_entry() = detail::CachedMulti{};
     detail::cached_parts_pipeline_entry() = detail::CachedPartsPipeline{};
+    detail::cached_segment_pipeline_entry() = detail::CachedSegmentPipeline{};
     detail::cached_parts_reader_entry() = detail::CachedPartsReader{};
 }
 

@@ -20,6 +20,17 @@ Every arm is warmed up, then the arms alternate three times in one process; the 
 synchronised before each clock reading.  Reported: GB/s of file bytes and parts/s per repeat.
 All arms' digests must agree (asserted).
 
+--segment BYTES[,BYTES...]: the same files and shapes through three arms that alternate: (a) the one
+cec_parts_encode call (arm b above), (b) the parts pipeline (arm d above, one arm per --depths
+entry) and (c) the segment pipeline, cec_segment_pipeline_submit_from, one arm per segment size
+and --depths entry: a part whose chunks are longer than the segment goes as column segments, one
+per batch, each batch first taking the next segment of every open part (--max-open at most;
+default: as many as a slot holds segments) and then new parts while the slot lasts (the plan is made before the clock starts, as for b).  The digests of
+the entries that end a part are copied out; the parity stays in the slots (put together and
+compared with a's once, untimed).  All arms' digests must agree (asserted).  A segment arm counts
+as faster than an incumbent only if its worst repeat is below the incumbent's best, and a switch
+of a default needs that at both shapes.
+
 --device: 4096 x RS(10,4) x 64 KiB parts, device resident: cec_encode_hash_ragged with uniform
 lengths, by its two-pass path (CEC_RAGGED_FUSED=0) and by the fused kernel (=1), and
 cec_encode_hash_split (the same parts, data and parity in regions of their own) against
@@ -72,6 +83,7 @@ Every arm must find every chunk good, and the one chunk that is flipped before t
 
     python tools/small_files_bench.py [--files 4096] [--repeats 3] [--shapes 3,2:10,4]
                                       [--slot-mib 64] [--depths 3,2] [--no-per-part]
+    python tools/small_files_bench.py --segment 16384,65536,262144 [--slot-mib 64] [--depths 3,2]
     python tools/small_files_bench.py --device
     python tools/small_files_bench.py --read [--slot-mib 64] [--depths 3,2] [--no-per-part]
     python tools/small_files_bench.py --verify
@@ -240,6 +252,105 @@ class Workload:
         return dig
 
 
+    def make_segment_pipeline(self, slot_bytes, depth, segment, max_parts=4096, max_open=None):
+        """A cec_segment_pipeline and the plan of its batches, made before any clock starts: each
+        batch takes the next segment of every open part, in part order, then new parts while the
+        slot, max_parts and the open ids last (the rule of FileWriteBuilder::many_segment).  Per
+        batch: the entries (part, offset, length, last), the call's arrays, and for the entries
+        that end a part their rows and parts."""
+        d = self.d
+        slot_bytes = max(slot_bytes, d * ce.ragged_stride(CHUNK))
+        if not max_open:  # as many open parts as a slot holds segments (many_segment's default)
+            max_open = max(1, min(max_parts, slot_bytes // (d * ce.ragged_stride(segment))))
+        pl = ce.SegmentPipeline(self.rs, slot_bytes, max_parts, depth, max_open)
+        free, open_parts, nxt, plan = list(range(max_open))[::-1], [], 0, []
+        while nxt < self.n or open_parts:
+            batch, room, still, freed = [], slot_bytes, [], []
+
+            def fits(ln):
+                return len(batch) < max_parts and d * ce.ragged_stride(ln) <= room
+            for k, done, oid in open_parts:
+                ln = min(segment, self.L[k] - done)
+                if not fits(ln):
+                    still.append((k, done, oid))
+                    continue
+                batch.append((k, done, ln, oid))
+                room -= d * ce.ragged_stride(ln)
+                if done + ln == self.L[k]:
+                    freed.append(oid)
+                else:
+                    still.append((k, done + ln, oid))
+            while nxt < self.n:
+                ln = min(segment, self.L[nxt])
+                whole = ln == self.L[nxt]
+                if not fits(ln) or (not whole and not free):
+                    break
+                oid = 0 if whole else free.pop()
+                if not whole:
+                    still.append((nxt, ln, oid))
+                batch.append((nxt, 0, ln, oid))
+                room -= d * ce.ragged_stride(ln)
+                nxt += 1
+            free += freed
+            open_parts = still
+            m = len(batch)
+            last = [q for q, (k, off, ln, _) in enumerate(batch) if off + ln == self.L[k]]
+            plan.append({
+                "entries": batch,
+                "bufs": (U8P * m)(*[self.ptrs[k] for k, _, _, _ in batch]),
+                "lengths": (ctypes.c_size_t * m)(*[self.lens[k] for k, _, _, _ in batch]),
+                "offs": (ctypes.c_size_t * m)(*[e[1] for e in batch]),
+                "segs": (ctypes.c_size_t * m)(*[e[2] for e in batch]),
+                "ids": (ctypes.c_uint32 * m)(*[e[3] for e in batch]),
+                "cs": (ctypes.c_size_t * m)(),
+                "last_rows": np.array(last, np.int64),
+                "last_parts": np.array([batch[q][0] for q in last], np.int64)})
+        return pl, plan
+
+    def arm_segments(self, pipe, check_parity=False):
+        """Every planned batch through the segment pipeline's slots; while later slots run the
+        oldest is collected: the digests of the entries that end a part copied out, the parity
+        pieces left in the slot's pinned region unless check_parity puts them together and
+        compares them with self.parity."""
+        pl, plan = pipe
+        dig = self.digests()
+        lib, h, t = ce._lib, pl._h, self.t
+        slot, par, dg, n = ctypes.c_size_t(0), U8P(), U8P(), ctypes.c_size_t(0)
+        pending = []
+        got_par = np.zeros_like(self.parity) if check_parity else None
+
+        def collect():
+            s, b = pending.pop(0)
+            ce._check(lib.cec_segment_pipeline_wait(h, s, ctypes.byref(par), ctypes.byref(dg),
+                                                    ctypes.byref(n)))
+            m = len(b["entries"])
+            assert n.value == m
+            rows = np.ctypeslib.as_array(dg, shape=(m, t, 32))
+            dig[b["last_parts"]] = rows[b["last_rows"]]
+            if check_parity:
+                _, poffs, _, pb = ce.split_layout(self.d, self.p, [e[2] for e in b["entries"]])
+                got = np.ctypeslib.as_array(par, shape=(pb,))
+                for (k, off, ln, _), po in zip(b["entries"], poffs):
+                    cs = ce.ragged_stride(ln)
+                    for i in range(self.p):
+                        to = int(self.par_off[k]) + i * self.L[k] + off
+                        got_par[to:to + ln] = got[po + i * cs:po + i * cs + ln]
+        for b in plan:
+            if len(pending) == pl.depth:
+                collect()
+            ce._check(lib.cec_segment_pipeline_acquire(h, ctypes.byref(slot)))
+            ce._check(lib.cec_segment_pipeline_submit_from(
+                h, slot.value, b["bufs"], b["lengths"], b["offs"], b["segs"], b["ids"],
+                len(b["entries"]), b["cs"]))
+            pending.append((slot.value, b))
+        while pending:
+            collect()
+        assert pl.open_count() == 0
+        if check_parity:
+            assert np.array_equal(got_par, self.parity), "assembled parity differs from a's"
+        return dig
+
+
 def set_env_knob(name, value):
     """CEC_* knob `name` = value (None: unset) from the next call on."""
     if value is None:
@@ -359,6 +470,64 @@ def host_staged(args):
         results.append(row)
         del w, pipes
     print(json.dumps({"tool": "small_files_bench", "mode": "host", "results": results}))
+
+
+def host_segments(args):
+    """--segment: the one call, the parts pipeline and the segment pipeline, alternating."""
+    pool, files = make_files(args.files)
+    results = []
+    slot = args.slot_mib << 20
+    for shape in args.shapes.split(":"):
+        d, p = (int(x) for x in shape.split(","))
+        w = Workload(pool, files, d, p)
+        print(f"== RS({d},{p}) chunk 1 MiB: {len(files)} files, {w.file_bytes / 2**30:.2f} GiB, "
+              f"{w.n} parts, longest chunk {max(w.L)} bytes", flush=True)
+        arms = [("a: one parts_encode call", w.arm_ragged)]
+        for depth in args.depths:
+            pipe = w.make_pipeline(slot, depth)
+            arms.append((f"b: parts pipeline {args.slot_mib} MiB x {depth}",
+                         lambda pipe=pipe: w.arm_pipeline(pipe)))
+        seg_pipes = {}
+        for seg in args.segment:
+            for depth in args.depths:
+                size = f"{seg >> 10} KiB" if seg % 1024 == 0 else f"{seg} B"
+                name = f"c: segment pipeline {size} segments, {args.slot_mib} MiB x {depth}"
+                seg_pipes[name] = w.make_segment_pipeline(slot, depth, seg,
+                                                          max_open=args.max_open)
+                arms.append((name, lambda pipe=seg_pipes[name]: w.arm_segments(pipe)))
+                print(f"   {name}: {len(seg_pipes[name][1])} batches, up to "
+                      f"{seg_pipes[name][0].max_open} parts open", flush=True)
+        for name, fn in arms:
+            sec, _ = timed(fn)
+            print(f"   warm-up {name}: {sec:.3f} s", flush=True)
+        for name, pipe in seg_pipes.items():  # c's parity against a's (untimed)
+            w.arm_segments(pipe, check_parity=True)
+        print("   c: the parity pieces in the slots, put together, equal a's parity", flush=True)
+        secs = {name: [] for name, _ in arms}
+        ref = None
+        for rep in range(args.repeats):
+            for name, fn in arms:
+                sec, dig = timed(fn)
+                secs[name].append(sec)
+                if ref is None:
+                    ref = dig
+                assert np.array_equal(dig, ref), f"digests of '{name}' differ"
+                print(f"   repeat {rep + 1} {name}: {sec:.3f} s  "
+                      f"{w.file_bytes / sec / 1e9:7.2f} GB/s", flush=True)
+        print("   digests agree across all arms and repeats")
+        gbps = {k: [w.file_bytes / x / 1e9 for x in v] for k, v in secs.items()}
+        row = {"d": d, "p": p, "files": len(files), "parts": w.n, "file_bytes": w.file_bytes,
+               "seconds": secs, "gbps": gbps, "verdicts": {}}
+        for name in seg_pipes:
+            for inc in [n for n, _ in arms if n[0] in "ab"]:
+                wins = min(gbps[name]) > max(gbps[inc])
+                row["verdicts"][f"{name} over {inc}"] = wins
+                print(f"   {name}: {min(gbps[name]):.2f}-{max(gbps[name]):.2f} GB/s against "
+                      f"{inc}: {min(gbps[inc]):.2f}-{max(gbps[inc]):.2f} GB/s -> worst above the "
+                      f"incumbent's best: {wins}", flush=True)
+        results.append(row)
+        del w, seg_pipes, arms
+    print(json.dumps({"tool": "small_files_bench", "mode": "segment", "results": results}))
 
 
 def oracle_store(pool, parts, L, d, p):
@@ -1152,12 +1321,20 @@ def main():
                     help="host mode and --read: leave out the a arms")
     ap.add_argument("--per-part-only", action="store_true",
                     help="host mode and --read: the a arms alone (the CEC_COALESCE_MIXED A/B)")
+    ap.add_argument("--segment", type=lambda s: [int(x) for x in s.split(",")], default=None,
+                    metavar="BYTES[,BYTES...]",
+                    help="the one call, the parts pipeline and the segment pipeline at these "
+                         "segment sizes (multiples of 64 bytes)")
+    ap.add_argument("--max-open", type=int, default=0,
+                    help="--segment: parts under way at most (0: as many as a slot holds segments)")
     ap.add_argument("--device", action="store_true")
     ap.add_argument("--read", action="store_true")
     ap.add_argument("--verify", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
-    if args.device:
+    if args.segment:
+        host_segments(args)
+    elif args.device:
         if args.read:
             device_read(args)
             device_read_async(args)
