@@ -528,10 +528,15 @@ struct cec_multi {
             if (f.staged_in || f.staged_out) {
                 // every depth slot at once (see run_write); an AHEAD slot's when it is used
                 hipError_t e = hipSuccess;
+                const size_t in_bytes = f.staged_in ? P * cw : 0, out_bytes = f.staged_out ? P * dw : 0;
                 for (size_t i = 0; i < s.rstage.size(); ++i)
-                    if (e == hipSuccess && (i < depth || i == slot))
-                        e = s.rstage[i].reserve(f.staged_in ? P * cw : 0,
-                                                f.staged_out ? P * dw : 0, s.device);
+                    if (e == hipSuccess && (i < depth || i == slot)) {
+                        // a slot's staging grows (resilver's output after a read's) only once the
+                        // batch in flight on it, whose copies and results are in it, is finished
+                        if (s.rstage[i].in_cap < in_bytes || s.rstage[i].out_cap < out_bytes)
+                            finish_read(s, i);
+                        e = s.rstage[i].reserve(in_bytes, out_bytes, s.device);
+                    }
                 if (e != hipSuccess) {
                     finish_parts(job, count - at, CEC_ERR_OUT_OF_MEMORY,
                                  std::string("multi staging: ") + hipGetErrorString(e));
