@@ -161,6 +161,20 @@ _sig("cec_segment_pipeline_query", [_vp, ctypes.c_size_t])
 _sig("cec_segment_pipeline_drain", [_vp])
 _sig("cec_segment_pipeline_open_count", [_vp], ctypes.c_size_t)
 _sig("cec_segment_pipeline_abandon", [_vp, ctypes.c_uint32])
+_sig("cec_verify_segments", [_vp, _szp, _szp, ctypes.c_size_t, _u32p, _u8p, _vp, ctypes.c_size_t,
+                             _vp, _vp, _vp])
+_sig("cec_scrub_pipeline_new", [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                ctypes.POINTER(_vp)])
+_sig("cec_scrub_pipeline_free", [_vp], None)
+_sig("cec_scrub_pipeline_depth", [_vp], ctypes.c_size_t)
+_sig("cec_scrub_pipeline_acquire", [_vp, _szp])
+_sig("cec_scrub_pipeline_submit_from", [_vp, ctypes.c_size_t, ctypes.POINTER(_u8p), _szp, _szp,
+                                        _szp, _u32p, _u8p, ctypes.c_size_t])
+_sig("cec_scrub_pipeline_wait", [_vp, ctypes.c_size_t, ctypes.POINTER(_u8p), _szp])
+_sig("cec_scrub_pipeline_query", [_vp, ctypes.c_size_t])
+_sig("cec_scrub_pipeline_drain", [_vp])
+_sig("cec_scrub_pipeline_open_count", [_vp], ctypes.c_size_t)
+_sig("cec_scrub_pipeline_abandon", [_vp, ctypes.c_uint32])
 _sig("cec_reconstruct_ragged", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, ctypes.c_int, _vp])
 _sig("cec_read_ragged", [_vp, _vp, _szp, _szp, ctypes.c_size_t, _u8p, _vp, _u8p,
                          ctypes.POINTER(ctypes.c_int), _vp])
@@ -737,6 +751,25 @@ def encode_hash_segments(codec: ReedSolomon, data_ptr: int, data_offsets: Sequen
         codec.handle, data_ptr, arr(data_offsets), parity_ptr, arr(parity_offsets), arr(seg_lens),
         n, (ctypes.c_uint32 * max(n, 1))(*state_slots), (ctypes.c_uint8 * max(n, 1))(*flags),
         midstates_ptr, n_state_slots, digests_ptr, _stream_ptr(stream)))
+
+
+def verify_segments(base_ptr: int, offsets: Sequence[int], seg_lens: Sequence[int],
+                    state_slots: Sequence[int], flags: Sequence[int], midstates_ptr: int,
+                    n_state_slots: int, expected_ptr: int, ok_ptr: int, stream=None) -> None:
+    """:func:`verify_ragged` of single copies over segments (``cec_verify_segments``), queued on
+    the stream with no wait: entry k is ``seg_lens[k]`` bytes at ``base_ptr + offsets[k]``, the
+    layout of :func:`ragged_layout` with one chunk per part.  The SHA-256 chain of its copy starts
+    (``SEG_FIRST``), resumes from the record of state slot ``state_slots[k]`` in the device pool at
+    ``midstates_ptr`` (``n_state_slots`` records of ``MIDSTATE_BYTES``), and with ``SEG_LAST``
+    ends: only then is row k of the device rows ``[n][32]`` at ``expected_ptr`` read and byte k of
+    the device bytes at ``ok_ptr`` written, 1 if the whole copy has that digest, else 0.
+    Successive segments of a copy go in order on one stream."""
+    n = len(seg_lens)
+    arr = lambda v: (ctypes.c_size_t * max(n, 1))(*v)  # noqa: E731
+    _check(_lib.cec_verify_segments(
+        base_ptr, arr(offsets), arr(seg_lens), n, (ctypes.c_uint32 * max(n, 1))(*state_slots),
+        (ctypes.c_uint8 * max(n, 1))(*flags), midstates_ptr, n_state_slots, expected_ptr, ok_ptr,
+        _stream_ptr(stream)))
 
 
 def sha256_batch(batch: PartBatch, first_chunk: int, n_chunks: int, digests_ptr: int,
@@ -1326,6 +1359,86 @@ class SegmentPipeline:
     def abandon(self, open_id: int) -> None:
         """Closes an open id whose part will not be finished."""
         _check(_lib.cec_segment_pipeline_abandon(self._h, open_id))
+
+
+class ScrubPipeline:
+    """cec_scrub_pipeline: :func:`parts_verify` with `depth` slots in flight, whose batches carry
+    segments of stored copies, so that a long copy passes through in pieces and no batch waits for
+    a long SHA-256 chain.  The midstates of the copies under way ("open", each holding an id below
+    `max_open` from its first to its last segment) stay on the device between batches.  It runs on
+    the current device; there is no codec.
+
+    Per batch: ``slot = pl.acquire()``, ``pl.submit_from(slot, entries)`` with entries
+    ``(buf, seg_offset, seg_len, open_id, expected)`` (bytes ``[seg_offset, seg_offset + seg_len)``
+    of the copy ``buf``; the id of a whole copy is ignored; ``expected`` is the copy's 32-byte
+    digest, read only for the entry that ends the copy, else it may be None), later ``ok =
+    pl.wait(slot)``: one flag per entry, valid for the entries that ended their copy.
+    """
+
+    def __init__(self, slot_bytes: int, max_entries: int, depth: int = 3, max_open: int = 0):
+        h = _vp()
+        _check(_lib.cec_scrub_pipeline_new(slot_bytes, max_entries, depth, max_open,
+                                           ctypes.byref(h)))
+        self._h = h
+        self.slot_bytes = slot_bytes
+        self.max_entries = max_entries
+        self.depth = depth
+        self.max_open = max_open
+
+    def __del__(self, _free=_lib.cec_scrub_pipeline_free):
+        h = getattr(self, "_h", None)
+        if h:
+            _free(h)
+            self._h = None
+
+    def acquire(self) -> int:
+        slot = ctypes.c_size_t(0)
+        _check(_lib.cec_scrub_pipeline_acquire(self._h, ctypes.byref(slot)))
+        return slot.value
+
+    def submit_from(self, slot: int, entries: Sequence) -> None:
+        """``entries[k] = (buf, seg_offset, seg_len, open_id, expected)``."""
+        n = len(entries)
+        keep: list = []
+        m = max(n, 1)
+        ptrs = (_u8p * m)(*[_buf_ptr(e[0], keep) for e in entries])
+        lens = (ctypes.c_size_t * m)(*[_nbytes(e[0]) for e in entries])
+        offs = (ctypes.c_size_t * m)(*[e[1] for e in entries])
+        segs = (ctypes.c_size_t * m)(*[e[2] for e in entries])
+        ids = (ctypes.c_uint32 * m)(*[e[3] for e in entries])
+        rows = b"".join(bytes(e[4]) if e[4] is not None else bytes(32) for e in entries)
+        if len(rows) != 32 * n:
+            raise ValueError("an expected digest is not 32 bytes")
+        exp = (ctypes.c_uint8 * (32 * m)).from_buffer_copy(rows.ljust(32 * m, b"\0"))
+        _check(_lib.cec_scrub_pipeline_submit_from(self._h, slot, ptrs, lens, offs, segs, ids, exp,
+                                                   n))
+
+    def wait(self, slot: int):
+        import numpy as np
+        ok = _u8p()
+        n = ctypes.c_size_t(0)
+        _check(_lib.cec_scrub_pipeline_wait(self._h, slot, ctypes.byref(ok), ctypes.byref(n)))
+        k = n.value
+        if not k:
+            return np.zeros(0, np.uint8)
+        return np.ctypeslib.as_array(ok, shape=(k,))
+
+    def query(self, slot: int) -> bool:
+        """True when the slot's batch is complete (never blocks)."""
+        r = _lib.cec_scrub_pipeline_query(self._h, slot)
+        if r < 0 or r > 1:
+            raise Error(r)
+        return bool(r)
+
+    def drain(self) -> None:
+        _check(_lib.cec_scrub_pipeline_drain(self._h))
+
+    def open_count(self) -> int:
+        return _lib.cec_scrub_pipeline_open_count(self._h)
+
+    def abandon(self, open_id: int) -> None:
+        """Closes an open id whose copy will not be finished."""
+        _check(_lib.cec_scrub_pipeline_abandon(self._h, open_id))
 
 
 class PartsReader:

@@ -28,6 +28,7 @@
 #pragma GCC visibility push(hidden)
 
 #include "ragged_words.hpp"  // hidden like everything here: its templates export nothing
+#include "scrub_words.hpp"
 #include "segment_words.hpp"
 
 namespace cec {
@@ -335,6 +336,26 @@ int segments_launch(cec_codec* c, const uint8_t* data, const size_t* doffs, uint
                     const uint8_t* flags, uint8_t* midstates, uint8_t* digests, hipStream_t s,
                     uint8_t* hwords = nullptr, uint8_t* dwords = nullptr,
                     hipEvent_t before_hash = nullptr, hipEvent_t after_hash = nullptr);
+
+// ---- The segmented verification (ragged.cpp), as the scrub pipeline (scrub_pipeline.cpp) shares it. ----
+
+// A caller's own staging for verify_segments_launch: page-locked and device memory of the same
+// layout, [what the caller placed: the entries' bytes][at words_off, 16-byte aligned:
+// plan::scrub_words(n)].
+struct ScrubStage {
+    uint8_t *h, *d;
+    size_t words_off;
+};
+// The launch of a checked segmented verification on s: one upload, then the verifying resume
+// launch.  stage null: words from the scratch pool, expected / ok the caller's device memory;
+// else the words, the expected rows and the ok bytes are the staging's, and everything the staging
+// holds up to the rows' end goes up in the one copy.  The launch waits for `before` and `after` is
+// recorded behind it (either may be null).
+int verify_segments_launch(const uint8_t* base, const size_t* offs, const size_t* seg_lens,
+                           size_t n, const uint32_t* slots, const uint8_t* flags,
+                           uint8_t* midstates, const uint8_t* expected, uint8_t* ok, hipStream_t s,
+                           const ScrubStage* stage = nullptr, hipEvent_t before = nullptr,
+                           hipEvent_t after = nullptr);
 
 // ---- The ragged read (ragged.cpp), as the read pipeline (ragged_read_pipeline.cpp) shares it. ----
 

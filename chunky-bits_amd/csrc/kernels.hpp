@@ -251,6 +251,22 @@ struct ShaResumeParams {
     uint32_t n_items;
 };
 hipError_t launch_sha256_resume(const ShaResumeParams& a, hipStream_t s);
+// The same list with a verdict where a chain ends (sha256_resume_verify_kernel): flags[i] & 2
+// (LAST): the digest of the whole message is compared with the 32 bytes at expected + i * 32
+// (16-byte aligned) and ok[i] = 1 on equality, else 0; nothing else is written.  Not LAST: the
+// record is written as above, and not one byte of ok is touched.
+struct ShaVerifyResumeParams {
+    const uint64_t* ptrs;
+    const uint64_t* lens;
+    const uint32_t* order;
+    const uint32_t* record;
+    const uint8_t* flags;
+    uint8_t* midstates;
+    const uint8_t* expected;
+    uint8_t* ok;
+    uint32_t n_items;
+};
+hipError_t launch_sha256_resume_verify(const ShaVerifyResumeParams& a, hipStream_t s);
 hipError_t launch_fill(const FillParams& a, hipStream_t s);
 
 // Packed <-> batch chunk moves (move_kernels.hip): packed chunk j (len bytes at packed + j*len)

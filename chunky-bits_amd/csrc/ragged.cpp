@@ -1,7 +1,8 @@
 // ragged.cpp — the ragged half of include/chunky_ec.h: parts of different chunk lengths in one
 // launch sequence (cec_encode_hash_ragged, cec_encode_hash_split, cec_encode_hash_segments, which
 // takes parts as column segments and resumes their SHA-256 chains, cec_reconstruct_ragged,
-// cec_verify_ragged, cec_read_ragged, cec_resilver_ragged and their _async forms, which plan the
+// cec_verify_ragged, cec_verify_segments (copies as segments, their chains resumed and ended by a
+// verdict), cec_read_ragged, cec_resilver_ragged and their _async forms, which plan the
 // decode on the device and never wait, cec_read_ragged_packed_async among them) and the host-staged calls on top of
 // them (cec_parts_encode, cec_parts_read, cec_parts_verify).  Part k's chunk i lies at
 // base + off[k] + i * stride(L_k), stride = L rounded up to 16; the split layout keeps the parity
@@ -264,6 +265,44 @@ int cec::segments_launch(cec_codec* c, const uint8_t* data, const size_t* doffs,
                             digests,               uint32_t(items)};
     HIP_TRY(launch_sha256_resume(h, s));
     if (after_hash) HIP_TRY(hipEventRecord(after_hash, s));
+    return CEC_OK;
+}
+
+// The launch of a checked segmented verification on `s`: the words filled (scrub_words.hpp), one
+// upload, then the verifying resume launch over the n entries (sha256_resume_kernels.hip).  Entry k
+// is seg_lens[k] bytes at base + offs[k].  The host arrays are copied into the words' page-locked
+// side before this returns.  Without `stage` the words take a buffer of the scratch pool, only the
+// list goes up, and expected / ok are the caller's device rows and bytes.  With it the words lie
+// at stage->words_off of the caller's page-locked and device staging, whose bytes from 0 to the
+// end of the words' expected rows go up in the one copy (the caller filled the data before them
+// and the rows), and expected / ok are the words' own regions.  before / after: as segments_launch.
+int cec::verify_segments_launch(const uint8_t* base, const size_t* offs, const size_t* seg_lens,
+                                size_t n, const uint32_t* slots, const uint8_t* flags,
+                                uint8_t* midstates, const uint8_t* expected, uint8_t* ok,
+                                hipStream_t s, const ScrubStage* stage, hipEvent_t before,
+                                hipEvent_t after) {
+    const plan::ScrubWords w = plan::scrub_words(n);
+    Scratch sc;  // the words of a caller that has none: released on s behind the launch below
+    if (!stage) CEC_TRY(sc.acquire(w.resume.bytes, s));
+    const plan::View v = stage ? plan::View{stage->h + stage->words_off, stage->d + stage->words_off}
+                               : plan::View{sc.host(), sc.dev()};
+    plan::scrub_fill(reinterpret_cast<uint64_t>(base), offs, seg_lens, n, slots, flags, w.resume, v);
+    if (stage) {
+        HIP_TRY(hipMemcpyAsync(stage->d, stage->h, stage->words_off + w.up_bytes,
+                               hipMemcpyHostToDevice, s));
+        expected = v.dev(w.expected)->b;
+        ok = v.dev(w.ok);
+    } else {
+        HIP_TRY(hipMemcpyAsync(v.d, v.h, w.resume.bytes, hipMemcpyHostToDevice, s));
+    }
+    if (before) HIP_TRY(hipStreamWaitEvent(s, before, 0));
+    const plan::ShaListWords& l = w.resume.list;
+    const ShaVerifyResumeParams h{v.dev(l.ptrs),          v.dev(l.lens),         v.dev(l.order),
+                                  v.dev(w.resume.record), v.dev(w.resume.flags), midstates,
+                                  expected,               ok,                    uint32_t(n)};
+    const hipError_t e = launch_sha256_resume_verify(h, s);
+    if (e != hipSuccess) return hip_fail(e, "launch_sha256_resume_verify");
+    if (after) HIP_TRY(hipEventRecord(after, s));
     return CEC_OK;
 }
 
@@ -954,6 +993,36 @@ int cec_verify_ragged(size_t total_shards, const uint8_t* base, const size_t* pa
     CEC_TRY(current_device(&dev));
     return verify_ragged(base, part_offsets, chunk_lens, n_parts, total_shards, present, expected,
                          verified, static_cast<hipStream_t>(stream));
+}
+
+int cec_verify_segments(const uint8_t* base, const size_t* offsets, const size_t* seg_lens,
+                        size_t n_segs, const uint32_t* state_slots, const uint8_t* flags,
+                        uint8_t* midstates, size_t n_state_slots, const uint8_t* expected,
+                        uint8_t* ok, void* stream) {
+    if (n_segs == 0) return CEC_OK;
+    if (!base || !offsets || !seg_lens || !state_slots || !flags || !expected || !ok)
+        return CEC_ERR_INVALID_ARGUMENT;
+    // the kernel's item index is 32-bit (checked before the arrays are walked)
+    if (n_segs > 0xFFFFFFFFull) return CEC_ERR_INVALID_ARGUMENT;
+    if (!midstates && !plan::all_whole(flags, n_segs)) return CEC_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < n_segs; ++k)
+        if (seg_lens[k] == 0) return CEC_EMPTY_SHARD;
+    if (reinterpret_cast<uintptr_t>(midstates) % kRaggedAlign ||
+        reinterpret_cast<uintptr_t>(expected) % kRaggedAlign)
+        return CEC_ERR_INVALID_ARGUMENT;
+    CEC_TRY(ragged_check(1, base, offsets, seg_lens, n_segs));
+    static const char* const kRule[] = {
+        "", "an entry that is not CEC_SEG_LAST has a length that is no multiple of 64",
+        "a state slot is not below n_state_slots",
+        "two entries of one call name the same state slot"};
+    if (const int rule = plan::scrub_rules(seg_lens, state_slots, flags, n_segs, n_state_slots)) {
+        set_last_error(std::string("cec_verify_segments: ") + kRule[rule]);
+        return CEC_ERR_INVALID_ARGUMENT;
+    }
+    int dev = 0;
+    CEC_TRY(current_device(&dev));
+    return verify_segments_launch(base, offsets, seg_lens, n_segs, state_slots, flags, midstates,
+                                  expected, ok, static_cast<hipStream_t>(stream));
 }
 
 int cec_read_ragged(const cec_codec* c, uint8_t* base, const size_t* part_offsets,

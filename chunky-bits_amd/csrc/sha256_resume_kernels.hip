@@ -10,6 +10,10 @@
 //                        item's midstate record and an end that is the record again or the
 //                        padding and the digest.  List mode only; every launch size takes this
 //                        form (there is no producer/rounds split of it).
+//  sha256_resume_verify_kernel  the same lane (one template, resume_kernel) for the segmented scrub
+//                        (cec_verify_segments): where a chain ends, the eight state words are
+//                        compared with the item's expected digest and one flag byte is written;
+//                        no digest is stored.
 #include "device_common.hpp"
 #include "kernels.hpp"
 #include "segment_words.hpp"
@@ -25,7 +29,28 @@ using plan::kSegLast;
 
 constexpr int kResumeThreads = 256;  // four waves, one per SIMD of a CU (sha256_lane_kernel)
 
-__global__ __launch_bounds__(kResumeThreads) void sha256_resume_kernel(ShaResumeParams a) {
+// The end of a chain, by the launch's params: the digest stored (sha256_resume_kernel) ...
+__device__ __forceinline__ void finish_chain(const ShaResumeParams& a, uint32_t item,
+                                             const uint32_t st[8]) {
+    store_digest(a.digests + uint64_t(item) * 32u, st);
+}
+// ... or compared with the item's expected row, in finish_item's byte order (sha256_kernels.hip),
+// and one byte written (sha256_resume_verify_kernel).
+__device__ __forceinline__ void finish_chain(const ShaVerifyResumeParams& a, uint32_t item,
+                                             const uint32_t st[8]) {
+    const uint4* e = reinterpret_cast<const uint4*>(a.expected + uint64_t(item) * 32u);
+    const uint4 e0 = e[0], e1 = e[1];
+    const bool eq = e0.x == bswap32(st[0]) && e0.y == bswap32(st[1]) && e0.z == bswap32(st[2]) &&
+                    e0.w == bswap32(st[3]) && e1.x == bswap32(st[4]) && e1.y == bswap32(st[5]) &&
+                    e1.z == bswap32(st[6]) && e1.w == bswap32(st[7]);
+    a.ok[item] = eq ? 1 : 0;
+}
+
+// One lane's segment, start to end: both kernels are this template, the ending chosen by the
+// params' type (finish_chain).  The body stands in the kernel itself: as an inlined function the
+// compiler gave the existing kernel another SGPR count (86 for 88).
+template <class Params>
+__global__ __launch_bounds__(kResumeThreads) void resume_kernel(Params a) {
     extern __shared__ uint32_t cu_reservation[];  // never touched: occupancy control only
     const uint32_t g = blockIdx.x * uint32_t(kResumeThreads) + threadIdx.x;
     if (g >= a.n_items) return;
@@ -82,24 +107,46 @@ __global__ __launch_bounds__(kResumeThreads) void sha256_resume_kernel(ShaResume
         tail_words(p + 64 * nfull, rem, blk, tb, total * 8, w);
         compress(st, w);
     }
-    store_digest(a.digests + uint64_t(item) * 32u, st);
+    finish_chain(a, item, st);
+}
+
+constexpr auto sha256_resume_kernel = &resume_kernel<ShaResumeParams>;
+constexpr auto sha256_resume_verify_kernel = &resume_kernel<ShaVerifyResumeParams>;
+
+}  // namespace
+
+namespace {
+
+// One workgroup per 256 items under the lane kernel's reservation rule, whatever the size.
+template <class Params>
+hipError_t launch_resume(void (*kernel)(Params), bool attr_ok, const Params& a, hipStream_t s) {
+    if (a.n_items == 0) return hipSuccess;
+    if (!attr_ok) return hipErrorInvalidValue;
+    dim3 grid((a.n_items + uint32_t(kResumeThreads) - 1) / uint32_t(kResumeThreads));
+    clear_stale_error();
+    hipLaunchKernelGGL(kernel, grid, dim3(kResumeThreads), sha_lane_reservation(grid.x), s, a);
+    return hipGetLastError();
+}
+
+template <class Params>
+bool reserve_max(void (*kernel)(Params)) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               int(sha_lane_reservation_max())) == hipSuccess;
 }
 
 }  // namespace
 
-// One workgroup per 256 items under the lane kernel's reservation rule, whatever the size.
 hipError_t launch_sha256_resume(const ShaResumeParams& a, hipStream_t s) {
     if (a.n_items == 0) return hipSuccess;
-    static const bool attr_ok =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&sha256_resume_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            int(sha_lane_reservation_max())) == hipSuccess;
-    if (!attr_ok) return hipErrorInvalidValue;
-    dim3 grid((a.n_items + uint32_t(kResumeThreads) - 1) / uint32_t(kResumeThreads));
-    clear_stale_error();
-    hipLaunchKernelGGL(sha256_resume_kernel, grid, dim3(kResumeThreads),
-                       sha_lane_reservation(grid.x), s, a);
-    return hipGetLastError();
+    static const bool attr_ok = reserve_max(sha256_resume_kernel);
+    return launch_resume(sha256_resume_kernel, attr_ok, a, s);
+}
+
+hipError_t launch_sha256_resume_verify(const ShaVerifyResumeParams& a, hipStream_t s) {
+    if (a.n_items == 0) return hipSuccess;
+    static const bool attr_ok = reserve_max(sha256_resume_verify_kernel);
+    return launch_resume(sha256_resume_verify_kernel, attr_ok, a, s);
 }
 
 }  // namespace cec

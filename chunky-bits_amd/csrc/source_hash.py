@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Source hash of libchunky_ec.so: SHA-256 over the library's sources (every csrc/*.cpp, *.hip,
 *.hpp, the Makefile, include/chunky_ec.h, include/chunky_ec_parts.h,
-include/chunky_ec_parts_read.h and include/chunky_ec_segments.h), each as its path relative to the repo root, a NUL,
+include/chunky_ec_parts_read.h, include/chunky_ec_segments.h and include/chunky_ec_scrub.h), each as its path relative to the repo root, a NUL,
 its bytes and a NUL, in sorted path order; printed as 16 hex digits.
 
 The Makefile compiles this value into the library (`cec_build_id()`), and chunky_ec refuses on
@@ -23,6 +23,7 @@ def source_files(root: str = ROOT):
     files.append(os.path.join(root, "include", "chunky_ec_parts.h"))
     files.append(os.path.join(root, "include", "chunky_ec_parts_read.h"))
     files.append(os.path.join(root, "include", "chunky_ec_segments.h"))
+    files.append(os.path.join(root, "include", "chunky_ec_scrub.h"))
     return sorted(os.path.relpath(f, root) for f in files)
 
 

@@ -44,6 +44,11 @@ pub mod sys {
     }
 
     #[repr(C)]
+    pub struct cec_scrub_pipeline {
+        _private: [u8; 0],
+    }
+
+    #[repr(C)]
     pub struct cec_multi {
         _private: [u8; 0],
     }
@@ -793,6 +798,69 @@ pub mod sys {
             pub fn cec_segment_pipeline_open_count(pipeline: *const cec_segment_pipeline) -> usize;
             pub fn cec_segment_pipeline_abandon(
                 pipeline: *mut cec_segment_pipeline,
+                id: u32,
+            ) -> c_int;
+        }
+    }
+
+    /// include/chunky_ec_scrub.h: the segmented scrub (resumable SHA-256 verification over
+    /// segments of stored copies) and the scrub pipeline, function for function.  Declarations
+    /// only: the crate has no loop on top of them.  The entry flags are `segments::CEC_SEG_*`.
+    pub mod scrub {
+        use super::*;
+
+        extern "C" {
+            pub fn cec_verify_segments(
+                base: *const u8,
+                offsets: *const usize,
+                seg_lens: *const usize,
+                n_segs: usize,
+                state_slots: *const u32,
+                flags: *const u8,
+                midstates: *mut u8,
+                n_state_slots: usize,
+                expected: *const u8,
+                ok: *mut u8,
+                stream: *mut c_void,
+            ) -> c_int;
+            pub fn cec_scrub_pipeline_new(
+                slot_bytes: usize,
+                max_entries: usize,
+                depth: usize,
+                max_open: usize,
+                out: *mut *mut cec_scrub_pipeline,
+            ) -> c_int;
+            pub fn cec_scrub_pipeline_free(pipeline: *mut cec_scrub_pipeline);
+            pub fn cec_scrub_pipeline_depth(pipeline: *const cec_scrub_pipeline) -> usize;
+            pub fn cec_scrub_pipeline_acquire(
+                pipeline: *mut cec_scrub_pipeline,
+                slot: *mut usize,
+            ) -> c_int;
+            pub fn cec_scrub_pipeline_submit_from(
+                pipeline: *mut cec_scrub_pipeline,
+                slot: usize,
+                bufs: *const *const u8,
+                lens: *const usize,
+                seg_offsets: *const usize,
+                seg_lens: *const usize,
+                open_ids: *const u32,
+                expected: *const u8,
+                n: usize,
+            ) -> c_int;
+            pub fn cec_scrub_pipeline_wait(
+                pipeline: *mut cec_scrub_pipeline,
+                slot: usize,
+                ok: *mut *const u8,
+                n: *mut usize,
+            ) -> c_int;
+            pub fn cec_scrub_pipeline_query(
+                pipeline: *mut cec_scrub_pipeline,
+                slot: usize,
+            ) -> c_int;
+            pub fn cec_scrub_pipeline_drain(pipeline: *mut cec_scrub_pipeline) -> c_int;
+            pub fn cec_scrub_pipeline_open_count(pipeline: *const cec_scrub_pipeline) -> usize;
+            pub fn cec_scrub_pipeline_abandon(
+                pipeline: *mut cec_scrub_pipeline,
                 id: u32,
             ) -> c_int;
         }

@@ -785,5 +785,7 @@ uint8_t cec_synth_byte(uint64_t seed, uint64_t part, uint64_t chunk, uint64_t of
 #include "chunky_ec_parts_read.h"
 /* And the segmented ragged writes (cec_encode_hash_segments, cec_segment_pipeline_*). */
 #include "chunky_ec_segments.h"
+/* And the segmented scrub (cec_verify_segments, cec_scrub_pipeline_*). */
+#include "chunky_ec_scrub.h"
 
 #endif /* CHUNKY_EC_H */

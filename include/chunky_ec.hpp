@@ -430,6 +430,32 @@ inline cec_segment_pipeline* cached_segment_pipeline(size_t d, size_t p, size_t 
     return e.pipe.get();
 }
 
+// The calling thread's most recent scrub pipeline (FileReference::verify_many_stream), kept the
+// same way: per (slot bytes, entries per slot, depth, open copies) and device.  It has no codec.
+struct CachedScrubPipeline {
+    std::vector<size_t> key;
+    std::shared_ptr<cec_scrub_pipeline> pipe;
+};
+inline CachedScrubPipeline& cached_scrub_pipeline_entry() {
+    thread_local CachedScrubPipeline e;
+    return e;
+}
+inline cec_scrub_pipeline* cached_scrub_pipeline(size_t slot_bytes, size_t max_entries,
+                                                 size_t depth, size_t max_open) {
+    CachedScrubPipeline& e = cached_scrub_pipeline_entry();
+    int device = 0;
+    check(cec_current_device(&device));
+    const std::vector<size_t> key{slot_bytes, max_entries, depth, max_open, size_t(device)};
+    if (!e.pipe || e.key != key) {
+        e.pipe.reset();
+        cec_scrub_pipeline* raw = nullptr;
+        check(cec_scrub_pipeline_new(slot_bytes, max_entries, depth, max_open, &raw));
+        e.pipe = std::shared_ptr<cec_scrub_pipeline>(raw, cec_scrub_pipeline_free);
+        e.key = key;
+    }
+    return e.pipe.get();
+}
+
 // The calling thread's most recent ragged read pipeline (FileReference::read_many_stream), kept
 // the same way: per (d, p, slot bytes, parts per slot, depth) and device.
 struct CachedPartsReader {
@@ -1267,6 +1293,121 @@ struct FileReference {
             });
         }
         window.flush(flush);
+        return out;
+    }
+
+    // verify_many(files, src) as a stream (a scrub of a whole store): the same reports, report for
+    // report, through the scrub pipeline (chunky_ec_scrub.h) in place of one cec_parts_verify call
+    // per window.  Every copy the skeleton rule leaves to be checked goes through as segments of
+    // at most segment_bytes (a multiple of 64), one per batch, its SHA-256 chain resumed from a
+    // record on the device, so that no batch waits for a chain longer than one segment; batches of
+    // up to slot_bytes of padded segments are planned by detail::SegmentPlanner (a copy is a part
+    // of one chunk) and `depth` of them are in flight.  max_open: copies under way at most (0: as
+    // many as a slot holds segments).  A part's report is summarised once all of its copies have
+    // ended; parts with empty chunks go through part.verify.  The copies are read where they lie
+    // in `src`, which must not be written during the call.  verify_many stays the default: which
+    // of the two is faster is a measurement.
+    static constexpr size_t kScrubSlotEntries = 4096;  // entries a slot's batch holds at most
+    static std::vector<std::vector<PartReport>> verify_many_stream(
+        const std::vector<const FileReference*>& files, const ChunkStore& src,
+        size_t segment_bytes = 16384, size_t slot_bytes = size_t(64) << 20, size_t depth = 3,
+        size_t max_open = 0) {
+        struct Copy {
+            const uint8_t* bytes;
+            const uint8_t* digest;
+            LocationIntegrity* where;
+            size_t report;  // index into `pending`
+        };
+        struct Pending {
+            PartReport* rep;
+            size_t left;  // copies that have not ended
+        };
+        std::vector<Copy> copies;
+        std::vector<size_t> lens;
+        std::vector<Pending> pending;
+        std::vector<std::vector<PartReport>> out(files.size());
+        for (size_t f = 0; f < files.size(); ++f) {
+            const FileReference& file = *files[f];
+            out[f].resize(file.parts.size());
+            for (size_t k = 0; k < file.parts.size(); ++k) {
+                const FilePart& part = file.parts[k];
+                PartReport& rep = out[f][k];
+                if (part.chunksize == 0) {  // no engine call takes an empty chunk
+                    rep = part.verify(src);
+                    continue;
+                }
+                if (skeleton_report(src, part, rep) == 0) {
+                    rep.summarize();
+                    continue;
+                }
+                pending.push_back({&rep, 0});
+                for_each_copy(rep, false, [&](size_t i, size_t j) {
+                    const Chunk& c = part.chunk(i);
+                    copies.push_back({src.find(c.locations[j])->data(), c.hash.digest().data(),
+                                      &rep.locations[i][j], pending.size() - 1});
+                    lens.push_back(part.chunksize);
+                    ++pending.back().left;
+                });
+            }
+        }
+        if (copies.empty()) return out;
+        if (!max_open && segment_bytes)
+            max_open = slot_bytes / detail::SegmentPlanner::stride16(segment_bytes);
+        detail::SegmentPlanner plan(1, segment_bytes, slot_bytes, kScrubSlotEntries, max_open, lens);
+        cec_scrub_pipeline* pl =
+            detail::cached_scrub_pipeline(slot_bytes, kScrubSlotEntries, depth, max_open);
+        struct Batch {
+            size_t slot;
+            std::vector<detail::SegmentEntry> entries;
+        };
+        std::deque<Batch> flying;  // oldest first
+        auto collect = [&] {
+            Batch b = std::move(flying.front());
+            flying.pop_front();
+            const uint8_t* ok = nullptr;
+            size_t got = 0;
+            detail::check(cec_scrub_pipeline_wait(pl, b.slot, &ok, &got));
+            if (got != b.entries.size())
+                throw std::logic_error("verify_many_stream: a slot lost its batch");
+            for (size_t q = 0; q < got; ++q) {
+                if (!b.entries[q].last) continue;
+                const Copy& c = copies[b.entries[q].part];
+                *c.where = ok[q] ? LocationIntegrity::Valid : LocationIntegrity::Invalid;
+                if (--pending[c.report].left == 0) pending[c.report].rep->summarize();
+            }
+        };
+        try {
+            while (!plan.planned()) {
+                if (flying.size() == depth) collect();  // the slot that comes round next
+                Batch b{0, plan.next_batch()};
+                const size_t m = b.entries.size();
+                std::vector<const uint8_t*> bufs(m);
+                std::vector<size_t> lengths(m), offs(m), segs(m);
+                std::vector<uint32_t> ids(m);
+                std::vector<uint8_t> expected(m * 32, 0);
+                for (size_t q = 0; q < m; ++q) {
+                    const detail::SegmentEntry& e = b.entries[q];
+                    bufs[q] = copies[e.part].bytes;
+                    lengths[q] = lens[e.part];
+                    offs[q] = e.off;
+                    segs[q] = e.len;
+                    ids[q] = e.id;
+                    if (e.last) std::memcpy(&expected[q * 32], copies[e.part].digest, 32);
+                }
+                detail::check(cec_scrub_pipeline_acquire(pl, &b.slot));
+                detail::check(cec_scrub_pipeline_submit_from(pl, b.slot, bufs.data(),
+                                                             lengths.data(), offs.data(),
+                                                             segs.data(), ids.data(),
+                                                             expected.data(), m));
+                flying.push_back(std::move(b));
+            }
+            while (!flying.empty()) collect();
+        } catch (...) {  // nothing of this call stays in flight or open
+            (void)cec_scrub_pipeline_drain(pl);
+            for (size_t id = 0; id < max_open; ++id)
+                (void)cec_scrub_pipeline_abandon(pl, uint32_t(id));
+            throw;
+        }
         return out;
     }
 

@@ -81,12 +81,24 @@ encodes it and every one of its d + p chunks is hashed and compared with its dig
 Every arm must find every chunk good, and the one chunk that is flipped before the run bad
 (asserted).
 
+--verify --segment BYTES[,BYTES...]: the same copies, one in 97 of them damaged (its first, a
+middle or its last byte), through two arms that alternate three times after a warm-up: (a) the one
+cec_parts_verify call (arm b above) and (c) the scrub pipeline, cec_scrub_pipeline_submit_from,
+one arm per segment size and --depths entry: a copy longer than the segment goes as segments, one
+per batch, each batch first taking the next segment of every open copy (--max-open at most;
+default: as many as a slot holds segments) and then new copies while the slot lasts (the plan, the
+pointer tables and the expected rows are made before the clock starts).  The flags of the entries
+that end a copy are copied out.  Every arm's flags must equal arm a's and the damage done
+(asserted).  Reported: GB/s of copy bytes per repeat, the batches and the most copies open; arm c
+counts as faster only if its worst repeat is above arm a's best.
+
     python tools/small_files_bench.py [--files 4096] [--repeats 3] [--shapes 3,2:10,4]
                                       [--slot-mib 64] [--depths 3,2] [--no-per-part]
     python tools/small_files_bench.py --segment 16384,65536,262144 [--slot-mib 64] [--depths 3,2]
     python tools/small_files_bench.py --device
     python tools/small_files_bench.py --read [--slot-mib 64] [--depths 3,2] [--no-per-part]
     python tools/small_files_bench.py --verify
+    python tools/small_files_bench.py --verify --segment 16384,65536 [--slot-mib 64] [--depths 3,2]
     python tools/small_files_bench.py --device --read"""
 import argparse
 import ctypes
@@ -872,6 +884,104 @@ class VerifyWorkload:
                                            self.expected.ctypes.data_as(U8P),
                                            self.ok.ctypes.data_as(U8P)))
 
+    def damage_more(self, every=97):
+        """One byte flipped in every `every`-th copy beyond the constructor's one: its first, a
+        middle or its last byte in turn."""
+        t = self.t
+        for x in range(0, self.n * t, every):
+            k, i = divmod(x, t)
+            if not self.want[k, i]:
+                continue
+            L = self.L[k]
+            self.store[int(self.off[k]) + i * L + (0, L // 2, L - 1)[(x // every) % 3]] ^= 0x20
+            self.want[k, i] = 0
+
+    def make_scrub_pipeline(self, slot_bytes, depth, segment, max_entries=4096, max_open=None):
+        """A cec_scrub_pipeline and the plan of its batches, made before any clock starts: each
+        batch takes the next segment of every open copy, in copy order, then new copies while the
+        slot, max_entries and the open ids last (the rule of FileReference::verify_many_stream).
+        Per batch: the call's arrays (the expected rows of the entries that end a copy among
+        them) and, for those entries, their rows and copies."""
+        t, n = self.t, self.n * self.t
+        lens = [L for L in self.L for _ in range(t)]
+        slot_bytes = max(slot_bytes, ce.ragged_stride(min(segment, max(lens))))
+        if not max_open:  # as many open copies as a slot holds segments (the C++ default)
+            max_open = max(1, slot_bytes // ce.ragged_stride(segment))
+        pl = ce.ScrubPipeline(slot_bytes, max_entries, depth, max_open)
+        exp = self.expected.reshape(n, 32)
+        free, open_copies, nxt, plan, most_open = list(range(max_open))[::-1], [], 0, [], 0
+        while nxt < n or open_copies:
+            batch, room, still, freed = [], slot_bytes, [], []
+
+            def fits(ln):
+                return len(batch) < max_entries and ce.ragged_stride(ln) <= room
+            for x, done, oid in open_copies:
+                ln = min(segment, lens[x] - done)
+                if not fits(ln):
+                    still.append((x, done, oid))
+                    continue
+                batch.append((x, done, ln, oid))
+                room -= ce.ragged_stride(ln)
+                if done + ln == lens[x]:
+                    freed.append(oid)
+                else:
+                    still.append((x, done + ln, oid))
+            while nxt < n:
+                ln = min(segment, lens[nxt])
+                whole = ln == lens[nxt]
+                if not fits(ln) or (not whole and not free):
+                    break
+                oid = 0 if whole else free.pop()
+                if not whole:
+                    still.append((nxt, ln, oid))
+                batch.append((nxt, 0, ln, oid))
+                room -= ce.ragged_stride(ln)
+                nxt += 1
+            free += freed
+            open_copies = still
+            most_open = max(most_open, len(still))
+            m = len(batch)
+            last = [q for q, (x, off, ln, _) in enumerate(batch) if off + ln == lens[x]]
+            rows = np.zeros((m, 32), np.uint8)
+            rows[last] = exp[[batch[q][0] for q in last]]
+            plan.append({
+                "m": m,
+                "bufs": (U8P * m)(*[self.all_ptrs[x] for x, _, _, _ in batch]),
+                "lens": (ctypes.c_size_t * m)(*[lens[x] for x, _, _, _ in batch]),
+                "offs": (ctypes.c_size_t * m)(*[e[1] for e in batch]),
+                "segs": (ctypes.c_size_t * m)(*[e[2] for e in batch]),
+                "ids": (ctypes.c_uint32 * m)(*[e[3] for e in batch]),
+                "rows": rows,
+                "last_rows": np.array(last, np.int64),
+                "last_copies": np.array([batch[q][0] for q in last], np.int64)})
+        return pl, plan, most_open
+
+    def arm_scrub(self, pipe):
+        """Every planned batch through the scrub pipeline's slots; while later slots run the
+        oldest is collected: the flags of the entries that end a copy copied into self.ok."""
+        pl, plan, _ = pipe
+        lib, h = ce._lib, pl._h
+        flat = self.ok.reshape(-1)
+        slot, okp, n = ctypes.c_size_t(0), U8P(), ctypes.c_size_t(0)
+        pending = []
+
+        def collect():
+            s, b = pending.pop(0)
+            ce._check(lib.cec_scrub_pipeline_wait(h, s, ctypes.byref(okp), ctypes.byref(n)))
+            assert n.value == b["m"]
+            flat[b["last_copies"]] = np.ctypeslib.as_array(okp, shape=(b["m"],))[b["last_rows"]]
+        for b in plan:
+            if len(pending) == pl.depth:
+                collect()
+            ce._check(lib.cec_scrub_pipeline_acquire(h, ctypes.byref(slot)))
+            ce._check(lib.cec_scrub_pipeline_submit_from(
+                h, slot.value, b["bufs"], b["lens"], b["offs"], b["segs"], b["ids"],
+                b["rows"].ctypes.data_as(U8P), b["m"]))
+            pending.append((slot.value, b))
+        while pending:
+            collect()
+        assert pl.open_count() == 0
+
     def arm_cpu(self, threads=16, count=None):
         lib = oracle.lib()
         t = self.t
@@ -927,6 +1037,63 @@ def host_verify(args):
                         "b_faster_each_repeat": wins})
         del w
     print(json.dumps({"tool": "small_files_bench", "mode": "host-verify", "results": results}))
+
+
+def host_verify_segments(args):
+    """--verify --segment: the one parts_verify call (arm a) and the scrub pipeline at these
+    segment sizes (arm c) over the same copies, some of them damaged, alternating."""
+    pool, files = make_files(args.files)
+    results = []
+    slot = args.slot_mib << 20
+    for shape in args.shapes.split(":"):
+        d, p = (int(x) for x in shape.split(","))
+        w = VerifyWorkload(pool, files, d, p)
+        w.damage_more()
+        print(f"== scrub RS({d},{p}) chunk 1 MiB: {len(files)} files, "
+              f"{w.stored_bytes / 2**30:.2f} GiB of chunks, {w.n} parts, {w.n * w.t} copies, "
+              f"{int((w.want == 0).sum())} of them damaged, longest copy {max(w.L)} bytes",
+              flush=True)
+        arms = [("a: one parts_verify call", w.arm_ragged)]
+        info = {}
+        for seg in args.segment:
+            for depth in args.depths:
+                size = f"{seg >> 10} KiB" if seg % 1024 == 0 else f"{seg} B"
+                name = f"c: scrub pipeline {size} segments, {args.slot_mib} MiB x {depth}"
+                pipe = w.make_scrub_pipeline(slot, depth, seg, max_open=args.max_open)
+                arms.append((name, lambda pipe=pipe: w.arm_scrub(pipe)))
+                info[name] = {"batches": len(pipe[1]), "max_open": pipe[0].max_open,
+                              "most_open": pipe[2]}
+                print(f"   {name}: {len(pipe[1])} batches, up to {pipe[2]} copies open "
+                      f"(of {pipe[0].max_open} ids)", flush=True)
+        for name, fn in arms:
+            w.ok[:] = 7
+            sec, _ = timed(fn)
+            assert np.array_equal(w.ok, w.want), f"flags of '{name}' differ (warm-up)"
+            print(f"   warm-up {name}: {sec:.3f} s", flush=True)
+        secs = {name: [] for name, _ in arms}
+        for rep in range(args.repeats):
+            for name, fn in arms:
+                w.ok[:] = 7
+                sec, _ = timed(fn)
+                secs[name].append(sec)
+                assert np.array_equal(w.ok, w.want), f"flags of '{name}' differ"
+                print(f"   repeat {rep + 1} {name}: {sec:.3f} s  "
+                      f"{w.stored_bytes / sec / 1e9:7.2f} GB/s of copies", flush=True)
+        print("   every arm's flags equal arm a's (and the damage done), in every repeat")
+        gbps = {k: [w.stored_bytes / x / 1e9 for x in v] for k, v in secs.items()}
+        row = {"d": d, "p": p, "files": len(files), "parts": w.n, "copies": w.n * w.t,
+               "stored_bytes": w.stored_bytes, "seconds": secs, "gbps_stored": gbps,
+               "pipelines": info, "verdicts": {}}
+        inc = arms[0][0]
+        for name in info:
+            wins = min(gbps[name]) > max(gbps[inc])
+            row["verdicts"][f"{name} over {inc}"] = wins
+            print(f"   {name}: {min(gbps[name]):.2f}-{max(gbps[name]):.2f} GB/s against {inc}: "
+                  f"{min(gbps[inc]):.2f}-{max(gbps[inc]):.2f} GB/s -> worst above the "
+                  f"incumbent's best: {wins}", flush=True)
+        results.append(row)
+        del w, arms
+    print(json.dumps({"tool": "small_files_bench", "mode": "verify-segment", "results": results}))
 
 
 def device_read(args):
@@ -1324,7 +1491,8 @@ def main():
     ap.add_argument("--segment", type=lambda s: [int(x) for x in s.split(",")], default=None,
                     metavar="BYTES[,BYTES...]",
                     help="the one call, the parts pipeline and the segment pipeline at these "
-                         "segment sizes (multiples of 64 bytes)")
+                         "segment sizes (multiples of 64 bytes); with --verify: the one "
+                         "parts_verify call and the scrub pipeline")
     ap.add_argument("--max-open", type=int, default=0,
                     help="--segment: parts under way at most (0: as many as a slot holds segments)")
     ap.add_argument("--device", action="store_true")
@@ -1332,7 +1500,9 @@ def main():
     ap.add_argument("--verify", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
-    if args.segment:
+    if args.segment and args.verify:
+        host_verify_segments(args)
+    elif args.segment:
         host_segments(args)
     elif args.device:
         if args.read:
